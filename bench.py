@@ -2,6 +2,8 @@
 
     python bench.py --gpus N --steps K --warmup W           (N > 1 without a launcher: bench.py starts the N ranks itself, as
                                                              children of a parent that never touches the GPU)
+    python bench.py --gpus 1 --steps K --warmup W --full    (+ the measurements beside the headline, see below)
+    python bench.py ... --dump-outputs DIR                  (+ what the timed path returned, as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (config 2 of BASELINE.json = configs[1]): one 1024x1024 synthetic target per GPU, literal-mode projection
@@ -21,7 +23,8 @@ Weights are seeded synthetic tensors (no checkpoint exists offline); inputs are 
 N > 1: one independent target per rank (pair-level sharding, no data-path collective) -> "weak" scaling; the only collective is the
 result gather after the timed region.  `--workload config3` is the list-of-targets shape of BASELINE config 3 (see its help).
 
-Rank 0 prints ONE JSON line.  Extra objects (rank 0, N = 1): "roofline" (the MFMA conv kernel with the largest total time: executed
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the run's configuration).  With `--full`, extra objects (rank 0, N = 1): "roofline" (the MFMA conv kernel with the largest total time: executed
 FLOPs / event-measured launch time vs the dense FP32-MFMA peak, PMC traffic and mfma_busy from the committed passes),
 "generator_forward", "gradient_mode" (the loss back-propagated into the latent, Adam; one target and --gradient-lockstep targets),
 "many_targets" (projections/s set-up included), "objectives" (the LPIPS(vgg) loop and config 3's four-term loop with the FaceNet
@@ -135,6 +138,14 @@ def parse():
                          "dlib (...sqz_MSE.py:159-170) -- the detector is a no-op stub (dlib is closed / absent), so the figure is what the engine's "
                          "host detour costs: the gray uint8 image built on the device, 1 MB per candidate to pinned host memory, one host->device "
                          "copy of the landmark rows, two hipGraphs per launch sequence")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline (rank 0, after the timed steps): roofline and generator-forward legs, "
+                         "gradient mode, many targets, config 4 / 5, objectives, bf16x3 mode, landmark callback, CPU baseline -- each can still be "
+                         "switched off by its own option.  Without --full a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returns to its caller (rank 0's ProjectionEngine.result(): best latent, "
+                         "best step, best loss, the loss history of every iteration run, and the losses of the last timed step) as DIR/<name>.npy in "
+                         "float32 / float64; the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group even for one rank (exercises the N>1 code path)")
     ap.add_argument("--force-launch", action="store_true", help="self-launch through torch.distributed.run even for --gpus 1 (exercises the launcher)")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)      # CPU/gloo dry run of the launcher (tests/)
@@ -708,6 +719,19 @@ def cpu_baseline_leg(sd, cfg, target, latent_mean, latent_std, lms, iters):
                       f"{cores} threads; {per:.2f} s/iter"}
 
 
+def dump_outputs(out_dir, latent, best_step, best_loss, losses, iters_run, batch):
+    """--dump-outputs: what ProjectionEngine.result() hands its caller after the timed steps, as DIR/<name>.npy -- the best latent (float32),
+    best step and best loss (float64 scalars), the loss history of the `iters_run` iterations run so far (warm-up + timed; the engine's
+    array is pre-sized and NaN beyond them) and the `batch` losses of the last timed step (float64).  A few kB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    hist = np.asarray(losses, dtype=np.float64)[:iters_run]
+    arrays = {"best_latent": latent.numpy().astype(np.float32), "best_step": np.float64(best_step), "best_loss": np.float64(best_loss),
+              "losses": hist, "last_step_losses": hist[iters_run - batch:]}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.asarray(arr))
+    log(f"wrote {', '.join(sorted(arrays))} to {out_dir}")
+
+
 def self_launch(a):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves -- `python -m torch.distributed.run` as a CHILD
     process, from a parent that has made no GPU call (nothing here imports torch; re-exec'ing a process that initialised HIP is what
@@ -949,6 +973,9 @@ def main():
     # EXACTLY K timed steps; `value` stays loop iterations per second (K * batch / elapsed).
     seqs, warm = a.steps, a.warmup
     steps = seqs * a.batch                             # loop iterations inside the timed region
+    # the per-layer noise of noise_mode="random" is keyed off torch's CUDA generator (Generator._draw_noise): seeded here, the run's inputs
+    # -- weights, target, landmarks, perturbations and noise -- are the same from run to run
+    torch.manual_seed(rank)
     sd, G, percept, eng, target, latent_mean, latent_std, lms = build(cfg, device, rank, (seqs + warm + 4) * a.batch, not a.no_graph, a.batch,
                                                                       a.biometric, bool(a.pipeline), a.lpips_net, a.arith)
 
@@ -978,7 +1005,7 @@ def main():
         # result gather (the only collective of the path): {latent, best loss, best step} per rank -- timed (second call: the first
         # one may include communicator set-up for this message size)
         from morphganformer_amd.distributed import gather_results
-        lat, bstep, bloss, _ = eng.result()
+        lat, bstep, bloss, losses = eng.result()
         lat_d = lat.to(device)
         gathered = gather_results(lat_d, bloss, bstep)
         torch.cuda.synchronize()
@@ -988,7 +1015,9 @@ def main():
         rank_stats = {"per_rank_iters_per_s": [round(v, 3) for v in per_rank], "gather_ms": round((time.perf_counter() - tg) * 1e3, 3)}
         assert gathered["latents"].shape[0] == world
     else:
-        eng.result()
+        lat, bstep, bloss, losses = eng.result()
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, lat, bstep, bloss, losses, (max(warm, 1) + seqs) * a.batch, a.batch)
     pr = rank_stats["per_rank_iters_per_s"]
     rank_stats.update(rank_min=min(pr), rank_max=max(pr), rank_mean=round(sum(pr) / len(pr), 3))
 
@@ -1008,7 +1037,7 @@ def main():
                    "lpips_backbone": f"seeded random {a.lpips_net} weights (torchvision's are a remote fetch) + the reference's vendored lin heads",
                    "timed_region": f"{seqs} steps = {seqs} hipGraph replays of {a.batch} loop iterations each = {steps} iterations"},
     }
-    if rank == 0:
+    if rank == 0 and a.full:
         out["roofline"] = roofline_leg(eng)
         out["generator_forward"] = generator_leg(eng)
         log(f"roofline leg done: {out['roofline']['kernel']} {out['roofline']['achieved']} TFLOP/s executed")
@@ -1074,6 +1103,7 @@ def main():
             except Exception as exc:        # noqa: BLE001 -- the measured GPU line is still printed, with the failure recorded
                 out["cpu_baseline"] = {"value": None, "error": f"{type(exc).__name__}: {exc}"}
                 log(f"cpu baseline leg failed: {exc}")
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

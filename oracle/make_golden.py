@@ -631,6 +631,62 @@ def gold_lpips_dist():
     print("lpips_dist: full val", out["full_val"].reshape(-1))
 
 
+# stands in for the module source the reference's persistence machinery embeds in every pickle: the fixture carries no reference code,
+# and the test checks that reading the file never executes it (executing it would register the marker module)
+PICKLE_SRC_MARKER = "mgf_fixture_module_src_executed"
+PICKLE_PLACEHOLDER_SRC = f"import sys\nsys.modules['{PICKLE_SRC_MARKER}'] = sys\n\nclass Generator:\n    pass\n"
+
+
+def gold_reference_pickle(ref):
+    """ref_pickle_tiny.pkl.gz: the reference Generator (TINY, seed 5) pickled as dict(G=G, D=G, Gs=G) by the reference's own
+    persistence machinery (torch_utils/persistence.py: _reconstruct_persistent_obj + meta), with the embedded module source replaced
+    by PICKLE_PLACEHOLDER_SRC."""
+    import gzip
+    import pickle
+    from morphganformer_amd.synth_weights import TINY, make_state_dict
+    G = build_reference_generator(ref, TINY, make_state_dict(TINY, seed=5))
+    classes = {type(m) for m in G.modules() if hasattr(type(m), "_orig_module_src")}
+    saved = {c: c._orig_module_src for c in classes}
+    try:
+        for c in classes:
+            c._orig_module_src = PICKLE_PLACEHOLDER_SRC
+        data = pickle.dumps(dict(G=G, D=G, Gs=G))
+    finally:
+        for c, src in saved.items():
+            c._orig_module_src = src
+    with gzip.GzipFile(os.path.join(OUT, "ref_pickle_tiny.pkl.gz"), "wb", mtime=0) as f:
+        f.write(data)
+
+
+def tf_state_digest(v):
+    """sha256 of one converted tensor (float32 values, -0 folded into +0, shape included): what tf_convert_mini256.npz pins."""
+    import hashlib
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.float32) + np.float32(0))
+    return hashlib.sha256(repr(a.shape).encode() + a.tobytes()).hexdigest()
+
+
+def gold_tf_conversion(ref):
+    """tf_convert_mini256.npz: the reference's convert_tf_generator (loader.py:91-247) on the synthetic TF-layout snapshot of
+    tests/test_host_and_abi.py (_mini256(), make_state_dict seed 7) -- every key of its state_dict with a digest of the tensor, and
+    the grid_pos tensors themselves (compared to 1e-6: computed, not copied)."""
+    import importlib
+    from morphganformer_amd.synth_weights import make_state_dict
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_host_and_abi import _mini256, _tf_stub_from_state
+    ref_loader = importlib.import_module("loader")
+    cfg = _mini256()
+    stub = _tf_stub_from_state(make_state_dict(cfg, seed=7), cfg)
+
+    def to_ref(s_):
+        return ref_loader._TFNetworkStub(version=s_["version"], static_kwargs=dict(s_["static_kwargs"]), variables=list(s_["variables"]),
+                                         components={k: to_ref(v) for k, v in s_["components"].items()})
+    want = {k: v.detach().numpy() for k, v in ref_loader.convert_tf_generator(to_ref(stub)).state_dict().items()}
+    keys = sorted(want)
+    out = {"keys": np.array(keys), "digests": np.array([tf_state_digest(want[k]) for k in keys])}
+    out.update({f"grid_pos/{k}": want[k] for k in keys if k.endswith("grid_pos")})
+    np.savez_compressed(os.path.join(OUT, "tf_convert_mini256.npz"), **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     sys.path.insert(0, ROOT)
@@ -643,6 +699,10 @@ def main():
     if only:
         if "lpips" in only:
             gold_lpips_dist()
+        if "pickle" in only:
+            gold_reference_pickle(ref)
+        if "tfconvert" in only:
+            gold_tf_conversion(ref)
         # regenerate a subset without touching the other fixtures
         if "config0" in only:
             gold_config0_256(ref)
@@ -680,6 +740,8 @@ def main():
     gold_config0_256(ref)
     gold_iresnet()
     gold_lpips_dist()
+    gold_reference_pickle(ref)
+    gold_tf_conversion(ref)
     if "--no-full" not in sys.argv:
         gold_generator_full(ref)
         gold_grad_full(ref)

@@ -462,7 +462,7 @@ def test_bench_force_dist_runs_the_rccl_path():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--gradient-steps", "0",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--gradient-steps", "0",
            "--targets", "0", "--objectives", "0", "--landmark-callback", "none", "--config4", "0", "--config5-targets", "0", "--bf16x3-leg", "0"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -472,6 +472,42 @@ def test_bench_force_dist_runs_the_rccl_path():
     assert d["rccl_ranks"] == 1 and d["n_gpus"] == 1 and d["value"] > 0
     assert d["ranks"]["gather_ms"] is not None and len(d["ranks"]["per_rank_iters_per_s"]) == 1
     assert d["roofline"]["frac"] > 0.3
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run in a CHILD process prints the headline line and none of the --full legs, and `--dump-outputs DIR` writes what
+    the timed path returned to its caller: ProjectionEngine.result() after 1 warm-up + 2 timed steps of 32 iterations each.  A second run
+    with the same arguments dumps the same arrays (seeded inputs, random per-layer noise included)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+
+    def run(out):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)], env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout.decode()[-2000:]
+        return json.loads(lines[0]), {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+
+    d, got = run(tmp_path / "a")
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["iters"] == 64 and d["unit"] == "iters/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["ms_per_step"] - 1e3 * 32 / d["value"]) <= 1e-3 * d["ms_per_step"]
+    assert not {"roofline", "generator_forward", "gradient_mode", "many_targets", "config4", "config5", "objectives", "bf16x3_mode",
+                "landmark_callback", "cpu_baseline"} & set(d)
+    assert set(got) == {"best_latent", "best_step", "best_loss", "losses", "last_step_losses"}
+    assert got["best_latent"].dtype == np.float32 and got["best_latent"].shape == (1, 17, 32) and np.isfinite(got["best_latent"]).all()
+    losses = got["losses"]
+    assert all(got[k].dtype == np.float64 for k in ("best_step", "best_loss", "losses", "last_step_losses"))
+    assert losses.shape == (96,) and np.isfinite(losses).all() and np.array_equal(got["last_step_losses"], losses[64:])
+    step = int(got["best_step"])
+    assert step == float(got["best_step"]) and losses[step] == got["best_loss"] == losses.min()
+    _, again = run(tmp_path / "b")
+    assert set(again) == set(got) and all(np.array_equal(again[k], got[k]) for k in got), {k: float(np.abs(again[k] - got[k]).max()) for k in got}
 
 
 def test_device_landmark_model_in_the_graph(golden):

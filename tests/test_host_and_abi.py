@@ -383,26 +383,25 @@ def test_network_pickle_reader_is_inert_and_complete(tmp_path):
         loader.load_network_stubs(p)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/torch_utils"), reason="reference tree not present (GPU box)")
 def test_network_pickle_reader_on_a_real_reference_pickle(tmp_path):
-    """Pickle the REFERENCE Generator with the REFERENCE persistence machinery, read it back with the inert reader."""
-    import pickle
+    """The REFERENCE Generator pickled by the REFERENCE persistence machinery (tests/golden/ref_pickle_tiny.pkl.gz, oracle/make_golden.py:
+    TINY, seed 5, module source replaced by a placeholder that registers a marker module when executed), read back with the inert reader."""
+    import gzip
     from morphganformer_amd import loader
     from morphganformer_amd.synth_weights import TINY, make_state_dict
-    from oracle.make_golden import build_reference_generator, import_reference
-    ref = import_reference()
-    sd = make_state_dict(TINY, seed=5)
-    G = build_reference_generator(ref, TINY, sd)
+    from oracle.make_golden import PICKLE_SRC_MARKER
     p = str(tmp_path / "ref.pkl")
-    with open(p, "wb") as f:
-        pickle.dump(dict(G=G, D=G, Gs=G), f)
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "ref_pickle_tiny.pkl.gz")) as src, open(p, "wb") as f:
+        f.write(src.read())
     assert b"class Generator" in open(p, "rb").read()           # module source is embedded ... and never executed below
+    sys.modules.pop(PICKLE_SRC_MARKER, None)
     stubs = loader.load_network_stubs(p)
+    assert PICKLE_SRC_MARKER not in sys.modules
     got = stubs["Gs"].state_dict()
-    want = G.state_dict()
+    want = make_state_dict(TINY, seed=5)                         # what the reference Generator was loaded with (strict: no key missing or extra)
     assert set(got) == set(want)
     for k, v in want.items():
-        assert torch.equal(v, got[k]), k
+        assert torch.equal(torch.from_numpy(np.asarray(v)), got[k]), k
     cfg = loader.config_from_stub(stubs["Gs"])
     assert cfg == TINY
 
@@ -607,32 +606,24 @@ def test_legacy_tf_snapshot_conversion_roundtrip(tmp_path):
     assert all(np.array_equal(got2[k], got[k]) for k in got)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/torch_utils"), reason="reference tree not present (GPU box)")
-def test_legacy_tf_conversion_matches_the_reference_converter():
-    """The same synthetic TF snapshot through the REFERENCE's convert_tf_generator (loader.py:91-247)."""
+def test_legacy_tf_conversion_matches_the_reference_converter(golden):
+    """The same synthetic TF snapshot through the REFERENCE's convert_tf_generator (loader.py:91-247): its state_dict as pinned by
+    tests/golden/tf_convert_mini256.npz (oracle/make_golden.py) -- every tensor's digest, the computed grid_pos tensors themselves."""
     from morphganformer_amd import loader
     from morphganformer_amd.synth_weights import make_state_dict
-    from oracle.make_golden import import_reference
-    import_reference()
-    import importlib
-    ref_loader = importlib.import_module("loader")
-    assert ref_loader.__file__.startswith("/root/reference")
+    from oracle.make_golden import tf_state_digest
+    g = golden("tf_convert_mini256.npz")
+    want = dict(zip(g["keys"].tolist(), g["digests"].tolist()))
     cfg = _mini256()
     sd = make_state_dict(cfg, seed=7)
     stub = _tf_stub_from_state(sd, cfg)
-
-    def to_ref(s_):
-        return ref_loader._TFNetworkStub(version=s_["version"], static_kwargs=dict(s_["static_kwargs"]), variables=list(s_["variables"]),
-                                         components={k: to_ref(v) for k, v in s_["components"].items()})
-    G = ref_loader.convert_tf_generator(to_ref(stub))
-    want = {k: v.detach().numpy() for k, v in G.state_dict().items()}
     got, gcfg = loader.convert_tf_generator(stub)
     assert gcfg == cfg
     for k, v in got.items():
         if k.endswith("grid_pos"):
-            assert np.allclose(v, want[k], atol=1e-6), k
+            assert np.allclose(v, g[f"grid_pos/{k}"], atol=1e-6), k
         else:
-            assert np.array_equal(v, want[k]), k
+            assert tf_state_digest(v) == want[k], k
     assert set(want) - set(got) == set() or all("num_batches" in k for k in set(want) - set(got))
 
 
@@ -669,6 +660,7 @@ def test_bench_fixed_batch_and_torch_free_launcher():
             f"spec = importlib.util.spec_from_file_location('bench_mod', {os.path.join(root, 'bench.py')!r}); "
             "mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod); a = mod.parse(); "
             "assert a.batch == 32 and a.steps == 97 and a.warmup == 5 and a.gpus == 1 and not hasattr(a, 'min_seconds'); "
+            "assert a.full is False and a.dump_outputs is None; "
             "assert 'torch' not in sys.modules and 'numpy' not in sys.modules; print('ok')")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr[-2000:]

@@ -1,4 +1,4 @@
-X="--bf16x3-leg 0 --no-cpu-baseline --gradient-steps 0 --targets 0 --objectives 0 --landmark-callback none --config4 0 --config5-targets 0 --arith bf16x3"
+X="--full --bf16x3-leg 0 --no-cpu-baseline --gradient-steps 0 --targets 0 --objectives 0 --landmark-callback none --config4 0 --config5-targets 0 --arith bf16x3"
 mkdir -p gpurun_out/bfx
 for r in 128 256 512; do
   MGF_BF_DIRECT_MAX_RES=$r python bench.py $X > gpurun_out/bfx/r$r.json 2> gpurun_out/bfx/r$r.err && python -c "

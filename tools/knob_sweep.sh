@@ -7,7 +7,7 @@ X="--bf16x3-leg 0 --no-cpu-baseline --targets 0 --objectives 0 --landmark-callba
 for kv in base $2 base; do
   if [ "$kv" = base ]; then E="MGF_NOOP=1"; else E="$kv"; fi
   if [ "${G:-0}" = 1 ]; then
-    env $E python bench.py $X --steps 2 --warmup 1 --gradient-steps 30 --gradient-lockstep 0 2>>$D/err.txt | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1])['gradient_mode']; print('$kv gradient', d['value'], d['ms_per_step'])" || exit 1
+    env $E python bench.py $X --full --steps 2 --warmup 1 --gradient-steps 30 --gradient-lockstep 0 2>>$D/err.txt | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1])['gradient_mode']; print('$kv gradient', d['value'], d['ms_per_step'])" || exit 1
   else
     env $E python bench.py $X --gradient-steps 0 2>>$D/err.txt | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$kv headline', d['value'], d['ms_per_step'])" || exit 1
   fi

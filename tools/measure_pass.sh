@@ -6,8 +6,8 @@ set -e
 D=$1; B=${2:-32}; R=${3:-r5}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf "$D"; mkdir -p "$D"
-echo "[measure] bench"; python3 bench.py > $D/bench.json 2> $D/bench.err
-echo "[measure] kernel trace"; LEAN="--no-cpu-baseline --gradient-steps 0 --targets 0 --landmark-callback none --objectives 0 --config4 0 --config5-targets 0 --bf16x3-leg 0"
+echo "[measure] bench"; python3 bench.py --full > $D/bench.json 2> $D/bench.err
+echo "[measure] kernel trace"; LEAN="--full --no-cpu-baseline --gradient-steps 0 --targets 0 --landmark-callback none --objectives 0 --config4 0 --config5-targets 0 --bf16x3-leg 0"
 rocprofv3 --kernel-trace --stats -d $D/trace -- python3 bench.py --steps 20 --warmup 2 $LEAN > $D/trace_bench.json 2> $D/trace.err
 # the same on ONE stream (--pipeline 0): kernels running alone, for the per-iteration analyses (iteration trace / floor) and the counter passes -- in the
 # default two-stream schedule the loss phase's kernels run beside the generator's and their durations (and per-kernel busy counters) describe the pair
@@ -18,7 +18,7 @@ echo "[measure] pmc fetch"; rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D
 echo "[measure] pmc write"; rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/pmc_write -- python3 bench.py $ARGS > $D/pmc_write.json 2> $D/pmc_write.err
 echo "[measure] pmc mfma"; rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $D/pmc_mfma -- python3 bench.py $ARGS > $D/pmc_mfma.json 2> $D/pmc_mfma.err
 echo "[measure] gradient traces"
-GL="--no-cpu-baseline --targets 0 --landmark-callback none --objectives 0 --config4 0 --config5-targets 0 --bf16x3-leg 0"
+GL="--full --no-cpu-baseline --targets 0 --landmark-callback none --objectives 0 --config4 0 --config5-targets 0 --bf16x3-leg 0"
 rocprofv3 --kernel-trace -d $D/gtrace1 -- python3 bench.py --steps 1 --warmup 1 $GL --gradient-steps 6 --gradient-lockstep 0 > $D/g1.json 2> $D/g1.err
 rocprofv3 --kernel-trace -d $D/gtrace8 -- python3 bench.py --steps 1 --warmup 1 $GL --gradient-steps 6 --gradient-lockstep 16 > $D/g8.json 2> $D/g8.err
 echo "[measure] bf16x3 mode: kernel trace + MFMA counters"
