@@ -322,6 +322,18 @@ int mgf_attn_values_multi(const mgf_attn_job* jobs_dev, int32_t njobs, const flo
  *   rgb_weights: out[n, c, co] = w[c, co] * s[n, co] */
 int mgf_randn_f32(float* out, int64_t n, uint64_t seed, void* state, mgf_stream_t stream);
 int mgf_rgb_weights_f32(float* out, const float* w, const float* s, int32_t n, int32_t c, int32_t cout, mgf_stream_t stream);
+/* conv_last and ToRGB of the last block composed into one per-sample 3x3 kernel.  conv_last is built without bias, noise and attention
+ * (networks.py:1124-1130), so it applies no bias and no activation (:973, :1010-1043); its only consumer is ToRGB, a modulated 1x1 without
+ * demodulation plus a bias (:1054-1065, :1169-1173).  The two linear maps are one [rgb_channels, cin, 3, 3] convolution per sample:
+ *   w_eff[n, c, ci, k] = s_last[n, ci] * sum_o (w_rgb[c, o] s_rgb[n, o]) d_last[n, o] w_last[o, ci, k]
+ * w_last: conv_last's weights times w_gain, [cout, cin, 3, 3]; s_last [n, cin], d_last [n, cout] (null: no demodulation); w_rgb
+ * [rgb_channels, cout]; s_rgb [n, cout] (ToRGB's styles times its w_gain).  Sum over o in float64, rounded once to float32.
+ * mgf_conv3x3_few_outputs_f32 (narrow_conv.hip) applies it: y[n, c, oy, ox] = bias[c] + sum_{ci,kh,kw} w[n, c, ci, kh, kw]
+ * x[n, ci, oy+kh-1, ox+kw-1], stride 1, zero padding 1, 1 <= cout <= 4, any cin / h / w; bias [cout] or null. */
+int mgf_torgb_compose_weights_f32(float* w_eff, const float* w_last, const float* s_last, const float* d_last, const float* w_rgb,
+                                  const float* s_rgb, int32_t n, int32_t cin, int32_t cout, int32_t rgb_channels, mgf_stream_t stream);
+int mgf_conv3x3_few_outputs_f32(float* y, const float* x, const float* w, const float* bias, int32_t n, int32_t cin, int32_t h, int32_t wd,
+                                int32_t cout, mgf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Mapping network z -> w  (MappingNetwork.forward, training/networks.py:894-942 with MLP/ResnetLayer :154-221 and the

@@ -442,6 +442,22 @@ def conv3x3s2_few_inputs(x, w, bias=None, relu=False, out=None):
     return out
 
 
+def conv3x3_few_outputs(x, w, bias=None, out=None):
+    """3x3 / stride-1 / zero-padded convolution with per-sample weights into <= 4 output channels (+ bias): the composed conv_last + ToRGB
+    map of the last block.  x [n, cin, h, w]; w [n, cout, cin, 3, 3]; bias [cout] or None."""
+    _lib.require_gpu(x, w, bias, out)
+    n, cin, h, wd = x.shape
+    cout = w.shape[1]
+    assert x.dtype == torch.float32 and x.is_contiguous() and w.dtype == torch.float32 and w.is_contiguous()
+    assert tuple(w.shape) == (n, cout, cin, 3, 3) and cout <= 4
+    if out is None:
+        out = torch.empty([n, cout, h, wd], dtype=torch.float32, device=x.device)
+    assert out.is_contiguous() and tuple(out.shape) == (n, cout, h, wd)
+    _lib.check(_lib.lib().mgf_conv3x3_few_outputs_f32(out.data_ptr(), x.data_ptr(), w.data_ptr(), _lib.ptr(bias), n, cin, h, wd, cout,
+                                                      _lib.stream_ptr()), "conv3x3_few_outputs")
+    return out
+
+
 def tconv3x3s2_forward(x, pc: PackedConv, in_scale=None, out_scale=None, out=None, bf=None):
     """Stride-2 3x3 transposed convolution t[2i+kh, 2j+kw] += w[kh,kw] x[i,j] -> view [n, cout, 2h+1, 2w+1] of a padded-pitch
     workspace (row pitch a multiple of 4 floats so the parity pairs are written as aligned float2)."""

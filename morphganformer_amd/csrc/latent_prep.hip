@@ -792,6 +792,23 @@ __global__ __launch_bounds__(256) void rgb_weights_kernel(float* out, const floa
     const int o = i % co, n = i / (c * co);
     out[i] = w[i % (c * co)] * s[n * co + o];
 }
+
+// w_eff[n, c, ci, k] = s_last[n, ci] * sum_o (w_rgb[c, o] s_rgb[n, o]) d_last[n, o] w_last[o, ci, k]: conv_last (no bias, noise or
+// activation, networks.py:1124-1130,1010-1043) and ToRGB (modulated 1x1, no demodulation, + bias, networks.py:1054-1065) composed into one
+// [rgb_channels, cin, 3, 3] kernel per sample.  One lane per output weight, the sum over o in float64, rounded once.
+__global__ __launch_bounds__(256) void torgb_compose_kernel(float* out, const float* w_last, const float* s_last, const float* d_last,
+                                                            const float* w_rgb, const float* s_rgb, int cin, int cout, int rc, int total) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int k = i % 9, ci = (i / 9) % cin, c = (i / (9 * cin)) % rc, n = i / (9 * cin * rc);
+    double acc = 0.0;
+    for (int o = 0; o < cout; ++o) {
+        const double a = (double)w_rgb[c * cout + o] * (double)s_rgb[(int64_t)n * cout + o];
+        const double d = d_last ? (double)d_last[(int64_t)n * cout + o] : 1.0;
+        acc += a * d * (double)w_last[((int64_t)o * cin + ci) * 9 + k];
+    }
+    out[i] = (float)(acc * (double)s_last[(int64_t)n * cin + ci]);
+}
 }  // namespace
 
 extern "C" int mgf_randn_f32(float* out, int64_t n, uint64_t seed, void* state, mgf_stream_t stream) {
@@ -809,6 +826,19 @@ extern "C" int mgf_rgb_weights_f32(float* out, const float* w, const float* s, i
     const int total = n * c * cout;
     hipLaunchKernelGGL(rgb_weights_kernel, dim3((unsigned)mgf_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, out, w, s, c, cout, total);
     MGF_CHECK_LAUNCH("rgb_weights");
+    return MGF_OK;
+}
+
+extern "C" int mgf_torgb_compose_weights_f32(float* w_eff, const float* w_last, const float* s_last, const float* d_last, const float* w_rgb,
+                                             const float* s_rgb, int32_t n, int32_t cin, int32_t cout, int32_t rgb_channels, mgf_stream_t stream) {
+    MGF_REQUIRE(w_eff && w_last && s_last && w_rgb && s_rgb && n >= 1 && cin >= 1 && cout >= 1 && rgb_channels >= 1, MGF_EINVAL,
+                "torgb_compose_weights: bad arguments");
+    MGF_REQUIRE((int64_t)n * rgb_channels * cin * 9 <= INT32_MAX && (int64_t)cout * cin * 9 <= INT32_MAX, MGF_ETOOBIG,
+                "torgb_compose_weights: too many weights");
+    const int total = n * rgb_channels * cin * 9;
+    hipLaunchKernelGGL(torgb_compose_kernel, dim3((unsigned)mgf_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w_eff, w_last, s_last,
+                       d_last, w_rgb, s_rgb, cin, cout, rgb_channels, total);
+    MGF_CHECK_LAUNCH("torgb_compose_weights");
     return MGF_OK;
 }
 

@@ -5,7 +5,11 @@
 // output in a K of 72, 3 live rows of 32); both are streams over the 64-channel map with ~0.25 FLOP per byte, so they run here as
 // VALU kernels: the narrow side in registers, the weights through the scalar cache or broadcast from LDS, every access of the wide map
 // coalesced.
-// Contracts: include/mgf.h (mgf_conv3x3s2_few_inputs_f32, mgf_tconv3x3s2_few_outputs_f32).
+// The third kernel is the generator's last 3x3 convolution composed with its ToRGB projection (32 -> 3 channels, stride 1, weights per
+// sample): the same kind of stream over a wide map into a narrow side.
+// Contracts: include/mgf.h (mgf_conv3x3s2_few_inputs_f32, mgf_tconv3x3s2_few_outputs_f32, mgf_conv3x3_few_outputs_f32).
+#include <algorithm>
+
 #include "mgf_common.h"
 
 namespace {
@@ -118,7 +122,125 @@ __global__ __launch_bounds__(256) void tconv3x3s2_few_outputs_kernel(float* __re
     }
 }
 
+// y[n, co, oy, ox] = bias[co] + sum_{ci, kh, kw} w[n, co, ci, kh, kw] * x[n, ci, oy + kh - 1, ox + kw - 1]   (stride 1, zero padding 1,
+// weights per sample, CO <= 4 outputs): the composed conv_last + ToRGB map of the last block (engine.py), a stream over the wide input
+// with 0.2 FLOP per byte.  A lane owns 4 adjacent pixels of a row (one 16-byte load per input row and channel, the two halo columns as
+// 4-byte loads that hit the lines its neighbours fetch); a workgroup walks `rows` output rows down its strip with a rolling 3-row window,
+// so every input row of the strip is read once: input row r feeds output rows r+1 (kh 0), r (kh 1) and r-1 (kh 2), and row r-1 is
+// complete -- stored -- once row r is in.  Per-sample weights come through the scalar cache (a workgroup never spans samples); pixel pairs
+// make every multiply-add a v_pk_fma_f32 with the weight broadcast.  Summation order per output: input row, then channel, then kw -- the
+// same for every strip height and batch size.
+// VEC: w % 4 == 0 and 16-byte aligned x / y (float4 rows); otherwise every column is loaded and stored on its own with bounds checks.
+typedef float nc_f2 __attribute__((ext_vector_type(2)));
+
+template <int CO, bool VEC>
+__global__ __launch_bounds__(256) void conv3x3_few_outputs_kernel(float* __restrict__ y, const float* __restrict__ x, const float* w,
+                                                                  const float* bias, int cin, int h, int wd, int rows) {
+    const int n = blockIdx.z, oy0 = blockIdx.y * rows, ox = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (ox >= wd) return;                                                  // (no LDS, no barrier)
+    const int oy1 = min(oy0 + rows, h);
+    const int64_t plane = (int64_t)h * wd;
+    const float* xn = x + (int64_t)n * cin * plane + ox;
+    float* yn = y + (int64_t)n * CO * plane + ox;
+    const nc_cfp wn = (nc_cfp)w + (int64_t)n * CO * cin * 9, bs = (nc_cfp)bias;
+    nc_f2 acc[3][CO][2];                                                   // output rows r-1, r, r+1 x channel x pixel pair
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int o = 0; o < CO; ++o) acc[s][o][0] = acc[s][o][1] = nc_f2{0.f, 0.f};
+    for (int r = oy0 - 1; r <= oy1; ++r) {
+        if (r >= 0 && r < h) {
+            const float* xr = xn + (int64_t)r * wd;
+#ifndef MGF_C3F_UNROLL
+#define MGF_C3F_UNROLL 2
+#endif
+#pragma unroll MGF_C3F_UNROLL
+            for (int ci = 0; ci < cin; ++ci) {
+                const float* xc = xr + ci * plane;
+                float v[6];                                                // columns ox-1 .. ox+4
+                if (VEC) {
+                    const float4 m = *reinterpret_cast<const float4*>(xc);
+                    v[0] = ox > 0 ? xc[-1] : 0.f;
+                    v[1] = m.x; v[2] = m.y; v[3] = m.z; v[4] = m.w;
+                    v[5] = ox + 4 < wd ? xc[4] : 0.f;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) v[j] = (ox + j - 1 >= 0 && ox + j - 1 < wd) ? xc[j - 1] : 0.f;
+                }
+                nc_f2 p[5];                                                // p[k] = columns (ox-1+k, ox+k): pixel pair q, tap kw -> p[2q+kw]
+#pragma unroll
+                for (int k = 0; k < 5; ++k) p[k] = nc_f2{v[k], v[k + 1]};
+#pragma unroll
+                for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+                    for (int o = 0; o < CO; ++o) {
+                        const nc_cfp wr = wn + (o * cin + ci) * 9 + kh * 3;
+#pragma unroll
+                        for (int kw = 0; kw < 3; ++kw) {
+                            const float wv = wr[kw];
+                            acc[2 - kh][o][0] = __builtin_elementwise_fma(nc_f2{wv, wv}, p[kw], acc[2 - kh][o][0]);
+                            acc[2 - kh][o][1] = __builtin_elementwise_fma(nc_f2{wv, wv}, p[2 + kw], acc[2 - kh][o][1]);
+                        }
+                    }
+            }
+        }
+        if (r - 1 >= oy0) {                                                // output row r-1 is complete (r-1 < oy1 <= h)
+            float* yr = yn + (int64_t)(r - 1) * wd;
+#pragma unroll
+            for (int o = 0; o < CO; ++o) {
+                const float b = bias ? bs[o] : 0.f;
+                const float4 q = make_float4(acc[0][o][0].x + b, acc[0][o][0].y + b, acc[0][o][1].x + b, acc[0][o][1].y + b);
+                float* yo = yr + o * plane;
+                if (VEC) {
+                    *reinterpret_cast<float4*>(yo) = q;
+                } else {
+                    yo[0] = q.x;
+                    if (ox + 1 < wd) yo[1] = q.y;
+                    if (ox + 2 < wd) yo[2] = q.z;
+                    if (ox + 3 < wd) yo[3] = q.w;
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < CO; ++o)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                acc[0][o][u] = acc[1][o][u];
+                acc[1][o][u] = acc[2][o][u];
+                acc[2][o][u] = nc_f2{0.f, 0.f};
+            }
+    }
+}
+
 }  // namespace
+
+extern "C" int mgf_conv3x3_few_outputs_f32(float* y, const float* x, const float* w, const float* bias, int32_t n, int32_t cin, int32_t h,
+                                           int32_t wd, int32_t cout, mgf_stream_t stream) {
+    MGF_REQUIRE(y && x && w && n >= 1 && cin >= 1 && h >= 1 && wd >= 1, MGF_EINVAL, "conv3x3_few_outputs: bad arguments");
+    MGF_REQUIRE(cout >= 1 && cout <= NC_MAX_NARROW, MGF_EUNSUPPORTED, "conv3x3_few_outputs: 1..%d output channels (got %d)", NC_MAX_NARROW, cout);
+    MGF_REQUIRE(n <= 65535 && (int64_t)cout * cin * 9 <= INT32_MAX, MGF_ETOOBIG, "conv3x3_few_outputs: tensor too large");
+    const int lanes = (int)mgf_cdiv(wd, 4);                                // 4 pixels per lane
+    const int threads = (int)std::min<int64_t>(256, mgf_cdiv(lanes, MGF_WAVE) * MGF_WAVE);
+    const int gx = (int)mgf_cdiv(lanes, threads);
+    // strip height: 16 rows (halo re-read 2/16) while that leaves >= 8 workgroups per CU, shorter strips for small batches / maps
+    int rows = 16;
+    while (rows > 4 && (int64_t)n * gx * mgf_cdiv(h, rows) < 8 * MGF_NUM_CU) rows /= 2;
+    static const char* rows_env = mgf_knob("MGF_C3F_ROWS");          // tuning hook (experiments only): the strip height
+    if (rows_env) rows = std::max(1, atoi(rows_env));
+    MGF_REQUIRE(mgf_cdiv(h, rows) <= 65535, MGF_ETOOBIG, "conv3x3_few_outputs: map too tall");
+    const bool vec = wd % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0;
+    const dim3 grid((unsigned)gx, (unsigned)mgf_cdiv(h, rows), (unsigned)n);
+    hipStream_t st = (hipStream_t)stream;
+#define MGF_C3F_LAUNCH(CO)                                                                                                         \
+    do {                                                                                                                           \
+        if (vec) hipLaunchKernelGGL((conv3x3_few_outputs_kernel<CO, true>), grid, dim3(threads), 0, st, y, x, w, bias, cin, h, wd, rows);  \
+        else hipLaunchKernelGGL((conv3x3_few_outputs_kernel<CO, false>), grid, dim3(threads), 0, st, y, x, w, bias, cin, h, wd, rows);     \
+    } while (0)
+    if (cout == 1) MGF_C3F_LAUNCH(1); else if (cout == 2) MGF_C3F_LAUNCH(2); else if (cout == 3) MGF_C3F_LAUNCH(3); else MGF_C3F_LAUNCH(4);
+#undef MGF_C3F_LAUNCH
+    MGF_CHECK_LAUNCH("conv3x3_few_outputs");
+    return MGF_OK;
+}
 
 extern "C" int mgf_conv3x3s2_few_inputs_f32(float* y, const float* x, const float* w, const float* bias, int32_t n, int32_t cin, int32_t in_h,
                                             int32_t in_w, int32_t cout, int32_t relu, mgf_stream_t stream) {

@@ -633,6 +633,7 @@ __global__ __launch_bounds__(256, 2) void wino3p_conv_kernel(Wino3Params p) {
     constexpr int FP = 6 * W3FW;                                   // footprint pixels per channel (6 rows x 34)
     constexpr int CST = 256, RAW = W3CK * CST;
     constexpr int NV = 16, NR = 8;
+    static_assert(!RGB || NCK == NR, "the deferred ToRGB projection runs one part per chunk body and stores after part NR - 1");
     constexpr unsigned OOB = 0xFFFFFFF0u;
     extern __shared__ float lds[];
     float* const raw0 = lds;

@@ -99,6 +99,7 @@ class ConvLayerPlan:
     act_gain: float = 1.0
     attn: "AttnPlan" = None
     w_raw: torch.Tensor = None      # toRGB only: [img_channels, cin] un-packed weights for the fused projection
+    w_gained: torch.Tensor = None   # conv_last only: [cout, cin, 3, 3] weights times w_gain, un-packed, for the composition with ToRGB
     wino_u: torch.Tensor = None     # 3x3 stride-1 layers on 16^2 .. 256^2 maps: Winograd-transformed weights (csrc/wino.hip)
     pcb: torch.Tensor = None        # arith="bf16x3" only: the weights split into two bfloat16 terms (conv.pack_weights_bf16x3)
     s_off: int = 0                  # offsets (floats) into the per-sample style / demod arenas
@@ -174,6 +175,10 @@ class SynthesisPlan:
                 lp.attn = self._fold_attention(sd, p, cout, res, T, D, t32, f64)
                 lp.attn.v_off = v_off
                 v_off += cout * T
+            # conv_last as the reference builds it -- no bias, noise or attention (networks.py:1124-1130) -- is linear and feeds ToRGB only:
+            # the two compose into one per-sample [img_channels, cin, 3, 3] kernel (mgf_torgb_compose_weights_f32)
+            if name == "conv_last" and lp.bias is None and lp.noise_strength is None and lp.attn is None and cfg.img_channels <= 4:
+                lp.w_gained = t32(w / math.sqrt(cin * 9))
             lp.s_off, lp.d_off = s_off, d_off
             s_off += cin
             d_off += cout
@@ -245,6 +250,9 @@ class Generator:
         # as the loss/generator pipeline: concurrent kernels stretch each other -- differently under graph replay than in the eager
         # roofline leg -- so per-kernel durations would no longer agree between bench.py and a rocprofv3 trace.
         self.overlap_skip = os.environ.get("MGF_OVERLAP_SKIP", "0") != "0"
+        # conv_last + ToRGB as ONE composed 32 -> 3 convolution (mgf_torgb_compose_weights_f32 + mgf_conv3x3_few_outputs_f32) wherever
+        # fuse_torgb holds; MGF_TORGB_COMPOSE=0 (tuning hook) = the full conv_last with the projection fused into its epilogue
+        self.torgb_compose = os.environ.get("MGF_TORGB_COMPOSE", "1") != "0"
         self._workspaces, self._pins = {}, {}
         self.noise_seed, self._noise_epoch = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF, None
         self.noise_state = torch.zeros(2, dtype=torch.int64, device=self.device)          # {stream position, ticket}: advanced on the device
@@ -259,7 +267,7 @@ class Generator:
     # of gradient mode reads, what `taps` / return_att hand out.  LEAN: the literal loop has no backward pass and only ever needs a block's
     # input, its transposed-conv workspace, its two layer outputs and its skip branch at the same time, so the layer outputs are views of
     # seven arenas sized for the largest user and re-used block after block (0.47 GB per sample: 15 instead of 51 GB at 32 steps per forward).
-    _WS_FIELDS = ("n", "lean", "w_buf", "styles", "demods", "vtabs", "noise_rand", "bufs", "img", "const_in", "rgbw", "style_jobs", "n_style_jobs",
+    _WS_FIELDS = ("n", "lean", "w_buf", "styles", "demods", "vtabs", "noise_rand", "bufs", "img", "const_in", "rgbw", "w_eff", "style_jobs", "n_style_jobs",
                   "max_style_cin", "attn_jobs", "n_attn_jobs", "style_jobs_pl", "attn_jobs_pl", "ws_bytes", "ws_gen")
 
     def _alloc(self, n, lean=None):
@@ -393,6 +401,7 @@ class Generator:
         self.img = e(n, cfg.img_channels, cfg.img_resolution, cfg.img_resolution)
         self.const_in = P.const.unsqueeze(0).repeat(n, 1, 1, 1).contiguous()            # networks.py:1147
         self.rgbw = e(n, cfg.img_channels, cfg.channels(cfg.img_resolution))
+        self.w_eff = e(n, cfg.img_channels, cfg.channels(cfg.img_resolution), 3, 3)
         self.ws_bytes = self._workspace_bytes(n, lean)
         self._build_jobs(n)
 
@@ -589,7 +598,14 @@ class Generator:
             if res == cfg.img_resolution:
                 lp = layers[b + ".conv_last"]
                 lt = layers[b + ".torgb"]
-                if self.taps is None and self.fuse_torgb and lp.cout <= 32:
+                if self.taps is None and self.fuse_torgb and self.torgb_compose and lp.w_gained is not None:
+                    # conv_last + ToRGB composed: one 3x3 convolution into the image channels (1.8 instead of 19.3 GFLOP per 1024^2 image),
+                    # the [n,32,R,R] conv_last activation never exists
+                    _lib.check(L.mgf_torgb_compose_weights_f32(self.w_eff.data_ptr(), lp.w_gained.data_ptr(), self._s(lp).data_ptr(),
+                                                               self._d(lp).data_ptr(), lt.w_raw.data_ptr(), self._s(lt).data_ptr(), n, lp.cin,
+                                                               lp.cout, lt.w_raw.shape[0], st), "torgb_compose_weights")
+                    cv.conv3x3_few_outputs(x, self.w_eff, lt.bias, out=self.img)
+                elif self.taps is None and self.fuse_torgb and lp.cout <= 32:
                     # conv_last + ToRGB in one kernel: the [n,32,R,R] conv_last activation never goes to HBM
                     _lib.check(L.mgf_rgb_weights_f32(self.rgbw.data_ptr(), lt.w_raw.data_ptr(), self._s(lt).data_ptr(), n, lt.w_raw.shape[0],
                                                      lt.w_raw.shape[1], st), "rgb_weights")                       # W[c,co] * s[n,co]
