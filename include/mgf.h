@@ -688,6 +688,33 @@ int mgf_adam_step_f32(float* param, float* exp_avg, float* exp_avg_sq, int32_t* 
                       const int32_t* step, const int32_t* valid, int64_t numel, int32_t steps_total, float beta1, float beta2, float eps,
                       float weight_decay, mgf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * MDF objective (mdfloss.py:16-47 over the SinGAN WDiscriminators of SinGAN/models.py:7-35; csrc/mdf.hip): per discriminator five
+ * VALID 3x3 / stride-1 convolutions, eval-mode BatchNorm folded into weight and bias (w [c][cin][3][3] in torch layout), LeakyReLU
+ * `slope` (0.2) behind head and body, taps x1 = head out, x2 = body out, x3 = tail out.  Maps are FRAMES of the image's h x w: a map of
+ * ring depth r holds its valid values at rows / columns [r, h - r) (image 0, x1 1, body block k 1 + k, x2 4, x3 5), so a valid conv of a
+ * ring-r map is the frame's zero-padded conv read on ring r + 1.  Targets are frames of one image (batch stride 0).
+ * Partial sums are float64 slabs of mgf_mdf_partials(h, w) values per candidate: part[candidate][k], fixed-order sums, no atomics.
+ *   head:   x1 [n,c,h,w] = lrelu(conv_pad1(img [n,3,h,w], w [c,3,3,3]) + bias) on the whole frame (models.py:7-12, head = ConvBlock);
+ *           with x1_target [c,h,w]: part = partial sums of (x1 - x1_target)^2 over ring 1 (mdfloss.py:39-40 for tap 0)
+ *   body:   y [n,c,h,w] = lrelu(conv_pad1(x, w) + bias), c in {32, 64, 128}, u = mgf_winograd2_weights_f32(w) (models.py:20-23, body
+ *           ConvBlocks); form-3 Winograd whose kernel choice depends on (c, h, w) only -- a sample's bits do not depend on the batch
+ *   tail:   x2 [n,c,h,w] of ring `ring`: part2 = partials of (x2 - x2_target)^2 over ring `ring`; x3 = conv(x2, w [1,c,3,3]) + bias on
+ *           ring `ring` + 1 (models.py:24, tail), written to x3 [n,h,w] when given (ring outside untouched), part3 = partials of
+ *           (x3 - x3_target)^2 (mdfloss.py:39-40 for taps 1, 2); every output may be NULL, a partial slab comes with its target
+ *   finish: out[b] (+)= scale * sum_s (sum_k part[s][b][k]) / counts[s] -- slabs s = 0 .. nslots-1 ([nslots][n][nblk], host array
+ *           `counts`: elements of each tap) summed in index order in float64, rounded to float32 once (mdfloss.py:24-47 per candidate;
+ *           the batch mean of :46 is the caller's) */
+int64_t mgf_mdf_partials(int32_t h, int32_t w);
+int mgf_mdf_head_f32(float* x1, double* part, const float* img, const float* w, const float* bias, const float* x1_target, int32_t n,
+                     int32_t c, int32_t h, int32_t wd, float slope, mgf_stream_t stream);
+int mgf_mdf_body_f32(float* y, const float* x, const float* u, const float* bias, int32_t n, int32_t c, int32_t h, int32_t wd, float slope,
+                     mgf_stream_t stream);
+int mgf_mdf_tail_f32(float* x3, double* part2, double* part3, const float* x2, const float* w, float bias, const float* x2_target,
+                     const float* x3_target, int32_t n, int32_t c, int32_t h, int32_t wd, int32_t ring, mgf_stream_t stream);
+int mgf_mdf_finish_f32(float* out, const double* part, int32_t nslots, int64_t nblk, const double* counts, int32_t n, float scale,
+                       int32_t accumulate, mgf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libmgf_hip.so")
 SOURCES = ["capi.cpp", "bias_act.hip", "upfirdn2d.hip", "conv_taps.hip", "latent_prep.hip", "attention.hip", "losses.hip", "lpips_stem.hip",
-           "embed.hip", "backward.hip", "wino.hip", "wino3.hip", "pointwise.hip", "narrow_conv.hip", "warp.hip", "lbp.hip"]
+           "embed.hip", "backward.hip", "wino.hip", "wino3.hip", "pointwise.hip", "narrow_conv.hip", "warp.hip", "lbp.hip", "mdf.hip"]
 HEADERS = [os.path.join(CSRC, "mgf_common.h"), os.path.join(ROOT, "include", "mgf.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=on: fma only inside one source expression (so `acc += a * b` still fuses) and never across statements --
@@ -57,20 +57,31 @@ def _compile_all(obj_dir, flags_for, verbose, force, prune=True):
     """Compile every source into obj_dir (missing objects only, unless force); returns the object paths in SOURCES order.
     prune: delete a source's other objects once its current one is built (the experiment cache keeps them: variants alternate)."""
     os.makedirs(obj_dir, exist_ok=True)
-    objs, procs = [], []
+    objs, todo = [], []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)
         flags = flags_for(src)
         op = os.path.join(obj_dir, f"{src}.{object_key(sp, flags)}.o")
         objs.append(op)
         if force or not os.path.exists(op):
-            cmd = [HIPCC] + flags + ["-c", sp, "-o", op + ".tmp"]
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            procs.append((src, op, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+            todo.append((src, op, [HIPCC] + flags + ["-c", sp, "-o", op + ".tmp"]))
+    procs, finished = [], []
+
+    def start(i):
+        src, op, cmd = todo[i]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        procs.append((src, op, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+
+    for i in range(min(max_jobs(), len(todo))):             # at most max_jobs() compilers at a time; the next starts when the oldest ends
+        start(i)
+    while len(finished) < len(procs):
+        src, op, pr = procs[len(finished)]
+        finished.append((src, op, pr, pr.communicate()[0]))
+        if len(procs) < len(todo):
+            start(len(procs))
     failed = False
-    for src, op, pr in procs:
-        out, _ = pr.communicate()
+    for src, op, pr, out in finished:
         if pr.returncode != 0:
             failed = True
             sys.stderr.write(f"[mgf build] {src} FAILED:\n{out.decode(errors='replace')}\n")
@@ -83,7 +94,20 @@ def _compile_all(obj_dir, flags_for, verbose, force, prune=True):
             sys.stderr.write(out.decode(errors="replace"))
     if failed:
         raise RuntimeError("hipcc failed; see messages above")
-    return objs, bool(procs)
+    return objs, bool(todo)
+
+
+def max_jobs() -> int:
+    """Concurrent hipcc processes: MAX_JOBS when set, else the CPUs this process may use, at most 16 (one compiler per source
+    would oversubscribe a machine that grants a build fewer cores than there are sources)."""
+    env = os.environ.get("MAX_JOBS")
+    if env and env.isdigit() and int(env) > 0:
+        return int(env)
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    return max(1, min(16, n))
 
 
 def _link(lib, objs, verbose):

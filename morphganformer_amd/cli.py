@@ -84,6 +84,13 @@ def _loop_arguments(p):
                         "reference fetches by name; required with --biometric unless --biometric-random")
     p.add_argument("--biometric-random", action="store_true", help="seeded random embedder weights (smoke runs only)")
     p.add_argument("--no-mse", action="store_true", help="drop the MSE term (beta * MSE)")
+    p.add_argument("--mdf", type=str, default=None, metavar="DS_PTH",
+                   help="add the MDF discriminator-feature loss of a Ds_*.pth file (mdf-main/weights/Ds_{SISR,Denoising,JPEG}.pth, what --mdfapp "
+                        "picks) -- alone, as 1024_example_mdfloss.py scores: --no-lpips --no-mse --min-loss-init 1000; the v1 scripts "
+                        "(projection_example_v1_mdfloss*.py) add --pool-above 256; literal mode only")
+    p.add_argument("--mdf-scales", type=int, default=8, help="discriminators the MDF loss uses (num_scales, default 8)")
+    p.add_argument("--mdf-descending", action="store_true", help="use the discriminators from the last one down (is_ascending=0)")
+    p.add_argument("--mdf-random", action="store_true", help="seeded random discriminators instead of --mdf (smoke runs only)")
 
 
 def build_parser():
@@ -255,7 +262,14 @@ def main(argv=None):
         else:
             print(f"WARNING: the biometric term runs on seeded random {a.biometric} weights (--biometric-random); it is not a face embedding")
         biometric = BiometricLoss(a.biometric, state=state, n=a.batch if a.mode == "literal" else 1, device=G.device)
-    if percept is None and a.no_mse and biometric is None and not getattr(a, "landmarks", None) and a.pixel_term != "lbp":
+    mdf = None
+    if a.mdf or a.mdf_random:
+        from .mdf import MDFLoss, random_discriminators
+        if a.mdf_random:
+            print("WARNING: the MDF term runs on seeded random discriminators (--mdf-random); it is not the trained loss")
+        mdf = MDFLoss(random_discriminators(0) if a.mdf_random else a.mdf, num_scales=a.mdf_scales, is_ascending=0 if a.mdf_descending else 1,
+                      device=G.device)
+    if percept is None and a.no_mse and biometric is None and mdf is None and not getattr(a, "landmarks", None) and a.pixel_term != "lbp":
         raise SystemExit(f"{a.cmd}: every term of the objective is switched off")
     if a.pixel_term == "lbp" and (a.cmd != "project" or a.mode != "literal"):
         raise SystemExit("--pixel-term lbp is the objective of the single-image literal loop (project --mode literal)")
@@ -269,6 +283,8 @@ def main(argv=None):
             init_process_group("nccl", device_id=torch.device("cuda", torch.cuda.current_device()))
         kw = dict(args=args, percept=percept, batch=a.batch, seed=a.seed, mode=a.mode, latent_space=space, keep_images=a.keep_images, pipeline=None if a.pipeline < 0 else (bool(a.pipeline) and a.mode == "literal"),
                   biometric=biometric, gamma=a.gamma, use_mse=not a.no_mse)
+        if mdf is not None:
+            kw["mdf"] = mdf
         if a.mode == "literal":
             kw["dynamic"] = a.dynamic
         res = drivers.morph_pairs(G, drivers.read_pair_csv(a.csv, a.threshold), a.src, a.dst_raw, a.dst_morph,
@@ -297,7 +313,7 @@ def main(argv=None):
     res = drivers.project_image(G, target, lm_t, lm_s, args=args, percept=percept, batch=a.batch, seed=a.seed,
                                 out_prefix=os.path.join(a.path_to_gen, stem), mode=a.mode, path_to_gen=a.path_to_gen,
                                 keep_images=a.keep_images, latent_space=space, biometric=biometric, gamma=a.gamma, use_mse=not a.no_mse, pipeline=None if a.pipeline < 0 else (bool(a.pipeline) and a.mode == "literal"),
-                                lbp_target=lbp_target)
+                                lbp_target=lbp_target, mdf=mdf)
     print(f"best step {res['step']}  loss {res['loss']:.6f}")
     return 0
 

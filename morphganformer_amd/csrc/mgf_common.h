@@ -55,6 +55,10 @@ static inline int mgf_stream_grid(int64_t work_items, int block, int per_thread)
 void mgf_prof_external_begin(hipStream_t st, const char* name, double flops, double bytes);
 void mgf_prof_external_end(hipStream_t st);
 
+// form-3 Winograd launch whose kernel choice depends on the layer's shape only (wino3.hip; the MDF body layers of mdf.hip)
+int mgf_wino3_batch_invariant_f32(float* y, const float* x, const float* u, int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout,
+                                  const mgf_epilogue* ep, mgf_stream_t stream);
+
 #ifdef __HIPCC__
 // Sum over the 64 lanes of a wave (DPP/bpermute butterflies emitted by the compiler for __shfl_xor).
 template <typename T>

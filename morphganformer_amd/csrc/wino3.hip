@@ -1065,7 +1065,7 @@ extern "C" int mgf_winograd3_force_shape(int32_t shape) {
 static int launch_wino3(float* y, const float* x, const float* u, const float* in_scale, const float* out_scale, int32_t n, int32_t cin, int32_t h,
                         int32_t w, int32_t cout, int32_t out_scale_stride, const mgf_epilogue* ep, const float* rgb_w, const float* rgb_bias,
                         float* rgb_out, int32_t rgb_channels, mgf_stream_t stream, const float* res_low = nullptr, int64_t y_batch = 0,
-                        int32_t y_choff = 0) {
+                        int32_t y_choff = 0, bool batch_invariant = false) {
     const bool rgb = rgb_out != nullptr;
     MGF_REQUIRE((y || rgb) && x && u && n >= 1 && cin >= 1 && cout >= 1 && h >= 2 && w >= 2, MGF_EINVAL, "conv3x3_winograd3: bad arguments");
     MGF_REQUIRE(cin % W3CK == 0 && cout % 32 == 0, MGF_EUNSUPPORTED, "conv3x3_winograd3: cin must be a multiple of %d and cout of 32 (got %d, %d)",
@@ -1096,7 +1096,8 @@ static int launch_wino3(float* y, const float* x, const float* u, const float* i
     // 2681 / 2525, 512^2 3078 / 3303 / 3011, 1024^2 - / 4376 / 3940 -- residency (latency hiding across workgroups) is worth more than
     // the instructions the wider shapes save.  MGF_W3_SHAPE = 21 | 12 | 11 or mgf_winograd3_force_shape pin a shape (tuning, tests).
     static const int env_forced = [] { const char* e = mgf_knob("MGF_W3_SHAPE"); return e ? atoi(e) : 0; }();
-    const int forced = g_w3_forced_shape ? g_w3_forced_shape : env_forced;
+    // batch_invariant (mgf_wino3_batch_invariant_f32): the form follows the layer's shape alone, never the sample count or a pinned shape
+    const int forced = batch_invariant ? 0 : (g_w3_forced_shape ? g_w3_forced_shape : env_forced);
     int shape = 11;
     // ... except where the 64-channel shape measures faster: deep K with enough workgroups left to fill the chip (the 128^2 x 256-channel
     // conv1 at 25 samples: 1969 vs 2097 us; at 64^2 x 512 its 6400 workgroups lose to 12800 of the small shape, 2151 vs 1998 us)
@@ -1107,7 +1108,7 @@ static int launch_wino3(float* y, const float* x, const float* u, const float* i
     // 618-631 at 8, 1161-1172 / 1222-1231 at 16, 2253-2266 / 2423-2509 at 32; 32^2: 149 / 164 at 8 (512 workgroups), 286-295 / 309-315 at 16, 610-664 /
     // 657-777 at 32, but 107 / 99 at 4 (256 workgroups); 256 channels 128^2: 85 / 94 at one sample (512 workgroups) .. 2394-2432 / 2573-2583 at 32.
     // The threshold was 12 800 workgroups for the kernel that requested them one chunk ahead.)
-    if (!forced && !rgb && !res_low && !odd && y_choff == 0 && cout % 64 == 0 && cin >= 256 &&
+    if (!batch_invariant && !forced && !rgb && !res_low && !odd && y_choff == 0 && cout % 64 == 0 && cin >= 256 &&
         (int64_t)n * mgf_cdiv(w, 32) * mgf_cdiv(h, 4) * (cout / 64) >= 512) shape = 21;
     if (forced == 21 && cout % 64 == 0 && !rgb) shape = 21;
     if (forced == 12 || forced == 11) shape = forced;
@@ -1147,7 +1148,8 @@ static int launch_wino3(float* y, const float* x, const float* u, const float* i
     const bool vert_ok = !vert_off && p.tiles_y % vlen == 0;
     const int64_t pcount = vert_ok ? (int64_t)n * p.tiles_x * (p.tiles_y / vlen) * p.co_tiles : (int64_t)n * (p.tiles_x / strip_len) * p.tiles_y * p.co_tiles;
     const bool persist = !persist_off && (!forced || force_persist) && shape == 11 && !odd && y_choff == 0 && p.y_batch == (int64_t)cout * h * w && cin == 32 &&
-                         w % 32 == 0 && h % 4 == 0 && p.tiles_x % strip_len == 0 && (!rgb || cout == 32) && (force_persist || pcount >= 2048);
+                         w % 32 == 0 && h % 4 == 0 && p.tiles_x % strip_len == 0 && (!rgb || cout == 32) &&
+                         (force_persist || batch_invariant || pcount >= 2048);
     if (persist) {
         p.vert = vert_ok ? 1 : 0;
         if (p.vert) { p.strip_len = vlen; p.strips_x = p.tiles_x; p.strips_y = p.tiles_y / vlen; }
@@ -1218,6 +1220,13 @@ extern "C" int mgf_conv3x3_winograd3_f32(float* y, const float* x, const float* 
                                          int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t out_scale_stride, const mgf_epilogue* ep,
                                          mgf_stream_t stream) {
     return launch_wino3(y, x, u, in_scale, out_scale, n, cin, h, w, cout, out_scale_stride, ep, nullptr, nullptr, nullptr, 0, stream);
+}
+
+// The MDF discriminators' body layers (csrc/mdf.hip): plain form-3 launch whose kernel choice depends on (cin, h, w) only, so that a
+// sample's result is the same bits whatever the batch it is launched in.
+int mgf_wino3_batch_invariant_f32(float* y, const float* x, const float* u, int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout,
+                                  const mgf_epilogue* ep, mgf_stream_t stream) {
+    return launch_wino3(y, x, u, nullptr, nullptr, n, cin, h, w, cout, 0, ep, nullptr, nullptr, nullptr, 0, stream, nullptr, 0, 0, true);
 }
 
 extern "C" int mgf_conv3x3_winograd3_slice_f32(float* y, const float* x, const float* u, const float* in_scale, const float* out_scale, int32_t n,

@@ -211,7 +211,8 @@ DEFAULT_BATCH = 32       # loop steps per generator forward in literal mode: the
 def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, percept=None, latent_mean=None, latent_std=None,
                   eps=None, out_prefix=None, batch=DEFAULT_BATCH, use_graph=True, noise_mode="random", use_mse=True, seed=None,
                   landmark_fn=None, mode="literal", weight_decay=0.0, path_to_gen=None, keep_images=64, engine=None,
-                  return_engine=False, latent_space="z", landmark_input="float", biometric=None, gamma=1.0, lbp_target=None, pipeline=None):
+                  return_engine=False, latent_space="z", landmark_input="float", biometric=None, gamma=1.0, lbp_target=None, pipeline=None,
+                  mdf=None):
     """One full `projection(...)` call (:135-208).  `target`: [1,3,S,S] from image_transform; `lm_target` [68,2] and either
     `lm_steps` [steps,68,2] (injected landmark detections) or `landmark_fn` (host detector called on every generated image,
     see ProjectionEngine; landmark_input="gray_u8" hands it the drivers' gray uint8 image, built on the device).  mode="literal" is the loop as the reference executes it (best-of-N noisy sampling, `batch` steps per
@@ -223,7 +224,9 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
 
     biometric / gamma: an iresnet.BiometricLoss (embedder "facenet" or "iresnetNN") adds gamma * MSE(embed(img), embed(target)) to the objective
     (BASELINE config 3; 1024_example_FaceNet_percept.py:147-158).  lbp_target: with args.pixel_term="lbp" the target FILE's LBP code map
-    (lbp.target_feature; 1024_example_LBP_percept.py:140).
+    (lbp.target_feature; 1024_example_LBP_percept.py:140).  mdf: an mdf.MDFLoss adds the MDF discriminator-feature loss in the p_loss slot --
+    the whole objective of 1024_example_mdfloss.py / projection_example_v1_mdfloss*.py with use_mse=False, args.min_loss_init=1000 (and
+    args.pool_above=256 for the v1 scripts); literal mode only.
 
     Outputs, like the drivers: with `path_to_gen` the SCORED image of every improvement -- the candidate as it was generated and
     ranked, its random per-layer noise included -- is written as `{path_to_gen}/{step:06d}_{loss:04f}.png` (:190-195; literal mode:
@@ -267,7 +270,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                                       ("percept", engine.percept is percept), ("use_mse", engine.use_mse == bool(use_mse)),
                                       ("noise_mode", engine.noise_mode == noise_mode), ("args", engine.args == args),
                                       ("landmark_fn", engine.landmark_fn is landmark_fn), ("biometric", engine.biometric is biometric),
-                                      ("gamma", biometric is None or engine.gamma == float(gamma))) if not ok]
+                                      ("gamma", biometric is None or engine.gamma == float(gamma)), ("mdf", engine.mdf is mdf)) if not ok]
         if diff:
             raise ValueError("engine= was built for another objective: " + ", ".join(diff) + " differ(s); build a fresh engine")
         eng = engine.retarget(target, lm_target=lm_target, lm_steps=lm_steps, eps=eps, seed=seed if eps is None else None,
@@ -276,12 +279,12 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
         eng = GradientProjectionEngine(G, target, latent_mean, float(latent_std), args, weight_decay=weight_decay, percept=percept,
                                        lm_target=lm_target, lm_steps=lm_steps, eps=eps, noise_mode=noise_mode, use_graph=use_graph,
                                        use_mse=use_mse, landmark_fn=landmark_fn, seed=0 if seed is None else seed, latent_space=latent_space,
-                                       biometric=biometric, gamma=gamma)
+                                       biometric=biometric, gamma=gamma, mdf=mdf)
     else:
         eng = ProjectionEngine(G, target, latent_mean, float(latent_std), args, percept=percept, lm_target=lm_target,
                                lm_steps=lm_steps, eps=eps, noise_mode=noise_mode, use_graph=use_graph, batch=batch, use_mse=use_mse,
                                landmark_fn=landmark_fn, keep_images=keep, seed=0 if seed is None else seed, landmark_input=landmark_input,
-                               biometric=biometric, gamma=gamma, lbp_target=lbp_target, pipeline=pipeline)
+                               biometric=biometric, gamma=gamma, lbp_target=lbp_target, pipeline=pipeline, mdf=mdf)
     w, step, loss, losses = eng.run().result()
     out = {"w": w, "step": step, "loss": loss, "losses": losses}
     if out_prefix is not None:

@@ -136,7 +136,7 @@ class ProjectionEngine:
     def __init__(self, G, target, latent_mean, latent_std, args: ProjectionArgs = None, percept=None, use_mse=True,
                  lm_target=None, lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, batch=1,
                  landmark_fn=None, biometric=None, gamma=1.0, wing_kind="wing", landmark_model=None, pipeline=False, keep_images=0,
-                 latent_shape=None, landmark_input="float", lbp_target=None):
+                 latent_shape=None, landmark_input="float", lbp_target=None, mdf=None):
         """batch = number of consecutive loop steps evaluated per generator forward.  In literal mode the steps do not depend
         on each other (latent_in never changes), so evaluating `batch` candidates at once and examining them in step order
         gives exactly the sequential loop's result while the small 4x4..64x64 layers, the mapping network and the LPIPS tail
@@ -159,6 +159,10 @@ class ProjectionEngine:
 
         biometric: optional `iresnet.BiometricLoss`; adds gamma * MSE(embed(img), embed(target)) to the objective (the
         FaceNet term of 1024_example_FaceNet_percept.py:147-158 on the vendored IResNet embedder).
+
+        mdf: optional `mdf.MDFLoss`; adds its per-candidate loss to the p_loss slot after LPIPS and the biometric term -- the whole
+        objective of the MDF drivers (1024_example_mdfloss.py:165, p_loss = criterion(imgs, img_gen), with use_mse=False and
+        min_loss_init 1000; on the pooled image when pool_above is set, projection_example_v1_mdfloss.py:153-157).
 
         landmark_model: optional DEVICE callable `m(img [B,3,H,W]) -> (landmarks [B,68,2] float64, valid [B] int32)` -- the GPU
         landmark-regressor interface of SURVEY.md 8f row 3.  It runs inside the launch sequence (graph-capturable if the model
@@ -189,7 +193,7 @@ class ProjectionEngine:
         self.use_lbp = a.pixel_term == "lbp"
         self.use_mse = use_mse and not self.use_lbp
         self.use_wing = lm_target is not None
-        if self.use_lbp and (lbp_target is None or self.use_wing or percept is not None or biometric is not None):
+        if self.use_lbp and (lbp_target is None or self.use_wing or percept is not None or biometric is not None or mdf is not None):
             raise _lib.MgfError("projection: pixel_term='lbp' is the whole objective of 1024_example_LBP_percept.py -- pass lbp_target "
                                 "(lbp.target_feature of the target file) and no landmark / LPIPS / biometric term")
         self.noise_mode = noise_mode
@@ -274,6 +278,9 @@ class ProjectionEngine:
         self.biometric, self.gamma = biometric, float(gamma)
         if biometric is not None:
             biometric.set_target(self.target)
+        self.mdf = mdf
+        if mdf is not None:
+            mdf.set_target(self.target)
         self.keep_images = int(keep_images)
         if self.keep_images > 0:
             per = G.cfg.img_channels * G.cfg.img_resolution ** 2
@@ -367,6 +374,8 @@ class ProjectionEngine:
                 self.p_loss.mul_(float(a.percept_weight))
         if self.biometric is not None:      # rides in the p_loss slot: p_loss = LPIPS + gamma * embedding MSE
             self.biometric.distance_into(self.p_loss, img, scale=self.gamma, accumulate=self.percept is not None)
+        if self.mdf is not None:            # p_loss (+)= MDF (1024_example_mdfloss.py:165)
+            self.mdf.distance_into(self.p_loss, img, accumulate=self.percept is not None or self.biometric is not None)
         if self.use_mse and a.pixel_term == "dssim":
             c, h, w = img.shape[1:]
             _lib.check(L.mgf_dssim_u8_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, c, h, w, 0, 255.0, 1.0, 0,
@@ -392,7 +401,7 @@ class ProjectionEngine:
         keep = self.keep_images > 0
         _lib.check(L.mgf_select_best(self.min_loss.data_ptr(), self.best_latent.data_ptr(), self.best_step.data_ptr(),
                                      self.losses.data_ptr(), latent_n.data_ptr(), self.numel,
-                                     _lib.ptr(self.p_loss if (self.percept is not None or self.biometric is not None) else None),
+                                     _lib.ptr(self.p_loss if (self.percept is not None or self.biometric is not None or self.mdf is not None) else None),
                                      _lib.ptr(self.w_loss if (self.use_wing or self.use_lbp) else None),
                                      _lib.ptr(self.mse_loss if self.use_mse else None), 1.0 if self.use_lbp else float(a.lamda), float(a.beta),
                                      self.step_ctr.data_ptr(), _lib.ptr(self.valid), B, self.steps,
@@ -699,6 +708,8 @@ class ProjectionEngine:
             self.percept.set_target(self.target)                  # same shapes: rewrites the cached taps in place
         if self.biometric is not None:
             self.biometric.set_target(self.target)
+        if self.mdf is not None:
+            self.mdf.set_target(self.target)
         if self.use_lbp:
             assert lbp_target is not None, "this engine scores the LBP distance: pass the new target's code map (lbp.target_feature)"
             self.lbp_codes.copy_(torch.as_tensor(lbp_target, dtype=torch.uint8).reshape(-1))
@@ -783,7 +794,7 @@ class GradientProjectionEngine(ProjectionEngine):
     def __init__(self, G, target, latent_mean, latent_std, args: ProjectionArgs = None, percept=None, use_mse=True, lm_target=None,
                  lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, landmark_fn=None, biometric=None,
                  gamma=1.0, wing_kind="wing", landmark_model=None, betas=(0.9, 0.999), adam_eps=1e-8, weight_decay=0.0,
-                 latent_space="z", **ignored):
+                 latent_space="z", mdf=None, **ignored):
         """latent_space: "z" -- the drivers' parameter, the gradient runs on through the mapping network -- or "w+": the parameter is the
         per-layer intermediate latent ws [k, num_ws, D] itself (north_star: "backprops into the k-component latent W+"; layer `slot` reads
         ws[:, slot], networks.py:1252-1253), perturbed, descended by Adam and kept best-of exactly like z.  latent_mean is then a w-space
@@ -791,6 +802,9 @@ class GradientProjectionEngine(ProjectionEngine):
         reference has no such driver (its "W+" averages 18 copies of z, projection_example_v2_percept.py:133-162); the oracle is torch autograd
         + Adam on ws through the CPU restatement (tests/test_hip_gradient.py)."""
         from .grad import GeneratorGrad
+        if mdf is not None:
+            raise _lib.MgfError("GradientProjectionEngine: the MDF objective has no backward pass -- the reference's MDF drivers "
+                                "(1024_example_mdfloss.py, projection_example_v1_mdfloss*.py) are literal loops: use ProjectionEngine(mdf=...)")
         assert latent_space in ("z", "w+"), latent_space
         self.latent_space = latent_space
         ls = (G.cfg.k, G.cfg.num_ws, G.cfg.w_dim) if latent_space == "w+" else (G.cfg.k, G.cfg.z_dim)
