@@ -244,6 +244,18 @@ int mgf_tconv3x3s2_border_f32(float* t, const float* x, const float* wp, const f
                               int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t cout_pad, int64_t t_pitch, int64_t t_plane,
                               int64_t t_batch, int64_t out_scale_stride, mgf_stream_t stream);
 
+/* The stride-2 transposed 3x3 conv of mgf_conv_taps_f32's tconv launch (t[n, co, 2i+kh, 2j+kw] += w[kh,kw] x[n, ci, i, j], x scaled by
+ * in_scale [n,cin] | NULL, the sum by out_scale | NULL) in polyphase Winograd form (csrc/wino_tconv.hip: 25 products per 2x2 input block
+ * instead of 36).  Writes rows / columns 0 .. 2h-1 / 2w-1 of t [n, cout, 2h+1, pitch] (t_plane, t_batch elements between channels /
+ * samples); row and column 2h / 2w come from mgf_tconv3x3s2_border_f32.  u from mgf_tconv_winograd_weights_f32; h, w even, cin % 4 == 0,
+ * cout % 32 == 0, pitch / t_plane / t_batch multiples of 4, t and u 16-byte aligned. */
+int mgf_tconv3x3s2_winograd_f32(float* t, const float* x, const float* u, const float* in_scale, const float* out_scale, int32_t n,
+                                int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t pitch, int64_t t_plane, int64_t t_batch,
+                                int64_t out_scale_stride, mgf_stream_t stream);
+/* Its weights: [cout, cin, 3, 3] float32 -> u [25][cin / 4][cout][4] = gain * (T w T^T) with T = [[0,0,1],[1,0,1],[1,0,0],[0,1,0],[0,1,0]],
+ * summed in float64 and rounded once; cin % 4 == 0.  Device pointers. */
+int mgf_tconv_winograd_weights_f32(float* u, const float* w, int32_t cout, int32_t cin, double gain, mgf_stream_t stream);
+
 /* Repack [cout, cin, kh, kw] float32 weights (times `gain`) into the [tap][cin][cout_pad] image read by
  * mgf_conv_taps_f32; `flip` reverses kh,kw (true convolution).  Taps are emitted in (kh, kw) row-major order.
  * Also emits wsq[cout, cin] = sum_k (w*gain)^2 when wsq != NULL (demodulation table). Device pointers. */

@@ -458,10 +458,37 @@ def conv3x3_few_outputs(x, w, bias=None, out=None):
     return out
 
 
-def tconv3x3s2_forward(x, pc: PackedConv, in_scale=None, out_scale=None, out=None, bf=None):
+TCONV_WINO = os.environ.get("MGF_TCONV_WINO", "1") != "0"                 # tuning hook: 0 = every transposed conv on the tap-list kernel
+# fewest workgroups the Winograd launch takes: 16 x 512 x 512 at 32 samples (2048) is 202 us slower than the tap-list launch, 32 x 512 x 512
+# (4096) 231 us faster (tools/tconv_wino_micro.py); one-target gradient mode and the 16-target lockstep's 32^2 layer stay on the tap list
+TCONV_WINO_MIN_WGS = 4096
+
+
+def tconv_winograd_weights(w: torch.Tensor, gain: float = 1.0) -> torch.Tensor:
+    """Weights of the polyphase Winograd transposed conv (mgf_tconv3x3s2_winograd_f32): [25, cin / 4, cout, 4] from [cout, cin, 3, 3]."""
+    _lib.require_gpu(w)
+    w = w.contiguous().float()
+    cout, cin, kh, kw = w.shape
+    assert (kh, kw) == (3, 3) and cin % 4 == 0
+    u = torch.empty([25, cin // 4, cout, 4], dtype=torch.float32, device=w.device)
+    _lib.check(_lib.lib().mgf_tconv_winograd_weights_f32(u.data_ptr(), w.data_ptr(), cout, cin, float(gain), _lib.stream_ptr()),
+               "tconv_winograd_weights")
+    return u
+
+
+def tconv_winograd_ok(n, cin, h, w, cout, out, bf=None) -> bool:
+    """The polyphase Winograd launch serves float32 calls on even maps with whole 4-channel chunks and 32-channel tiles, a 16-byte
+    aligned workspace and enough workgroups to fill the chip (32 channels x 32 input blocks each); the rest keeps the tap-list kernel."""
+    return bool(TCONV_WINO and SPLIT_TCONV_BORDER and bf is None and h % 2 == 0 and w % 2 == 0 and min(h, w) >= TCONV_SPLIT_MIN and cin % 4 == 0 and cout % 32 == 0
+                and out.shape[3] % 4 == 0 and out.data_ptr() % 16 == 0
+                and n * -(-h // 4) * -(-w // 32) * (cout // 32) >= TCONV_WINO_MIN_WGS)
+
+
+def tconv3x3s2_forward(x, pc: PackedConv, in_scale=None, out_scale=None, out=None, bf=None, wt=None):
     """Stride-2 3x3 transposed convolution t[2i+kh, 2j+kw] += w[kh,kw] x[i,j] -> view [n, cout, 2h+1, 2w+1] of a padded-pitch
-    workspace (row pitch a multiple of 4 floats so the parity pairs are written as aligned float2)."""
-    _lib.require_gpu(x, pc.wp, in_scale, out_scale, out)
+    workspace (row pitch a multiple of 4 floats so the parity pairs are written as aligned float2).
+    wt: the layer's tconv_winograd_weights, or None; with it, shapes tconv_winograd_ok accepts take the polyphase Winograd launch."""
+    _lib.require_gpu(x, pc.wp, in_scale, out_scale, out, wt)
     assert pc.kh == 3 and pc.kw == 3 and x.dtype == torch.float32 and x.is_contiguous()
     n, cin, h, w = x.shape
     oh, ow = 2 * h + 1, 2 * w + 1
@@ -479,6 +506,17 @@ def tconv3x3s2_forward(x, pc: PackedConv, in_scale=None, out_scale=None, out=Non
         rc = _lib.lib().mgf_tconv3x3s2_few_outputs_f32(out.data_ptr(), x.data_ptr(), pc.wp.data_ptr(), n, cin, h, w, pc.cout, pc.cout_pad,
                                                        pitch, oh * pitch, pc.cout * oh * pitch, _lib.stream_ptr())
         _lib.check(rc, "tconv3x3s2_few_outputs")
+        return out[:, :, :, :ow]
+    if wt is not None and tconv_winograd_ok(n, cin, h, w, pc.cout, out, bf):
+        assert tuple(wt.shape) == (25, cin // 4, pc.cout, 4)
+        os_stride = 0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0
+        rc = _lib.lib().mgf_tconv3x3s2_winograd_f32(out.data_ptr(), x.data_ptr(), wt.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale), n, cin, h,
+                                                    w, pc.cout, pitch, oh * pitch, pc.cout * oh * pitch, os_stride, _lib.stream_ptr())
+        _lib.check(rc, "tconv3x3s2_winograd")
+        rc = _lib.lib().mgf_tconv3x3s2_border_f32(out.data_ptr(), x.data_ptr(), pc.wp.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale),
+                                                  n, cin, h, w, pc.cout, pc.cout_pad, pitch, oh * pitch, pc.cout * oh * pitch, os_stride,
+                                                  _lib.stream_ptr())
+        _lib.check(rc, "tconv3x3s2_border")
         return out[:, :, :, :ow]
     # (one or two images -- gradient mode at a single target -- keep the single launch up to 64 px: the border kernel's few workgroups then
     # cost more than the padded tiles, 6.76 -> 6.64 ms per gradient step; from four images on the split wins from 16 px, 686 vs 677 iters/s)

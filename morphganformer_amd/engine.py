@@ -32,6 +32,9 @@ SQRT2 = math.sqrt(2.0)
 SQRT_HALF = math.sqrt(0.5)
 USE_WINOGRAD = os.environ.get("MGF_WINOGRAD", "1") != "0"
 WINOGRAD_MAX_RES = int(os.environ.get("MGF_WINOGRAD_MAX_RES", "1024"))
+# largest block whose up-sampling conv takes the polyphase Winograd kernel (tools/tconv_wino_micro.py, 32 samples, with the border kernel: 64^2
+# -231 us, 128^2 -175, 256^2 -156 against the tap-list launch; 512^2 at parity (-12), 1024^2 +524 -- the shallow-K layers keep the tap list)
+TCONV_WINO_MAX_RES = int(os.environ.get("MGF_TCONV_WINO_MAX_RES", "256"))
 BF_DIRECT_MAX_RES = int(os.environ.get("MGF_BF_DIRECT_MAX_RES", "128"))     # arith="bf16x3": largest map whose 3x3 layers leave Winograd (tuning hook)
 
 
@@ -101,6 +104,7 @@ class ConvLayerPlan:
     w_raw: torch.Tensor = None      # toRGB only: [img_channels, cin] un-packed weights for the fused projection
     w_gained: torch.Tensor = None   # conv_last only: [cout, cin, 3, 3] weights times w_gain, un-packed, for the composition with ToRGB
     wino_u: torch.Tensor = None     # 3x3 stride-1 layers on 16^2 .. 256^2 maps: Winograd-transformed weights (csrc/wino.hip)
+    wino_t: torch.Tensor = None     # transposed convs of the blocks up to TCONV_WINO_MAX_RES: polyphase Winograd weights (csrc/wino_tconv.hip)
     pcb: torch.Tensor = None        # arith="bf16x3" only: the weights split into two bfloat16 terms (conv.pack_weights_bf16x3)
     s_off: int = 0                  # offsets (floats) into the per-sample style / demod arenas
     d_off: int = 0
@@ -160,6 +164,10 @@ class SynthesisPlan:
                 # everywhere, MGF_WINOGRAD_MAX_RES limits the map size
                 if kind == "conv3" and USE_WINOGRAD and cv.winograd_ok(cin, cout, res, res) and res <= WINOGRAD_MAX_RES:
                     lp.wino_u = cv.winograd_pack(t32(w), wg, res)
+                # polyphase Winograd transposed conv (float32 mode): the up-sampling layers into the blocks up to TCONV_WINO_MAX_RES
+                if (kind == "tconv" and arith != "bf16x3" and cv.TCONV_WINO and res <= TCONV_WINO_MAX_RES and cin % 4 == 0
+                        and cout % 32 == 0):
+                    lp.wino_t = cv.tconv_winograd_weights(t32(w), wg)
                 # the opt-in bf16x3 arithmetic: every transposed conv and 3x3 layer the kernel serves (maps at least 32 wide, cin % 16 == 0)
                 if arith == "bf16x3" and cin % 16 == 0 and res // up >= 32:
                     lp.pcb = cv.pack_weights_bf16x3(lp.pc)
@@ -709,7 +717,7 @@ class Generator:
         has_att = lp.attn is not None
         s, d = self._s(lp), self._d(lp)
         if lp.kind == "tconv":
-            t = cv.tconv3x3s2_forward(x, lp.pc, in_scale=s, out_scale=d, out=B["t"], bf=lp.pcb)
+            t = cv.tconv3x3s2_forward(x, lp.pc, in_scale=s, out_scale=d, out=B["t"], bf=lp.pcb, wt=lp.wino_t)
             # plan.fir is the outer product of the 1-D resample kernel (networks.py:1113 / upfirdn2d.setup_filter): separable
             y = cv.upfirdn_into(B[key], t, self.plan.fir, up=1, pad=(1, 1, 1, 1), gain=4.0, epilogue=None if has_att else ep,
                                 separable=True)
