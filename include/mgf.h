@@ -726,6 +726,26 @@ int mgf_mdf_tail_f32(float* x3, double* part2, double* part3, const float* x2, c
                      const float* x3_target, int32_t n, int32_t c, int32_t h, int32_t wd, int32_t ring, mgf_stream_t stream);
 int mgf_mdf_finish_f32(float* out, const double* part, int32_t nslots, int64_t nblk, const double* counts, int32_t n, float scale,
                        int32_t accumulate, mgf_stream_t stream);
+/* MDF backward (gradient mode: dimg (+)= s * d loss / d img per candidate, the forward's frames and ring depths; phi'(a) = a > 0 ? 1 : slope
+ * of the stored post-activation, torch's in-place LeakyReLU backward).  Every gradient frame is written whole and is 0 outside its ring
+ * (a Winograd tile straddling the ring boundary would otherwise mix in whatever lies outside).
+ *   tail_backward: d3 [n,c,h,w] = (tail_adj(g3) + coef2 (x2 - x2_target)) * phi'(x2) on ring `ring` (4), 0 elsewhere, with
+ *           g3 = coef3 (x3 - x3_target) on ring + 1 and 0 elsewhere formed on the fly from x3 [n,h,w] (valid on ring + 1 only) and
+ *           x3_target [h,w]; x2_target [c,h,w]; w the tail weights [c][3][3]; coef2 = s 2 / count(x2), coef3 = s 2 / count(x3)
+ *   body_backward: d [n,c,h,w] = conv_pad1(g, w~) * phi'(a_prev) on ring `ring`, 0 elsewhere; u_adj = mgf_winograd2_weights_f32(w~),
+ *           w~[ci][co][kh][kw] = w[co][ci][2-kh][2-kw] (the adjoint of a body block); c in {32, 64, 128}; the batch-invariant form-3
+ *           launch of mgf_mdf_body_f32 with a masked epilogue that reads a_prev where the residual would be: a candidate's gradient is the
+ *           same bits in any batch
+ *   head_backward: dimg [n,3,h,w] (+)= conv_pad1(d0, w~_head) on the whole frame, d0 = d0m + coef1 (x1 - x1_target) phi'(x1) on ring 1 and 0
+ *           elsewhere (d0m: body_backward of the first body block, ring 1; x1_target [c,h,w]; coef1 = s 2 / count(x1)); w the head weights
+ *           [c][3][3][3] in the forward's layout; no atomics, one launch per discriminator, `accumulate` chains them in a fixed order */
+int mgf_mdf_tail_backward_f32(float* d3, const float* x2, const float* x2_target, const float* x3, const float* x3_target, const float* w,
+                              int32_t n, int32_t c, int32_t h, int32_t wd, int32_t ring, float coef2, float coef3, float slope,
+                              mgf_stream_t stream);
+int mgf_mdf_body_backward_f32(float* d, const float* g, const float* u_adj, const float* a_prev, int32_t n, int32_t c, int32_t h, int32_t wd,
+                              int32_t ring, float slope, mgf_stream_t stream);
+int mgf_mdf_head_backward_f32(float* dimg, const float* d0, const float* x1, const float* x1_target, const float* w, int32_t n, int32_t c,
+                              int32_t h, int32_t wd, float coef1, float slope, int32_t accumulate, mgf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -183,6 +183,9 @@ _SIGS = {
     "mgf_mdf_body_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
     "mgf_mdf_tail_f32": (C.c_int, [vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "mgf_mdf_finish_f32": (C.c_int, [vp, vp, i32, i64, C.POINTER(f64), i32, f32, i32, vp]),
+    "mgf_mdf_tail_backward_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp]),
+    "mgf_mdf_body_backward_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]),
+    "mgf_mdf_head_backward_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, vp]),
 }
 
 EXPORTED_SYMBOLS = sorted(_SIGS)

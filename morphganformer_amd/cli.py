@@ -87,7 +87,8 @@ def _loop_arguments(p):
     p.add_argument("--mdf", type=str, default=None, metavar="DS_PTH",
                    help="add the MDF discriminator-feature loss of a Ds_*.pth file (mdf-main/weights/Ds_{SISR,Denoising,JPEG}.pth, what --mdfapp "
                         "picks) -- alone, as 1024_example_mdfloss.py scores: --no-lpips --no-mse --min-loss-init 1000; the v1 scripts "
-                        "(projection_example_v1_mdfloss*.py) add --pool-above 256; literal mode only")
+                        "(projection_example_v1_mdfloss*.py) add --pool-above 256 (literal mode); with --mode gradient the loss is differentiated into the "
+                        "latent, 1024_example_mdfloss.py's loop without its detach (one target per engine)")
     p.add_argument("--mdf-scales", type=int, default=8, help="discriminators the MDF loss uses (num_scales, default 8)")
     p.add_argument("--mdf-descending", action="store_true", help="use the discriminators from the last one down (is_ascending=0)")
     p.add_argument("--mdf-random", action="store_true", help="seeded random discriminators instead of --mdf (smoke runs only)")
@@ -187,6 +188,11 @@ def _extract_facenet(a):
     return 0
 
 
+def mdf_options(a):
+    """MDFLoss keyword arguments of the parsed command line: gradient mode builds the loss with its backward pass."""
+    return dict(num_scales=a.mdf_scales, is_ascending=0 if a.mdf_descending else 1, differentiable=a.mode == "gradient")
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.cmd == "merge-files":                              # file bookkeeping only (1024_merge_files.py): no generator, no GPU
@@ -267,8 +273,7 @@ def main(argv=None):
         from .mdf import MDFLoss, random_discriminators
         if a.mdf_random:
             print("WARNING: the MDF term runs on seeded random discriminators (--mdf-random); it is not the trained loss")
-        mdf = MDFLoss(random_discriminators(0) if a.mdf_random else a.mdf, num_scales=a.mdf_scales, is_ascending=0 if a.mdf_descending else 1,
-                      device=G.device)
+        mdf = MDFLoss(random_discriminators(0) if a.mdf_random else a.mdf, device=G.device, **mdf_options(a))
     if percept is None and a.no_mse and biometric is None and mdf is None and not getattr(a, "landmarks", None) and a.pixel_term != "lbp":
         raise SystemExit(f"{a.cmd}: every term of the objective is switched off")
     if a.pixel_term == "lbp" and (a.cmd != "project" or a.mode != "literal"):

@@ -158,6 +158,86 @@ __global__ __launch_bounds__(256) void mdf_finish_kernel(float* out, const doubl
     }
 }
 
+
+// ---- backward (dimg (+)= s * d loss / d img).  Frames as in the forward; phi'(a) = a > 0 ? 1 : slope of the stored POST-activation (torch's
+// in-place LeakyReLU backward).  Every gradient frame is written whole, 0 outside its ring: the adjoint Winograd launches read it zero-padded.
+
+// d3 [n,c,h,w] = (sum_{kh,kw} w[c,kh,kw] g3[y - kh + 1, x - kw + 1] + coef2 (x2 - x2_target)) * phi'(x2) on ring r, 0 elsewhere, with
+// g3 = coef3 (x3 - x3_target) on ring r + 1 and 0 elsewhere, formed on the fly from x3 (no g3 buffer)
+__global__ __launch_bounds__(256) void mdf_tail_bwd_kernel(float* __restrict__ d3, const float* __restrict__ x2, const float* __restrict__ x2t,
+                                                           const float* __restrict__ x3, const float* __restrict__ x3t, const float* w,
+                                                           int c, int h, int wd, int r, float coef2, float coef3, float slope) {
+    const int x = blockIdx.x * MDF_BX + threadIdx.x, y = blockIdx.y * MDF_BY + threadIdx.y, n = blockIdx.z;
+    if (x >= wd || y >= h) return;
+    const bool v2 = x >= r && x < wd - r && y >= r && y < h - r;
+    const int64_t plane = (int64_t)h * wd, pix = (int64_t)y * wd + x;
+    float* db = d3 + (int64_t)n * c * plane + pix;
+    if (!v2) {
+        for (int ci = 0; ci < c; ++ci) db[ci * plane] = 0.f;
+        return;
+    }
+    float g[9];                                           // g[k]: g3 at (y - kh + 1, x - kw + 1), k = 3 kh + kw
+    const float* x3b = x3 + (int64_t)n * plane;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int yy = y - k / 3 + 1, xx = x - k % 3 + 1;
+        const bool v3 = xx >= r + 1 && xx < wd - r - 1 && yy >= r + 1 && yy < h - r - 1;
+        const int64_t q = (int64_t)yy * wd + xx;
+        g[k] = v3 ? coef3 * (x3b[q] - x3t[q]) : 0.f;
+    }
+    const float* xb = x2 + (int64_t)n * c * plane + pix;
+    const mdf_cfp ws = (mdf_cfp)w;
+    for (int ci = 0; ci < c; ++ci) {
+        const mdf_cfp wr = ws + ci * 9;
+        float a = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) a = fmaf(wr[k], g[k], a);
+        const float xv = xb[ci * plane];
+        a = fmaf(coef2, xv - x2t[ci * plane + pix], a);
+        db[ci * plane] = xv > 0.f ? a : a * slope;
+    }
+}
+
+// dimg [n,3,h,w] (+)= sum_{co,kh,kw} w[co,ci,kh,kw] d0[co, y - kh + 1, x - kw + 1] on the whole frame (the head's adjoint: pad 1), with
+// d0 = d0m + coef1 (x1 - x1_target) phi'(x1) on ring 1 and 0 elsewhere -- d0m is the masked adjoint of the first body block, the tap-0
+// term joins here
+__global__ __launch_bounds__(256) void mdf_head_bwd_kernel(float* __restrict__ dimg, const float* __restrict__ d0m, const float* __restrict__ x1,
+                                                           const float* __restrict__ x1t, const float* w, int c, int h, int wd, float coef1,
+                                                           float slope, int accumulate) {
+    const int x = blockIdx.x * MDF_BX + threadIdx.x, y = blockIdx.y * MDF_BY + threadIdx.y, n = blockIdx.z;
+    if (x >= wd || y >= h) return;
+    const int64_t plane = (int64_t)h * wd;
+    int64_t off[9];
+    bool ok[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int yy = y - k / 3 + 1, xx = x - k % 3 + 1;
+        ok[k] = xx >= 1 && xx < wd - 1 && yy >= 1 && yy < h - 1;
+        off[k] = ok[k] ? (int64_t)yy * wd + xx : 0;
+    }
+    const float* db = d0m + (int64_t)n * c * plane;
+    const float* xb = x1 + (int64_t)n * c * plane;
+    const mdf_cfp ws = (mdf_cfp)w;
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int co = 0; co < c; ++co) {
+        const int64_t cp = co * plane;
+        const mdf_cfp wr = ws + co * 27;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            float d = 0.f;
+            if (ok[k]) {
+                const float xv = xb[cp + off[k]], t = coef1 * (xv - x1t[cp + off[k]]);
+                d = db[cp + off[k]] + (xv > 0.f ? t : t * slope);
+            }
+#pragma unroll
+            for (int ci = 0; ci < 3; ++ci) acc[ci] = fmaf(wr[ci * 9 + k], d, acc[ci]);
+        }
+    }
+    float* ob = dimg + (int64_t)n * 3 * plane + (int64_t)y * wd + x;
+#pragma unroll
+    for (int ci = 0; ci < 3; ++ci) ob[ci * plane] = accumulate ? ob[ci * plane] + acc[ci] : acc[ci];
+}
+
 }  // namespace
 
 extern "C" int64_t mgf_mdf_partials(int32_t h, int32_t w) {
@@ -218,5 +298,41 @@ extern "C" int mgf_mdf_finish_f32(float* out, const double* part, int32_t nslots
     }
     hipLaunchKernelGGL(mdf_finish_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, out, part, nslots, nblk, n, a, scale, accumulate);
     MGF_CHECK_LAUNCH("mdf_finish");
+    return MGF_OK;
+}
+
+extern "C" int mgf_mdf_tail_backward_f32(float* d3, const float* x2, const float* x2_target, const float* x3, const float* x3_target, const float* w,
+                                         int32_t n, int32_t c, int32_t h, int32_t wd, int32_t ring, float coef2, float coef3, float slope,
+                                         mgf_stream_t stream) {
+    MGF_REQUIRE(d3 && x2 && x2_target && x3 && x3_target && w && n >= 1 && n <= 65535 && ring >= 0 && h - 2 * ring >= 3 && wd - 2 * ring >= 3 &&
+                h <= 65535 * MDF_BY, MGF_EINVAL, "mdf_tail_backward: bad arguments");
+    MGF_REQUIRE(c >= 1 && c <= MDF_MAX_C, MGF_EUNSUPPORTED, "mdf_tail_backward: 1 .. %d channels (got %d)", MDF_MAX_C, c);
+    const dim3 grid((unsigned)mgf_cdiv(wd, MDF_BX), (unsigned)mgf_cdiv(h, MDF_BY), (unsigned)n), blk(MDF_BX, MDF_BY);
+    mgf_prof_external_begin((hipStream_t)stream, "mdf_tail_bwd_kernel", 2.0 * 10 * c * (double)h * wd * n,
+                            4.0 * (double)h * wd * (n * (2.0 * c + 1) + c + 1));
+    hipLaunchKernelGGL(mdf_tail_bwd_kernel, grid, blk, 0, (hipStream_t)stream, d3, x2, x2_target, x3, x3_target, w, c, h, wd, ring, coef2, coef3, slope);
+    mgf_prof_external_end((hipStream_t)stream);
+    MGF_CHECK_LAUNCH("mdf_tail_backward");
+    return MGF_OK;
+}
+
+extern "C" int mgf_mdf_body_backward_f32(float* d, const float* g, const float* u_adj, const float* a_prev, int32_t n, int32_t c, int32_t h,
+                                         int32_t wd, int32_t ring, float slope, mgf_stream_t stream) {
+    MGF_REQUIRE(d && g && u_adj && a_prev && n >= 1 && h >= 3 && wd >= 3 && ring >= 1, MGF_EINVAL, "mdf_body_backward: bad arguments");
+    MGF_REQUIRE(c == 32 || c == 64 || c == 128, MGF_EUNSUPPORTED, "mdf_body_backward: 32, 64 or 128 channels (got %d)", c);
+    return mgf_wino3_batch_invariant_masked_f32(d, g, u_adj, a_prev, n, c, h, wd, ring, slope, stream);
+}
+
+extern "C" int mgf_mdf_head_backward_f32(float* dimg, const float* d0, const float* x1, const float* x1_target, const float* w, int32_t n,
+                                         int32_t c, int32_t h, int32_t wd, float coef1, float slope, int32_t accumulate, mgf_stream_t stream) {
+    MGF_REQUIRE(dimg && d0 && x1 && x1_target && w && n >= 1 && n <= 65535 && h >= 3 && wd >= 3 && h <= 65535 * MDF_BY, MGF_EINVAL,
+                "mdf_head_backward: bad arguments");
+    MGF_REQUIRE(c >= 1 && c <= MDF_MAX_C, MGF_EUNSUPPORTED, "mdf_head_backward: 1 .. %d channels (got %d)", MDF_MAX_C, c);
+    const dim3 grid((unsigned)mgf_cdiv(wd, MDF_BX), (unsigned)mgf_cdiv(h, MDF_BY), (unsigned)n), blk(MDF_BX, MDF_BY);
+    mgf_prof_external_begin((hipStream_t)stream, "mdf_head_bwd_kernel", 2.0 * 27 * c * (double)h * wd * n,
+                            4.0 * (double)h * wd * (n * (2.0 * c + 3 * (accumulate ? 2 : 1)) + c));
+    hipLaunchKernelGGL(mdf_head_bwd_kernel, grid, blk, 0, (hipStream_t)stream, dimg, d0, x1, x1_target, w, c, h, wd, coef1, slope, accumulate);
+    mgf_prof_external_end((hipStream_t)stream);
+    MGF_CHECK_LAUNCH("mdf_head_backward");
     return MGF_OK;
 }

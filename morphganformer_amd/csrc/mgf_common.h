@@ -58,6 +58,9 @@ void mgf_prof_external_end(hipStream_t st);
 // form-3 Winograd launch whose kernel choice depends on the layer's shape only (wino3.hip; the MDF body layers of mdf.hip)
 int mgf_wino3_batch_invariant_f32(float* y, const float* x, const float* u, int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout,
                                   const mgf_epilogue* ep, mgf_stream_t stream);
+// ... with the masked epilogue of the MDF backward: y = conv_pad1(x, u) * (mask > 0 ? 1 : slope) on ring `ring`, 0 outside (cin = cout = c)
+int mgf_wino3_batch_invariant_masked_f32(float* y, const float* x, const float* u, const float* mask, int32_t n, int32_t c, int32_t h, int32_t w,
+                                         int32_t ring, float slope, mgf_stream_t stream);
 
 #ifdef __HIPCC__
 // Sum over the 64 lanes of a wave (DPP/bpermute butterflies emitted by the compiler for __shfl_xor).

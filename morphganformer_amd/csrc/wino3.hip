@@ -58,6 +58,8 @@ struct Wino3Params {
     int low_pieces;           // the half-resolution residual's rows are whole 16-byte pieces (one-shot kernel: three 16-byte DMAs per lane instead of nine 4-byte ones)
     int strip_len, strips_x;  // persistent form (wino3p_conv_kernel): tiles per workgroup, strips per tile row
     int vert, strips_y;       // ... vert: a strip walks DOWN a 32-pixel column (strips_x = tile columns, strips_y = strips per column)
+    int mask_ring;            // masked variants (MASK = true): outputs outside ring mask_ring are 0, inside acc * (m > 0 ? 1 : mask_slope)
+    float mask_slope;         // with m = ep.residual at the output (the MDF backward: the adjoint conv times LeakyReLU' of the stored activation)
 };
 
 #ifndef W3_OCC1
@@ -67,8 +69,10 @@ constexpr int W3CK = 4;                    // input channels per chunk
 constexpr int W3FW = 34;                   // footprint width: 16 tiles x 2 + 2
 __constant__ float w3_ones[W3CK] = {1.f, 1.f, 1.f, 1.f};          // the "styles" of an un-modulated launch (read with stride 0)
 
-template <int CB, int TB, bool RGB>
+// (MASK: the masked epilogue of the MDF backward -- see Wino3Params::mask_ring -- instead of the fused one)
+template <int CB, int TB, bool RGB, bool MASK = false>
 __global__ __launch_bounds__(256, (CB * TB == 2 ? 2 : W3_OCC1)) void wino3_conv_kernel(Wino3Params p) {
+    static_assert(!MASK || (CB == 1 && TB == 1 && !RGB), "the masked epilogue is built for the one-block shape");
     constexpr int NB = CB * TB;                                    // 32x32 blocks per position and wave: 2 (128 accumulators) or 1 (64)
     static_assert(NB == 1 || NB == 2, "a wave carries one or two 32x32 blocks per position");
     constexpr int FH = 4 * TB + 2, FP = FH * W3FW;                 // footprint rows / pixels per channel
@@ -544,12 +548,18 @@ __global__ __launch_bounds__(256, (CB * TB == 2 ? 2 : W3_OCC1)) void wino3_conv_
             float v[2];
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
+                if constexpr (MASK) {
+                    const float t = pa[(2 * k + q) * 64] + sgn * (own[2 * k + q] + pb[(2 * k + q) * 64]), m = q ? rr[k].y : rr[k].x;
+                    const int r = p.mask_ring, px = ox + q;
+                    v[q] = (oy >= r && oy < p.h - r && px >= r && px < p.w - r) ? (m > 0.f ? t : t * p.mask_slope) : 0.f;
+                } else {
                 float t = (pa[(2 * k + q) * 64] + sgn * (own[2 * k + q] + pb[(2 * k + q) * 64])) * osv[k];
                 t += nzq[q];
                 t += do_ep ? bvv[k] : 0.f;
                 { float ts = t * slope, m; asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(t), "v"(ts)); t = m; }   // slope in [0, 1] (host-checked): leaky / plain ReLU / identity = max(t, slope t); as an instruction: `fmaxf` adds a canonicalising v_max x, x
                 t = t * gain + (q ? rr[k].y : rr[k].x);
                 v[q] = t;
+                }
             }
             vout[k] = make_float2(v[0], v[1]);
         }
@@ -627,8 +637,9 @@ __device__ __forceinline__ void w3_dma_b128(w3_v4i rsrc, unsigned lds_addr, unsi
 #ifndef W3P_XD_RGB
 #define W3P_XD_RGB 8
 #endif
-template <int NCK, bool RGB>
+template <int NCK, bool RGB, bool MASK = false>
 __global__ __launch_bounds__(256, 2) void wino3p_conv_kernel(Wino3Params p) {
+    static_assert(!MASK || !RGB, "the masked epilogue replaces the plain one");
     static_assert(NCK % 2 == 0 && NCK >= 4, "the staging buffers alternate per chunk");
     constexpr int FP = 6 * W3FW;                                   // footprint pixels per channel (6 rows x 34)
     constexpr int CST = 256, RAW = W3CK * CST;
@@ -919,12 +930,18 @@ __global__ __launch_bounds__(256, 2) void wino3p_conv_kernel(Wino3Params p) {
             float v[2];
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
+                if constexpr (MASK) {
+                    const float t = pa[(2 * k + q) * 64] + sgn * (own[2 * k + q] + pb[(2 * k + q) * 64]), m = q ? rr[k].y : rr[k].x;
+                    const int r = p.mask_ring, px = ox + q;
+                    v[q] = (oy >= r && oy < p.h - r && px >= r && px < p.w - r) ? (m > 0.f ? t : t * p.mask_slope) : 0.f;
+                } else {
                 float tt = (pa[(2 * k + q) * 64] + sgn * (own[2 * k + q] + pb[(2 * k + q) * 64])) * osv[k];
                 tt += q ? nz1 : nz0;
                 tt += bvv[k];
                 { float ts = tt * slope, m; asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(tt), "v"(ts)); tt = m; }   // (slope in [0, 1]: max(t, slope t), one instruction instead of compare + select)
                 tt = tt * gain + (q ? rr[k].y : rr[k].x);
                 v[q] = tt;
+                }
             }
             vout[k] = make_float2(v[0], v[1]);
         }
@@ -1065,7 +1082,7 @@ extern "C" int mgf_winograd3_force_shape(int32_t shape) {
 static int launch_wino3(float* y, const float* x, const float* u, const float* in_scale, const float* out_scale, int32_t n, int32_t cin, int32_t h,
                         int32_t w, int32_t cout, int32_t out_scale_stride, const mgf_epilogue* ep, const float* rgb_w, const float* rgb_bias,
                         float* rgb_out, int32_t rgb_channels, mgf_stream_t stream, const float* res_low = nullptr, int64_t y_batch = 0,
-                        int32_t y_choff = 0, bool batch_invariant = false) {
+                        int32_t y_choff = 0, bool batch_invariant = false, bool masked = false, int32_t mask_ring = 0, float mask_slope = 0.f) {
     const bool rgb = rgb_out != nullptr;
     MGF_REQUIRE((y || rgb) && x && u && n >= 1 && cin >= 1 && cout >= 1 && h >= 2 && w >= 2, MGF_EINVAL, "conv3x3_winograd3: bad arguments");
     MGF_REQUIRE(cin % W3CK == 0 && cout % 32 == 0, MGF_EUNSUPPORTED, "conv3x3_winograd3: cin must be a multiple of %d and cout of 32 (got %d, %d)",
@@ -1124,6 +1141,9 @@ static int launch_wino3(float* y, const float* x, const float* u, const float* i
     p.res_low = res_low;
     p.y_batch = y_batch ? y_batch : (int64_t)cout * h * w; p.y_choff = y_choff; p.odd = odd;
     p.strip_len = 0; p.strips_x = 0; p.vert = 0; p.strips_y = 0;
+    p.mask_ring = mask_ring; p.mask_slope = mask_slope;
+    MGF_REQUIRE(!masked || (batch_invariant && shape == 11 && !rgb && !res_low && ep && ep->residual), MGF_EINVAL,
+                "conv3x3_winograd3: the masked epilogue is a batch-invariant one-block launch with a mask map");
     static const bool pieces_off = [] { const char* e = mgf_knob("MGF_W3_LOW_PIECES"); return e && e[0] == '0'; }();   // tuning hook (A/B runs)
     p.low_pieces = (res_low && !pieces_off && ((w >> 1) & 3) == 0 && ((uintptr_t)res_low & 15) == 0) ? 1 : 0;
     if (res_low) {
@@ -1162,15 +1182,17 @@ static int launch_wino3(float* y, const float* x, const float* u, const float* i
         if (!pattr_set) {
             hipError_t e = hipFuncSetAttribute((const void*)wino3p_conv_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
             if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wino3p_conv_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)(wino3p_conv_kernel<8, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
             if (e != hipSuccess) { mgf_set_error("conv3x3_winograd3: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return MGF_ELAUNCH; }
             pattr_set = true;
         }
-        const char* pname = rgb ? "wino3p_conv_kernel<8, true>" : "wino3p_conv_kernel<8, false>";
+        const char* pname = masked ? "wino3p_conv_kernel<8, false, true>" : (rgb ? "wino3p_conv_kernel<8, true>" : "wino3p_conv_kernel<8, false>");
         mgf_prof_external_begin((hipStream_t)stream, pname, 2.0 * 9 * cin * (double)cout * h * w * n,
                                 4.0 * ((double)n * cin * h * w + 9.0 * cin * cout + (double)n * (rgb ? rgb_channels : cout) * h * w));
         const dim3 pgrid((unsigned)pblocks), pblk(256);
         hipStream_t pst = (hipStream_t)stream;
-        if (rgb) hipLaunchKernelGGL((wino3p_conv_kernel<8, true>), pgrid, pblk, plds, pst, p);
+        if (masked) hipLaunchKernelGGL((wino3p_conv_kernel<8, false, true>), pgrid, pblk, plds, pst, p);
+        else if (rgb) hipLaunchKernelGGL((wino3p_conv_kernel<8, true>), pgrid, pblk, plds, pst, p);
         else hipLaunchKernelGGL((wino3p_conv_kernel<8, false>), pgrid, pblk, plds, pst, p);
         mgf_prof_external_end((hipStream_t)stream);
         MGF_CHECK_LAUNCH("conv3x3_winograd3(persistent)");
@@ -1200,13 +1222,14 @@ static int launch_wino3(float* y, const float* x, const float* u, const float* i
         attr_set = true;
     }
     // names as rocprofv3 prints the instantiations; algorithmic accounting of the direct form (what the launch replaces)
-    const char* name = rgb ? (shape == 12 ? "wino3_conv_kernel<1, 2, true>" : "wino3_conv_kernel<1, 1, true>")
+    const char* name = masked ? "wino3_conv_kernel<1, 1, false, true>" : rgb ? (shape == 12 ? "wino3_conv_kernel<1, 2, true>" : "wino3_conv_kernel<1, 1, true>")
                            : (shape == 21 ? "wino3_conv_kernel<2, 1, false>" : (shape == 12 ? "wino3_conv_kernel<1, 2, false>" : "wino3_conv_kernel<1, 1, false>"));
     mgf_prof_external_begin((hipStream_t)stream, name, 2.0 * 9 * cin * (double)cout * h * w * n,
                             4.0 * ((double)n * cin * h * w + 9.0 * cin * cout + (double)n * (rgb ? rgb_channels : cout) * h * w));
     const dim3 grid((unsigned)blocks), blk(256);
     hipStream_t st = (hipStream_t)stream;
-    if (rgb && shape == 12) hipLaunchKernelGGL((wino3_conv_kernel<1, 2, true>), grid, blk, lds, st, p);
+    if (masked) hipLaunchKernelGGL((wino3_conv_kernel<1, 1, false, true>), grid, blk, lds, st, p);
+    else if (rgb && shape == 12) hipLaunchKernelGGL((wino3_conv_kernel<1, 2, true>), grid, blk, lds, st, p);
     else if (rgb) hipLaunchKernelGGL((wino3_conv_kernel<1, 1, true>), grid, blk, lds, st, p);
     else if (shape == 21) hipLaunchKernelGGL((wino3_conv_kernel<2, 1, false>), grid, blk, lds, st, p);
     else if (shape == 12) hipLaunchKernelGGL((wino3_conv_kernel<1, 2, false>), grid, blk, lds, st, p);
@@ -1227,6 +1250,18 @@ extern "C" int mgf_conv3x3_winograd3_f32(float* y, const float* x, const float* 
 int mgf_wino3_batch_invariant_f32(float* y, const float* x, const float* u, int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout,
                                   const mgf_epilogue* ep, mgf_stream_t stream) {
     return launch_wino3(y, x, u, nullptr, nullptr, n, cin, h, w, cout, 0, ep, nullptr, nullptr, nullptr, 0, stream, nullptr, 0, 0, true);
+}
+
+// The MDF backward's body adjoints (csrc/mdf.hip): the same batch-invariant launch with the masked epilogue -- y = conv(x) * (mask > 0 ?
+// 1 : slope) on ring `ring` of the frame, 0 outside it; mask has y's layout and is read where the residual would be.
+int mgf_wino3_batch_invariant_masked_f32(float* y, const float* x, const float* u, const float* mask, int32_t n, int32_t c, int32_t h, int32_t w,
+                                         int32_t ring, float slope, mgf_stream_t stream) {
+    MGF_REQUIRE(mask && ring >= 0, MGF_EINVAL, "conv3x3_winograd3(masked): needs a mask map and a ring depth >= 0");
+    mgf_epilogue ep{};
+    ep.residual = mask;
+    ep.act = MGF_ACT_LINEAR;
+    ep.gain = 1.f;
+    return launch_wino3(y, x, u, nullptr, nullptr, n, c, h, w, c, 0, &ep, nullptr, nullptr, nullptr, 0, stream, nullptr, 0, 0, true, true, ring, slope);
 }
 
 extern "C" int mgf_conv3x3_winograd3_slice_f32(float* y, const float* x, const float* u, const float* in_scale, const float* out_scale, int32_t n,

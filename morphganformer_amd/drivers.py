@@ -420,10 +420,12 @@ def morph_pairs(G, pairs, src_dir, dst_raw, dst_morph, landmarks=None, truncatio
 
 def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=None, latent_mean=None, latent_std=None, eps=None,
                    use_graph=True, noise_mode="random", use_mse=True, seed=None, weight_decay=0.0, mode="gradient", latent_space="z",
-                   biometric=None, gamma=1.0, batch=None, pipeline=None, **unused):
+                   biometric=None, gamma=1.0, batch=None, pipeline=None, mdf=None, **unused):
     """B targets through one lockstep GradientProjectionEngine; returns dict(w [B,k,D] (W+: [B,k,num_ws,D]), step [B], loss [B],
     losses [B,steps])."""
     args = args or ProjectionArgs()
+    if mdf is not None:
+        raise _lib.MgfError("project_many(lockstep > 1): the MDF objective runs one target per engine in gradient mode; use lockstep=1")
     if unused or pipeline:                          # (`batch` is literal mode's steps per forward: gradient mode evaluates one candidate per step; `pipeline` is literal mode's too)
         unused = dict(unused, **({"pipeline": pipeline} if pipeline else {}))
         raise TypeError(f"project_many(lockstep=...): unsupported arguments {sorted(unused)}")

@@ -292,10 +292,17 @@ def fold_bn(sd, eps=BN_EPS):
     return layers
 
 
+def adjoint_weights(w):
+    """The adjoint of a 3x3 pad-1 convolution as another one: W~[ci][co][kh][kw] = W[co][ci][2-kh][2-kw] (float64 numpy; transposing and
+    flipping is exact, so its float32 rounding is the transposed rounding of W)."""
+    w = np.asarray(w, dtype=np.float64)
+    return np.ascontiguousarray(w.transpose(1, 0, 2, 3)[:, :, ::-1, ::-1])
+
+
 class _Disc:
     """One discriminator's folded weights on the device, in the layouts of the mdf kernels."""
 
-    def __init__(self, sd, device, idx):
+    def __init__(self, sd, device, idx, differentiable=False):
         self.N = check_state(sd, idx)
         layers = fold_bn(sd)
         t32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=device)
@@ -305,6 +312,8 @@ class _Disc:
         self.body_b = [t32(b) for _, b in body]
         self.body_u = [cv.winograd2_weights(w) for w in self.body_w]
         self.tail_w, self.tail_b = t32(tw.reshape(self.N * 9)), float(np.float32(tb[0]))
+        # backward: the body blocks' adjoints as Winograd weight planes (the head and tail backward kernels read head_w / tail_w flipped)
+        self.body_uadj = [cv.winograd2_weights(t32(adjoint_weights(w))) for w, _ in body] if differentiable else None
         self._packed = None
 
     def packed(self):
@@ -323,9 +332,12 @@ class MDFLoss:
     (mdfloss.py:16-47 for one candidate; `forward` / `__call__` add the reference's batch mean).  The target's taps are computed once
     per target (the reference recomputes them every step)."""
 
-    def __init__(self, Ds, num_scales=8, is_ascending=1, device="cuda"):
+    def __init__(self, Ds, num_scales=8, is_ascending=1, device="cuda", differentiable=False):
         """Ds: a Ds_*.pth path or a list of per-discriminator state dicts (load_discriminators / random_discriminators).
-        num_scales discriminators are used, Ds[0 ..] ascending or Ds[-1 ..] descending (mdfloss.py:24-31)."""
+        num_scales discriminators are used, Ds[0 ..] ascending or Ds[-1 ..] descending (mdfloss.py:24-31).
+        differentiable: also build the backward pass (distance_into(dimg=...), autograd through `forward`, GradientProjectionEngine): the
+        adjoint weights are prepared once and the workspace keeps one discriminator's activations x1, a1, a2, x2 (4 N planes) and x3 per
+        candidate.  Without it memory and launches are those of the literal loop."""
         _lib.lib()
         self.device = torch.device(device)
         if isinstance(Ds, (str, bytes, os.PathLike)):
@@ -335,7 +347,8 @@ class MDFLoss:
             raise _lib.MgfError(f"MDFLoss: num_scales must be 1 .. {self.num_discs} (the file holds {self.num_discs} discriminators)")
         self.num_scales, self.is_ascending = int(num_scales), int(is_ascending)
         self.order = [s if self.is_ascending else self.num_discs - 1 - s for s in range(self.num_scales)]
-        self.nets = [_Disc(Ds[i], self.device, i) for i in self.order]
+        self.differentiable = bool(differentiable)
+        self.nets = [_Disc(Ds[i], self.device, i, self.differentiable) for i in self.order]
         self.cmax = max(d.N for d in self.nets)
         self._hw, self._n = None, 0
         self._tgt = None
@@ -346,7 +359,10 @@ class MDFLoss:
             if h < MIN_SIDE or w < MIN_SIDE:
                 raise _lib.MgfError(f"MDFLoss: images of at least {MIN_SIDE}x{MIN_SIDE} pixels (got {h}x{w}): five valid 3x3 convolutions")
             e = lambda *s, dt=torch.float32: torch.empty(s, dtype=dt, device=self.device)
-            self.frames = [e(n * self.cmax * h * w), e(n * self.cmax * h * w)]
+            self.frames = [e(n * self.cmax * h * w), e(n * self.cmax * h * w)]     # (differentiable: also the two gradient frames)
+            if self.differentiable:                                                # x1, a1, a2, x2 and x3 of the discriminator in flight
+                self.acts = [e(n * self.cmax * h * w) for _ in range(1 + BODY_BLOCKS)]
+                self.x3 = e(n * h * w)
             self.nblk = int(_lib.lib().mgf_mdf_partials(h, w))
             self.part = e(3 * len(self.nets), n, self.nblk, dt=torch.float64)
             self._hw, self._n = (h, w), n
@@ -368,15 +384,18 @@ class MDFLoss:
         _lib.check(_lib.lib().mgf_mdf_body_f32(y.data_ptr(), x.data_ptr(), d.body_u[k].data_ptr(), d.body_b[k].data_ptr(), n, d.N, h, w,
                                                SLOPE, _lib.stream_ptr()), "mdf_body")
 
-    def _features(self, d, img, n, h, w, x1, x2_out, x3_out, tgt=None, part=None):
+    def _features(self, d, img, n, h, w, x1, x2_out, x3_out, tgt=None, part=None, mids=None):
         """head -> 3 body blocks -> tail of one discriminator on img [n,3,h,w].  With tgt = (x1t, x2t, x3t) and part (3 slabs) the taps'
-        partial sums land in part; without, the taps are written to x1 / x2_out / x3_out (the target's frames)."""
+        partial sums land in part; without, the taps are written to x1 / x2_out / x3_out (the target's frames).  mids: frames for a1 and
+        a2 (the backward keeps them) instead of the workspace's ping-pong."""
         L, st = _lib.lib(), _lib.stream_ptr()
         _lib.check(L.mgf_mdf_head_f32(x1.data_ptr(), _lib.ptr(part[0] if part is not None else None), img.data_ptr(), d.head_w.data_ptr(),
                                       d.head_b.data_ptr(), _lib.ptr(tgt[0] if tgt else None), n, d.N, h, w, SLOPE, st), "mdf_head")
         f0, f1 = self.frames
         # ping-pong through the two workspace frames; the target's x1 / x2 land in its own frames
         seq = [x1, f0, f1, x2_out] if x2_out is not None else [x1, f1, f0, f1]
+        if mids is not None:
+            seq = [x1, mids[0], mids[1], x2_out]
         for k in range(BODY_BLOCKS):
             self._body(d, seq[k], seq[k + 1], n, h, w, k)
         x2 = seq[BODY_BLOCKS]
@@ -402,7 +421,24 @@ class MDFLoss:
         for d, (x1t, x2t, x3t) in zip(self.nets, self._tgt):
             self._features(d, img, 1, h, w, x1t, x2t, x3t)
 
-    def _run(self, pred):
+    def _backward(self, i, d, tgt, dimg, n, h, w, scale, accumulate):
+        """dimg (+)= scale * d loss_i / d pred for discriminator position i, from the activations its forward left in self.acts / self.x3
+        (include/mgf.h, "MDF backward"): tail -> three masked body adjoints -> head, through the two gradient frames."""
+        L, st = _lib.lib(), _lib.stream_ptr()
+        A, (g0, g1) = self.acts, self.frames
+        c1, c2, c3 = (float(self.counts[3 * i + t]) for t in range(3))
+        _lib.check(L.mgf_mdf_tail_backward_f32(g0.data_ptr(), A[3].data_ptr(), tgt[1].data_ptr(), self.x3.data_ptr(), tgt[2].data_ptr(),
+                                               d.tail_w.data_ptr(), n, d.N, h, w, RING_X2, 2.0 * scale / c2, 2.0 * scale / c3, SLOPE, st),
+                   "mdf_tail_backward")
+        src, dst = g0, g1
+        for k in reversed(range(BODY_BLOCKS)):           # delta_k = adj_{k+1}(delta_{k+1}) * phi'(a_k) on ring k + 1
+            _lib.check(L.mgf_mdf_body_backward_f32(dst.data_ptr(), src.data_ptr(), d.body_uadj[k].data_ptr(), A[k].data_ptr(), n, d.N, h, w,
+                                                   k + 1, SLOPE, st), "mdf_body_backward")
+            src, dst = dst, src
+        _lib.check(L.mgf_mdf_head_backward_f32(dimg.data_ptr(), src.data_ptr(), A[0].data_ptr(), tgt[0].data_ptr(), d.head_w.data_ptr(), n, d.N,
+                                               h, w, 2.0 * scale / c1, SLOPE, int(accumulate), st), "mdf_head_backward")
+
+    def _run(self, pred, dimg=None, scale=1.0, grad_accumulate=False):
         assert self._tgt is not None, "call set_target first"
         _lib.require_gpu(pred)
         n, c, h, w = pred.shape
@@ -413,7 +449,13 @@ class MDFLoss:
         self._reserve(n, h, w)
         part = self.part_view(n)
         for i, (d, tgt) in enumerate(zip(self.nets, self._tgt)):
-            self._features(d, pred, n, h, w, self.frames[0], None, None, tgt, [part[3 * i + t] for t in range(3)])
+            slabs = [part[3 * i + t] for t in range(3)]
+            if dimg is None:
+                self._features(d, pred, n, h, w, self.frames[0], None, None, tgt, slabs)
+            else:                                        # forward keeping the activations, then this discriminator's backward
+                A = self.acts
+                self._features(d, pred, n, h, w, A[0], A[3], self.x3, tgt, slabs, mids=(A[1], A[2]))
+                self._backward(i, d, tgt, dimg, n, h, w, scale, grad_accumulate or i > 0)
         return part, n
 
     def part_view(self, n):
@@ -421,9 +463,16 @@ class MDFLoss:
         need = 3 * len(self.nets) * n * self.nblk
         return self.part.view(-1)[:need].view(3 * len(self.nets), n, self.nblk)
 
-    def distance_into(self, out, pred, scale=1.0, accumulate=False):
-        """out[i] (+)= scale * loss(pred[i]);  out: float32 [n].  Graph-capturable once a call of this batch size has run (workspace)."""
-        part, n = self._run(pred)
+    def distance_into(self, out, pred, scale=1.0, accumulate=False, dimg=None, grad_accumulate=False):
+        """out[i] (+)= scale * loss(pred[i]);  out: float32 [n].  Graph-capturable once a call of this batch size has run (workspace).
+        dimg (differentiable=True): also dimg[i] (+)= scale * d loss(pred[i]) / d pred[i] (grad_accumulate: +=), each discriminator's
+        backward right behind its own forward; the loss is the same bits as without dimg, a candidate's gradient the same bits in any batch."""
+        if dimg is not None:
+            if not self.differentiable:
+                raise _lib.MgfError("MDFLoss.distance_into(dimg=...): build the loss with MDFLoss(..., differentiable=True) for its backward pass")
+            if tuple(dimg.shape) != tuple(pred.shape) or dimg.dtype != torch.float32 or not dimg.is_contiguous():
+                raise _lib.MgfError(f"MDFLoss: dimg must be a contiguous float32 tensor shaped like pred {tuple(pred.shape)}")
+        part, n = self._run(pred, dimg, float(scale), grad_accumulate)
         _lib.check(_lib.lib().mgf_mdf_finish_f32(out.data_ptr(), part.data_ptr(), part.shape[0], self.nblk, self.counts, n, float(scale),
                                                  int(accumulate), _lib.stream_ptr()), "mdf_finish")
         return out
@@ -437,17 +486,41 @@ class MDFLoss:
         return torch.from_numpy((sums / counts[:, None]).T.reshape(n, len(self.nets), 3).copy())
 
     def forward(self, x, y):
-        """The reference's call: mean over the batch of loss(x[i], y[i]) (mdfloss.py:16-47; x = the target(s), y = the candidates)."""
+        """The reference's call: mean over the batch of loss(x[i], y[i]) (mdfloss.py:16-47; x = the target(s), y = the candidates).
+        differentiable=True and y.requires_grad: the result is connected to y (the gradient is computed here, eagerly, and scaled by
+        grad_output / n in backward) -- the reference's `p_loss = criterion(imgs, img_gen); p_loss.backward()`.  Otherwise detached."""
+        if self.differentiable and y.requires_grad and torch.is_grad_enabled():
+            return _MDFFunction.apply(y, self, x)
+        return self._forward_detached(x, y)[0]
+
+    def _forward_detached(self, x, y, want_grad=False):
         y = y.detach().float().contiguous()
+        g = torch.empty_like(y) if want_grad else None
         out = torch.zeros(y.shape[0], dtype=torch.float32, device=y.device)
         if x.shape[0] == 1:
             self.set_target(x)
-            self.distance_into(out, y)
+            self.distance_into(out, y, dimg=g)
         else:
             assert x.shape[0] == y.shape[0], "x and y pair up"
             for i in range(x.shape[0]):
                 self.set_target(x[i:i + 1])
-                self.distance_into(out[i:i + 1], y[i:i + 1])
-        return out.mean()
+                self.distance_into(out[i:i + 1], y[i:i + 1], dimg=None if g is None else g[i:i + 1])
+        return out.mean(), g
 
     __call__ = forward
+
+
+class _MDFFunction(torch.autograd.Function):
+    """MDFLoss.forward with a gradient for the candidates: computed eagerly by the HIP backward, scaled in backward."""
+
+    @staticmethod
+    def forward(ctx, y, crit, x):
+        loss, g = crit._forward_detached(x.detach(), y, want_grad=True)
+        ctx.save_for_backward(g)
+        ctx.n, ctx.dtype = int(y.shape[0]), y.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g, = ctx.saved_tensors
+        return (g * (grad_out / ctx.n)).to(ctx.dtype), None, None

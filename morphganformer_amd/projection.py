@@ -802,9 +802,12 @@ class GradientProjectionEngine(ProjectionEngine):
         reference has no such driver (its "W+" averages 18 copies of z, projection_example_v2_percept.py:133-162); the oracle is torch autograd
         + Adam on ws through the CPU restatement (tests/test_hip_gradient.py)."""
         from .grad import GeneratorGrad
-        if mdf is not None:
-            raise _lib.MgfError("GradientProjectionEngine: the MDF objective has no backward pass -- the reference's MDF drivers "
-                                "(1024_example_mdfloss.py, projection_example_v1_mdfloss*.py) are literal loops: use ProjectionEngine(mdf=...)")
+        if mdf is not None and not getattr(mdf, "differentiable", False):
+            raise _lib.MgfError("GradientProjectionEngine: this MDF loss was built without its backward pass -- build it with "
+                                "mdf.MDFLoss(..., differentiable=True) for gradient mode (ProjectionEngine(mdf=...), the literal loop, takes either)")
+        if mdf is not None and int(target.shape[0]) > 1:
+            raise _lib.MgfError("GradientProjectionEngine: the MDF objective runs with one target per engine (lockstep targets would need "
+                                "per-target discriminator activations); project the targets one after the other")
         assert latent_space in ("z", "w+"), latent_space
         self.latent_space = latent_space
         ls = (G.cfg.k, G.cfg.num_ws, G.cfg.w_dim) if latent_space == "w+" else (G.cfg.k, G.cfg.z_dim)
@@ -813,7 +816,7 @@ class GradientProjectionEngine(ProjectionEngine):
             super().__init__(G, target, latent_mean, latent_std, args, percept=percept, use_mse=use_mse, lm_target=lm_target,
                              lm_steps=lm_steps, lm_valid=lm_valid, eps=eps, noise_mode=noise_mode, seed=seed, use_graph=use_graph, batch=1,
                              landmark_fn=landmark_fn, biometric=biometric, gamma=gamma, wing_kind=wing_kind,
-                             landmark_model=landmark_model, pipeline=False, latent_shape=ls)
+                             landmark_model=landmark_model, pipeline=False, latent_shape=ls, mdf=mdf)
             self.lm_tables = [self.lm_steps] if self.use_wing else None
         else:
             self._init_multi(G, target, latent_mean, latent_std, args, percept, use_mse, lm_target, lm_steps, lm_valid, eps, noise_mode,
@@ -888,6 +891,7 @@ class GradientProjectionEngine(ProjectionEngine):
             biometric.set_target(self.target)                 # one embedding per target
         self.use_graph, self.graph, self.pipeline, self.keep_images = use_graph, None, False, 0
         self.pool_factor = 1
+        self.mdf = None                                       # (refused with B > 1 targets, see __init__)
 
     def _state(self):
         return super()._state() + (self.latent_in, self.exp_avg, self.exp_avg_sq, self.adam_t)
@@ -918,11 +922,14 @@ class GradientProjectionEngine(ProjectionEngine):
         if self.biometric is not None:      # rides in the p_loss slot, like the literal loop
             self.biometric.distance_into(self.p_loss, img, scale=self.gamma, accumulate=self.percept is not None)
             self.biometric.grad_into(self.dimg, scale=self.gamma, accumulate=True)
+        if self.mdf is not None:            # p_loss (+)= MDF, dimg += d MDF / d img (1024_example_mdfloss.py:165 without the detach)
+            self.mdf.distance_into(self.p_loss, img, accumulate=self.percept is not None or self.biometric is not None, dimg=self.dimg,
+                                   grad_accumulate=True)
         if self.use_mse:
             _lib.check(L.mgf_mse_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, per, tstride, 1.0, 0,
                                      self.scratch.data_ptr(), st), "mse")
         dz = self.gg.backward_ws(self.dimg) if self.latent_space == "w+" else self.gg.backward(self.dimg)
-        has_p = self.percept is not None or self.biometric is not None
+        has_p = self.percept is not None or self.biometric is not None or self.mdf is not None
         for j in range(B):                   # per-target optimizer step, Wing term and best-of bookkeeping (tiny launches)
             ctr = self.step_ctr[j:]
             valid = None if self.valid is None else (self.valid[j] if B > 1 else self.valid)

@@ -17,7 +17,7 @@ for line in open(one if os.path.exists(one) else os.path.join(ROOT, "profiles", 
         continue
     name, calls, total_ms = short(m.group(1)), int(m.group(2)), float(m.group(3))
     rows[name] = [calls, total_ms]
-    if name.startswith("wino3p_conv_kernel<8, false>"):
+    if name.startswith(("wino3p_conv_kernel<8, false>", "wino3p_conv_kernel<8, false, false>")):
         iters = calls                                    # one launch per iteration
 mf = json.load(open(os.path.join(ROOT, "profiles", f"{tag}_pmc_mfma.json")))
 tr = json.load(open(os.path.join(ROOT, "profiles", f"{tag}_pmc_traffic.json")))
