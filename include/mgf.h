@@ -385,6 +385,22 @@ int mgf_mse_f32(float* out, const float* a, const float* b, int32_t n, int64_t n
 int64_t mgf_dssim_scratch_bytes(int32_t n, int32_t c, int32_t h, int32_t w);
 int mgf_dssim_u8_f32(float* out, const float* img, const float* target, int32_t n, int32_t c, int32_t h, int32_t w, int64_t t_batch_stride,
                      float data_range, float scale, int32_t accumulate, void* scratch, mgf_stream_t stream);
+/* dssim, continuous (gradient mode's pixel term): the same function -- same window, covariance, constants, positions and means -- on the
+ *        UNQUANTISED pixels p = 127.5 img + 127.5, q = 127.5 target + 127.5 (no rint, no clip: the quantisation of mgf_dssim_u8_f32 has gradient
+ *        zero almost everywhere; img may leave [-1, 1]).  On images that lie on the uint8 grid the two agree to float32 rounding.  float32 loads,
+ *        float64 arithmetic in a fixed order, no atomics (bit-reproducible); identical images give exactly 0.  Same arguments, same scratch
+ *        (mgf_dssim_scratch_bytes) as above.
+ *   mgf_dssim_f32:       out[i] (+)= scale * dssim(img[i], target)
+ *   mgf_dssim_grad_f32:  dimg[i] (+)= scale * d dssim(img[i], target) / d img[i]  (dimg [n,c,h,w]; accumulate_dimg != 0 adds to what is there), and,
+ *                        when out is not NULL, out[i] (+)= dssim(img[i], target) -- UNSCALED, the bits of mgf_dssim_f32(scale = 1) -- from the same
+ *                        pass.  The gradient is three adjoint 7x7 box filters of per-position maps, with S = A1 A2 / (B1 B2) as in skimage:
+ *                        d dssim / d img[r,c] = -(127.5 / (2 c positions 49)) (sum ga + 2 p[r,c] sum gb + q[r,c] sum gc) over the windows that
+ *                        hold (r,c), ga = dS/dux (through vx, vxy), gb = dS/duxx = -S cov / B2, gc = dS/duxy = 2 cov A1 / (B1 B2). */
+int mgf_dssim_f32(float* out, const float* img, const float* target, int32_t n, int32_t c, int32_t h, int32_t w, int64_t t_batch_stride,
+                  float data_range, float scale, int32_t accumulate, void* scratch, mgf_stream_t stream);
+int mgf_dssim_grad_f32(float* dimg, float* out, const float* img, const float* target, int32_t n, int32_t c, int32_t h, int32_t w,
+                       int64_t t_batch_stride, float data_range, float scale, int32_t accumulate_dimg, int32_t accumulate_out, void* scratch,
+                       mgf_stream_t stream);
 /* The LBP matching distance of 1024_example_LBP_percept.py:34-58,162-166 per candidate, in three steps (csrc/lbp.hip):
  *   lbp_gray224:  gray [n,224,224] u8 = cv2.resize(cv2.cvtColor(to_pil(img), COLOR_BGR2GRAY), (224, 224)) of img [n,3,h,w] in [-1, 1]: misc.to_pil's
  *                 rint quantisation (misc.py:115-116), OpenCV's 8-bit gray weights (1868, 9617, 4899, >> 14) with the FIRST channel in the blue

@@ -43,7 +43,8 @@ def _loop_arguments(p):
     p.add_argument("--pixel-term", choices=["mse", "psnr", "dssim", "lbp"], default="mse",
                    help="psnr = the pixel term of 1024_example_PSNR.py (10 log10(255^2 / MSE), minimised like the script does, and -- see --psnr-layout -- "
                         "with the script's element order; use with --no-lpips); "
-                        "dssim = (1 - SSIM) / 2 of the uint8 images (1024_example_SSIM.py's `dssim`); lbp = the LBP matching distance of "
+                        "dssim = (1 - SSIM) / 2 (1024_example_SSIM.py's `dssim`): of the uint8 images in literal mode, of the unquantised pixels with --mode gradient "
+                        "(the quantisation has no gradient; the two agree on uint8-grid images); lbp = the LBP matching distance of "
                         "1024_example_LBP_percept.py, the whole objective of that script (use with --no-lpips; literal mode)")
     p.add_argument("--psnr-layout", choices=["script", "aligned"], default="script",
                    help="script = 1024_example_PSNR.py:150-158 as written: the candidate's C-H-W stream against the target's H-W-C stream (different pixels "

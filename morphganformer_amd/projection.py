@@ -59,7 +59,9 @@ class ProjectionArgs:
     # function defines on corresponding pixels (a deliberate deviation from the script; ranks candidates by their MSE)
     # "dssim": `dssim` of 1024_example_SSIM.py:115-117 (= lpips/__init__.py:54-55), (1 - SSIM) / 2 with skimage's defaults, on the uint8
     # images (the generated image as the drivers save it, misc.to_pil) -- the function as defined; the script's own call site (:158) passes
-    # flattened float arrays, which compare_ssim rejects
+    # flattened float arrays, which compare_ssim rejects.  That is the literal loop (mgf_dssim_u8_f32).  Gradient mode descends the SAME function
+    # on the unquantised pixels 127.5 x + 127.5 (mgf_dssim_grad_f32: the rint / clip has gradient zero almost everywhere); the two agree to float32
+    # rounding on images that lie on the uint8 grid
     # "lbp": the matching distance of 1024_example_LBP_percept.py:34-58,162-166 -- 1 - cos(LBP(24, 3, 'uniform') code map of the saved image at
     # 224 x 224, the target file's code map) in float64 -- in place of every other term (the script scores nothing else); needs
     # ProjectionEngine(lbp_target=lbp.target_feature(file pixels))
@@ -777,8 +779,8 @@ class GradientProjectionEngine(ProjectionEngine):
     """Gradient mode: the same loop with the loss back-propagated into the latent.
 
         latent_n = latent_in + eps_i * sigma_i;  img = G(latent_n)
-        total = percept_weight * LPIPS + lamda * Wing + beta * MSE [+ gamma * embedding MSE]     (Wing's landmarks come from a
-                                                                                                 detector: no gradient)
+        total = percept_weight * LPIPS + lamda * Wing + beta * (MSE | DSSIM) [+ gamma * embedding MSE]     (Wing's landmarks come from a
+                                                                                                           detector: no gradient)
         latent_in <- Adam(lr_i = get_lr(i / steps)).step(d total / d latent_in);  keep (latent_n, i) if total < min_loss
 
     i.e. the drivers' loop (...sqz_MSE.py:143-189) with the `.cpu().detach().numpy()` at :158 removed.  One candidate per target
@@ -808,6 +810,15 @@ class GradientProjectionEngine(ProjectionEngine):
         if mdf is not None and int(target.shape[0]) > 1:
             raise _lib.MgfError("GradientProjectionEngine: the MDF objective runs with one target per engine (lockstep targets would need "
                                 "per-target discriminator activations); project the targets one after the other")
+        a = args or ProjectionArgs()
+        if a.latent_copies != 1:
+            raise _lib.MgfError("GradientProjectionEngine: latent_copies is the literal-mode v2 driver's averaged latent (projection_example_v2_percept.py); "
+                                "gradient mode optimises one latent")
+        if a.pixel_term not in ("mse", "dssim") or a.pool_above:
+            raise _lib.MgfError("GradientProjectionEngine: pixel_term='psnr', pixel_term='lbp' and pool_above are literal-mode objectives with no backward pass "
+                                "here: PSNR as the script minimises it descends towards a LARGER error, the LBP distance is a histogram of integer codes "
+                                "(its gradient is zero almost everywhere), and pool_above is the v1 driver's block mean in front of the losses, which has "
+                                "no adjoint kernel; gradient mode descends Wing / LPIPS / MSE / DSSIM / biometric / MDF")
         assert latent_space in ("z", "w+"), latent_space
         self.latent_space = latent_space
         ls = (G.cfg.k, G.cfg.num_ws, G.cfg.w_dim) if latent_space == "w+" else (G.cfg.k, G.cfg.z_dim)
@@ -824,12 +835,7 @@ class GradientProjectionEngine(ProjectionEngine):
             assert landmark_fn is None and landmark_model is None, "landmark detectors are wired for one target per engine"
         self.targets = B
         a, dev = self.args, self.device
-        if a.latent_copies != 1:
-            raise _lib.MgfError("GradientProjectionEngine: latent_copies is the literal-mode v2 driver's averaged latent (projection_example_v2_percept.py); "
-                                "gradient mode optimises one latent")
-        if a.pixel_term != "mse" or a.pool_above:
-            raise _lib.MgfError("GradientProjectionEngine: pixel_term='psnr' / 'dssim' / 'lbp' / pool_above are literal-mode objectives (the PSNR / v1 drivers "
-                                "sever the gradient like every other driver; only the Wing / LPIPS / MSE / biometric terms have backward passes)")
+        self.use_dssim = self.use_mse and a.pixel_term == "dssim"
         if biometric is not None and hasattr(biometric.embedder, "keep_activations"):
             biometric.embedder.keep_activations = True          # (the FaceNet embedder re-uses its buffers block after block otherwise)
         self.gg = GeneratorGrad(G)
@@ -892,6 +898,12 @@ class GradientProjectionEngine(ProjectionEngine):
         self.use_graph, self.graph, self.pipeline, self.keep_images = use_graph, None, False, 0
         self.pool_factor = 1
         self.mdf = None                                       # (refused with B > 1 targets, see __init__)
+        if a.pixel_term == "dssim" and use_mse:
+            c, h, w = self.target.shape[-3:]
+            nbytes = int(_lib.lib().mgf_dssim_scratch_bytes(B, c, h, w))
+            if nbytes <= 0:
+                raise _lib.MgfError(f"projection: pixel_term='dssim' needs images of at least 7x7 pixels, got {h}x{w}")
+            self.dssim_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
 
     def _state(self):
         return super()._state() + (self.latent_in, self.exp_avg, self.exp_avg_sq, self.adam_t)
@@ -909,7 +921,11 @@ class GradientProjectionEngine(ProjectionEngine):
             self._landmarks(img)                                                  # before Adam: a "no face" step must not move the latent
         per = img.numel() // B
         tstride = per if B > 1 else 0
-        if self.use_mse:
+        if self.use_dssim:                   # dimg = beta * d dssim / d img and the unscaled value, one pass (the continuous DSSIM, see ProjectionArgs)
+            c, h, w = img.shape[1:]
+            _lib.check(L.mgf_dssim_grad_f32(self.dimg.data_ptr(), self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, c, h, w, tstride,
+                                            255.0, float(a.beta), 0, 0, self.dssim_scratch.data_ptr(), st), "dssim_grad")
+        elif self.use_mse:
             _lib.check(L.mgf_mse_grad_f32(self.dimg.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, per, tstride, float(a.beta), 0,
                                           st), "mse_grad")
         else:
@@ -925,7 +941,7 @@ class GradientProjectionEngine(ProjectionEngine):
         if self.mdf is not None:            # p_loss (+)= MDF, dimg += d MDF / d img (1024_example_mdfloss.py:165 without the detach)
             self.mdf.distance_into(self.p_loss, img, accumulate=self.percept is not None or self.biometric is not None, dimg=self.dimg,
                                    grad_accumulate=True)
-        if self.use_mse:
+        if self.use_mse and not self.use_dssim:
             _lib.check(L.mgf_mse_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, per, tstride, 1.0, 0,
                                      self.scratch.data_ptr(), st), "mse")
         dz = self.gg.backward_ws(self.dimg) if self.latent_space == "w+" else self.gg.backward(self.dimg)
