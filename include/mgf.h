@@ -694,6 +694,27 @@ int mgf_linear_bwd_f32(float* dx, const float* dy, const float* w, int32_t n, in
 int mgf_resize_bilinear_bwd_f32(float* dx, const float* dy, int32_t nc, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
                                 mgf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Depthwise convolutions of the MobileFaceNet embedder (backbones/mobilefacenet.py; csrc/depthwise.hip): what
+ * `Conv2d(c, c, k, groups=c, stride, padding, bias=False)` -> BatchNorm2d -> [PReLU(c)] computes in eval mode (ConvBlock :16-26 and
+ * LinearBlock :29-38 with groups == channels: the middle step of DepthWise :41-60, layers[1] :94, the 7x7 of GDC :75-85).
+ *   y[n,c,oy,ox] = prelu_c( scale[c] * sum_{kh,kw} w[c][kh][kw] * x[n,c, stride oy + kh - pad, stride ox + kw - pad] + shift[c] )
+ * NCHW float32, zero padding, out = (in + 2 pad - k) / stride + 1 (floor); scale / shift / slope may each be NULL (1 / 0 / no activation).
+ * Built geometries: 3x3 pad 1 at stride 1 and 2, 7x7 pad 0 at stride 1, on any n, c, in_h, in_w with a non-empty output; anything else
+ * is MGF_EINVAL.  Streaming VALU kernels, fixed summation order, no atomics: a sample's bits do not depend on the batch. */
+int mgf_dwconv_f32(float* y, const float* x, const float* w, const float* scale, const float* shift, const float* slope, int32_t n,
+                   int32_t c, int32_t in_h, int32_t in_w, int32_t kh, int32_t kw, int32_t stride, int32_t pad, mgf_stream_t stream);
+/* Its data gradient (what autograd runs through the same modules, mobilefacenet.py:16-38): dy [n,c,out_h,out_w] is the gradient at the
+ * layer's OUTPUT (behind BatchNorm and PReLU), dx [n,c,in_h,in_w] the gradient at its input; in_h / in_w are given because a stride-2
+ * layer maps two input sizes to one output size.
+ *   dx = m_in * scale[c] * conv_adjoint( m_out * dy ),   m_out = (y > 0 ? 1 : slope[c]),   m_in = (x_act > 0 ? 1 : x_slope[c])
+ * y [n,c,out_h,out_w] is the layer's stored post-activation output (with slope; both NULL = no PReLU behind the layer); x_act
+ * [n,c,in_h,in_w] is the stored post-activation map the layer READ and x_slope the slopes of the PReLU that made it (both NULL = stop at
+ * the layer's input).  Reading the masks off post-activations needs positive slopes (sign(output) = sign(input)), as mgf_prelu_bwd_f32. */
+int mgf_dwconv_bwd_data_f32(float* dx, const float* dy, const float* w, const float* scale, const float* y, const float* slope,
+                            const float* x_act, const float* x_slope, int32_t n, int32_t c, int32_t in_h, int32_t in_w, int32_t kh,
+                            int32_t kw, int32_t stride, int32_t pad, mgf_stream_t stream);
+
 /* Landmark-Delaunay warp post-process (1024_warp_morphs.py:78-113,163-210): per triangle of the mesh the script pastes
  * cv2.warpAffine(patch, INTER_LINEAR, BORDER_REFLECT_101) through a cv2.fillConvexPoly mask, later triangles over earlier ones.
  *   label [h,w] int32:  the index of the triangle that wrote each pixel LAST, -1 = none (drivers.warp_plan rasterises OpenCV's polygon fill

@@ -76,12 +76,13 @@ def _loop_arguments(p):
                    help="literal = the loop as the reference executes it (best-of-N noisy sampling); gradient = back-propagate the loss "
                         "into the latent and let Adam move it")
     p.add_argument("--seed", type=int, default=None)
-    p.add_argument("--biometric", type=str, default="none", choices=["none", "facenet", "iresnet18", "iresnet34", "iresnet50", "iresnet100"],
+    p.add_argument("--biometric", type=str, default="none", choices=["none", "facenet", "iresnet18", "iresnet34", "iresnet50", "iresnet100", "mobilefacenet"],
                    help="add gamma * MSE(embed(img), embed(target)): facenet = InceptionResnetV1 on the un-resized image, the term "
-                        "1024_example_FaceNet_percept.py:147-158 scores with (alone: --no-lpips --no-mse); iresnetNN = the vendored ArcFace network")
+                        "1024_example_FaceNet_percept.py:147-158 scores with (alone: --no-lpips --no-mse); iresnetNN = the vendored ArcFace network; "
+                        "mobilefacenet = the vendored MobileFaceNet (same 112x112 -> 512-d contract, ~0.45 GFLOP per image)")
     p.add_argument("--gamma", type=float, default=1.0, help="coefficient of the biometric term")
     p.add_argument("--biometric-weights", type=str, default=None, metavar="STATE_DICT",
-                   help="the embedder's state dict (.pth / .npz; facenet_pytorch's vggface2 weights, an insightface iresnet checkpoint) -- what the "
+                   help="the embedder's state dict (.pth / .npz; facenet_pytorch's vggface2 weights, an insightface iresnet / mobilefacenet checkpoint) -- what the "
                         "reference fetches by name; required with --biometric unless --biometric-random")
     p.add_argument("--biometric-random", action="store_true", help="seeded random embedder weights (smoke runs only)")
     p.add_argument("--no-mse", action="store_true", help="drop the MSE term (beta * MSE)")

@@ -259,15 +259,19 @@ class BiometricLoss:
     def __init__(self, embedder="iresnet50", **kw):
         """embedder: an embedder object (IResNetEmbedder, facenet.InceptionResnetV1Embedder) or a name -- "facenet": the network the
         driver scores with, on the un-resized image (1024_example_FaceNet_percept.py:30-32,147-158); "iresnet18/34/50/100": the vendored
-        ArcFace network on a 112x112 resize (backbones/iresnet.py).  kw (state=, n=, device=, seed=) go to the embedder's constructor."""
+        ArcFace network on a 112x112 resize (backbones/iresnet.py); "mobilefacenet": the vendored MobileFaceNet, same contract at ~0.45 GFLOP
+        per image (backbones/mobilefacenet.py).  kw (state=, n=, device=, seed=) go to the embedder's constructor."""
         if isinstance(embedder, str):
             if embedder == "facenet":
                 from .facenet import InceptionResnetV1Embedder
                 embedder = InceptionResnetV1Embedder(**kw)
+            elif embedder == "mobilefacenet":
+                from .mobilefacenet import MobileFaceNetEmbedder
+                embedder = MobileFaceNetEmbedder(**kw)
             elif embedder.startswith("iresnet"):
                 embedder = IResNetEmbedder(depth=int(embedder[len("iresnet"):]), **kw)
             else:
-                raise ValueError(f"unknown embedder {embedder!r} (facenet, iresnet18/34/50/100)")
+                raise ValueError(f"unknown embedder {embedder!r} (facenet, iresnet18/34/50/100, mobilefacenet)")
         self.embedder = embedder
         self._target = None
         self._target_stride = 0
