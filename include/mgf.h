@@ -736,6 +736,34 @@ int mgf_cv_warp_triangles_f32(float* out, const float* src, const int32_t* label
 int mgf_adam_step_f32(float* param, float* exp_avg, float* exp_avg_sq, int32_t* adam_t, const float* grad, const float* lr_table,
                       const int32_t* step, const int32_t* valid, int64_t numel, int32_t steps_total, float beta1, float beta2, float eps,
                       float weight_decay, mgf_stream_t stream);
+/* The same step, expression for expression (bit-identical on a tensor both accept), on as many workgroups as numel needs -- the
+ * per-layer noise maps of gradient mode total 2.8 M floats at 1024^2.  *adam_t is advanced by a launch of its own behind the update. */
+int mgf_adam_elementwise_f32(float* param, float* exp_avg, float* exp_avg_sq, int32_t* adam_t, const float* grad, const float* lr_table,
+                             const int32_t* step, const int32_t* valid, int64_t numel, int32_t steps_total, float beta1, float beta2,
+                             float eps, float weight_decay, mgf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Noise-map optimisation (gradient mode): the generator's per-layer noise inputs as parameters next to the latent, with the
+ * regulariser and the normalisation the drivers still carry (1024_example_wing_loss_perceptual_sqz_MSE.py:32-60).  float32 in and out,
+ * float64 accumulation, fixed summation order, no atomics; scratch is the caller's (8-byte aligned, sizes from the *_scratch_bytes queries).
+ *
+ * noise_grad:  dnoise[p] (+)= strength[0] * sum_c dpre[c, p] for a layer's pre-activation gradient dpre [c, hw] (y = lrelu(conv + strength
+ *              * noise + bias)); channels in index order (maps too small to fill the chip: contiguous channel slices, added in index order).
+ * noise_regularize:  value (+)= scale * reg(x) for one square map of side `side` (a power of two):  at sides side, side/2, ... down to the
+ *              first side <= 8,  mean(x * roll(x, 1, cols))^2 + mean(x * roll(x, 1, rows))^2  (the rolls wrap), 2 x 2 block means between
+ *              the levels.
+ * noise_regularize_grad:  dx (+)= scale * d reg / dx -- per level 2A/N (left + right neighbour) + 2B/N (upper + lower), carried down through
+ *              the block mean's adjoint -- and, when `value` is given, value (+)= scale * reg from the same pass.
+ * noise_normalize:  x <- (x - mean(x)) / std(x) in place, std unbiased (N - 1) like torch's default; with `step` given nothing happens when
+ *              *step >= steps_total or valid[*step] == 0 (valid may be NULL). */
+int mgf_noise_grad_f32(float* dnoise, const float* dpre, const float* strength, int32_t c, int64_t hw, int32_t accumulate, mgf_stream_t stream);
+int64_t mgf_noise_regularize_scratch_bytes(int32_t side);
+int mgf_noise_regularize_f32(float* value, const float* x, int32_t side, float scale, int32_t accumulate, void* scratch, mgf_stream_t stream);
+int mgf_noise_regularize_grad_f32(float* dx, float* value, const float* x, int32_t side, float scale, int32_t accumulate_dx,
+                                  int32_t accumulate_value, void* scratch, mgf_stream_t stream);
+int64_t mgf_noise_normalize_scratch_bytes(void);
+int mgf_noise_normalize_f32(float* x, int64_t numel, const int32_t* step, const int32_t* valid, int32_t steps_total, void* scratch,
+                            mgf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * MDF objective (mdfloss.py:16-47 over the SinGAN WDiscriminators of SinGAN/models.py:7-35; csrc/mdf.hip): per discriminator five

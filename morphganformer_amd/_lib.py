@@ -178,6 +178,13 @@ _SIGS = {
     "mgf_cv_warp_triangle_bytes": (i64, []),
     "mgf_cv_warp_triangles_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
     "mgf_adam_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, vp]),
+    "mgf_adam_elementwise_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, vp]),
+    "mgf_noise_grad_f32": (C.c_int, [vp, vp, vp, i32, i64, i32, vp]),
+    "mgf_noise_regularize_scratch_bytes": (i64, [i32]),
+    "mgf_noise_regularize_f32": (C.c_int, [vp, vp, i32, f32, i32, vp, vp]),
+    "mgf_noise_regularize_grad_f32": (C.c_int, [vp, vp, vp, i32, f32, i32, i32, vp, vp]),
+    "mgf_noise_normalize_scratch_bytes": (i64, []),
+    "mgf_noise_normalize_f32": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
     "mgf_mapping_bwd_scratch_floats": (i64, [i32, i32, i32]),
     "mgf_mapping_backward": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "mgf_mapping_forward_save": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -35,7 +35,13 @@ def _loop_arguments(p):
     p.add_argument("--noise_ramp", type=float, default=0.75)
     p.add_argument("--ratio", type=float, default=1.0)
     p.add_argument("--truncation_psi", type=float, default=0.7)
-    p.add_argument("--noise_regularize", type=float, default=1e5)       # accepted and unused, like the reference
+    p.add_argument("--noise_regularize", type=float, default=1e5,
+                   help="weight of the noise regulariser (…sqz_MSE.py:32-52,243); read with --optimize-noise, accepted and unused otherwise, like the reference")
+    p.add_argument("--optimize-noise", action="store_true",
+                   help="with --mode gradient (project): also descend the generator's per-layer noise maps (Adam + noise_normalize_, "
+                        "--noise_regularize times the regulariser in the total); the .mat gains the best step's maps beside 'w'")
+    p.add_argument("--noise-init", choices=["randn", "const"], default="randn",
+                   help="--optimize-noise: start the maps from seeded N(0, 1) draws or from every layer's noise_const")
     p.add_argument("--w_plus", action="store_true",
                    help="with --mode gradient: optimise the per-layer latent W+ [k, num_ws, D] instead of z (the reference accepts the flag "
                         "and never reads it; in literal mode it stays unused here too)")
@@ -243,7 +249,7 @@ def main(argv=None):
     args = ProjectionArgs(step=a.step, lamda=a.lamda, beta=a.beta, lr=a.lr, lr_rampup=a.lr_rampup, lr_rampdown=a.lr_rampdown,
                           noise=a.noise, noise_ramp=a.noise_ramp, truncation_psi=a.truncation_psi, n_mean_latent=a.n_mean_latent,
                           ratio=a.ratio, percept_weight=a.percept_weight, pixel_term=a.pixel_term, psnr_layout=a.psnr_layout, pool_above=a.pool_above,
-                          latent_copies=a.latent_copies, min_loss_init=a.min_loss_init)
+                          latent_copies=a.latent_copies, min_loss_init=a.min_loss_init, noise_regularize=a.noise_regularize)
     percept = None
     if not a.no_lpips:
         if a.lpips_backbone is None and not a.lpips_random_backbone:
@@ -280,6 +286,8 @@ def main(argv=None):
         raise SystemExit(f"{a.cmd}: every term of the objective is switched off")
     if a.pixel_term == "lbp" and (a.cmd != "project" or a.mode != "literal"):
         raise SystemExit("--pixel-term lbp is the objective of the single-image literal loop (project --mode literal)")
+    if a.optimize_noise and (a.cmd != "project" or a.mode != "gradient"):
+        raise SystemExit("--optimize-noise is for project --mode gradient (one target; the literal loop never back-propagates)")
     space = "w+" if (a.w_plus and a.mode == "gradient") else "z"
     if a.cmd == "morph-pairs":
         # one process per GPU under `python -m torch.distributed.run --nproc-per-node N -m morphganformer_amd.cli morph-pairs ...`: the
@@ -320,7 +328,7 @@ def main(argv=None):
     res = drivers.project_image(G, target, lm_t, lm_s, args=args, percept=percept, batch=a.batch, seed=a.seed,
                                 out_prefix=os.path.join(a.path_to_gen, stem), mode=a.mode, path_to_gen=a.path_to_gen,
                                 keep_images=a.keep_images, latent_space=space, biometric=biometric, gamma=a.gamma, use_mse=not a.no_mse, pipeline=None if a.pipeline < 0 else (bool(a.pipeline) and a.mode == "literal"),
-                                lbp_target=lbp_target, mdf=mdf)
+                                lbp_target=lbp_target, mdf=mdf, optimize_noise=a.optimize_noise, noise_init=a.noise_init)
     print(f"best step {res['step']}  loss {res['loss']:.6f}")
     return 0
 

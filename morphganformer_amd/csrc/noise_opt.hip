@@ -1,0 +1,376 @@
+// Noise-map optimisation of gradient mode: the per-layer noise inputs as parameters next to the latent.
+//   mgf_noise_grad_f32             dnoise[p] (+)= strength * sum_c dpre[c, p]                (the layer's pre-activation gradient, channel sum)
+//   mgf_noise_regularize(_grad)_f32  noise_regularize of the drivers (1024_example_wing_loss_perceptual_sqz_MSE.py:32-52) and its gradient
+//   mgf_noise_normalize_f32        noise_normalize_ (:55-60): x <- (x - mean) / std, std unbiased
+//   mgf_adam_elementwise_f32       mgf_adam_step_f32's arithmetic on any number of workgroups
+// float32 in and out, float64 accumulation, fixed summation order (block partials in caller scratch, folded by a fixed tree), no atomics.
+#include "mgf_common.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int NO_PARTS = 256;          // at most this many block partials per reduction (one per thread of the block that folds them)
+
+// Sum over the 256 threads of a block in a fixed order (wave butterflies, then the four waves in index order); every thread gets the result.
+__device__ __forceinline__ double block_sum_256(double v, double* sh) {
+    v = wave_sum(v);
+    __syncthreads();                    // (sh may still be read from the previous call)
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+// ---------------------------------------------------------------------------------------------- d noise
+// block = PQ pixel groups x S channel slices (PQ * S = 256); a thread sums its slice's channels in index order for V consecutive pixels,
+// the slices are then added in index order.  S > 1 only where the map is too small to fill the chip with one thread per pixel group.
+template <int V, int S>
+__global__ __launch_bounds__(256) void noise_grad_kernel(float* __restrict__ dnoise, const float* __restrict__ dpre, const float* __restrict__ strength,
+                                                         int c, int64_t hw, int accumulate) {
+    constexpr int PQ = 256 / S;
+    __shared__ double part[S > 1 ? S : 1][PQ][V];
+    const int pq = threadIdx.x % PQ, sl = threadIdx.x / PQ;
+    const int64_t groups = hw / V;
+    const int64_t q = (int64_t)blockIdx.x * PQ + pq;
+    const bool live = q < groups;
+    const int per = (c + S - 1) / S;
+    const int c0 = sl * per, c1 = min(c, c0 + per);
+    double acc[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc[j] = 0.0;
+    if (live) {
+        const float* src = dpre + q * V;
+        int ch = c0;
+        if (V == 4) {
+            for (; ch + 4 <= c1; ch += 4) {                                   // four loads in flight, added in channel order
+                float4 t[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) t[u] = *reinterpret_cast<const float4*>(src + (int64_t)(ch + u) * hw);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { acc[0] += (double)t[u].x; acc[1 % V] += (double)t[u].y; acc[2 % V] += (double)t[u].z; acc[3 % V] += (double)t[u].w; }
+            }
+            for (; ch < c1; ++ch) {
+                const float4 t = *reinterpret_cast<const float4*>(src + (int64_t)ch * hw);
+                acc[0] += (double)t.x; acc[1 % V] += (double)t.y; acc[2 % V] += (double)t.z; acc[3 % V] += (double)t.w;
+            }
+        } else {
+            for (; ch < c1; ++ch) acc[0] += (double)src[(int64_t)ch * hw];
+        }
+    }
+    if (S > 1) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) part[sl][pq][j] = acc[j];
+        __syncthreads();
+        if (sl != 0) return;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            double s = part[0][pq][j];
+            for (int k = 1; k < S; ++k) s += part[k][pq][j];
+            acc[j] = s;
+        }
+    }
+    if (!live) return;
+    const double k = (double)strength[0];
+    float* dst = dnoise + q * V;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const float g = (float)(k * acc[j]);
+        dst[j] = accumulate ? dst[j] + g : g;
+    }
+}
+
+template <int V, int S>
+void launch_noise_grad(float* dnoise, const float* dpre, const float* strength, int c, int64_t hw, int accumulate, hipStream_t st) {
+    const int64_t groups = hw / V;
+    const int grid = (int)mgf_cdiv(groups, 256 / S);
+    hipLaunchKernelGGL((noise_grad_kernel<V, S>), dim3(grid), dim3(256), 0, st, dnoise, dpre, strength, c, hw, accumulate);
+}
+
+// ---------------------------------------------------------------------------------------------- regulariser
+// One level of the pyramid, side s: block partials of  a = sum x[y,x] x[y,x-1]  and  b = sum x[y,x] x[y-1,x]  (indices modulo s: the rolls
+// wrap), one thread per 2 x 2 block, and -- when `next` is given -- the block means, the next level's map.
+template <typename T>
+__global__ __launch_bounds__(256) void reg_level_fwd_kernel(double* __restrict__ partials, double* __restrict__ next, const T* __restrict__ x, int s) {
+    __shared__ double sh[4];
+    const int half = s >> 1;
+    const int64_t blocks = (int64_t)half * half;
+    double a = 0.0, b = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < blocks; i += (int64_t)gridDim.x * 256) {
+        const int by = (int)(i / half), bx = (int)(i % half);
+        const int y0 = 2 * by, x0 = 2 * bx;
+        const int ym = (y0 + s - 1) % s, xm = (x0 + s - 1) % s;
+        const T* r0 = x + (int64_t)y0 * s;
+        const T* r1 = r0 + s;
+        const T* ru = x + (int64_t)ym * s;
+        const double v00 = (double)r0[x0], v01 = (double)r0[x0 + 1], v10 = (double)r1[x0], v11 = (double)r1[x0 + 1];
+        const double l0 = (double)r0[xm], l1 = (double)r1[xm], u0 = (double)ru[x0], u1 = (double)ru[x0 + 1];
+        a += v00 * l0 + v01 * v00 + v10 * l1 + v11 * v10;
+        b += v00 * u0 + v01 * u1 + v10 * v00 + v11 * v01;
+        if (next) next[i] = (v00 + v01 + v10 + v11) * 0.25;
+    }
+    a = block_sum_256(a, sh);
+    b = block_sum_256(b, sh);
+    if (threadIdx.x == 0) { partials[2 * blockIdx.x] = a; partials[2 * blockIdx.x + 1] = b; }
+}
+
+struct RegLevels {
+    int32_t levels;
+    int32_t side[16];
+    int32_t nparts[16];
+};
+
+// One workgroup: fold every level's partials, stats[l] = {mean of the column product, mean of the row product}, and
+// value (+)= scale * sum_l (A_l^2 + B_l^2) when `value` is given.
+__global__ __launch_bounds__(256) void reg_finish_kernel(double* __restrict__ stats, float* value, const double* __restrict__ partials, RegLevels lv,
+                                                         double scale, int accumulate) {
+    __shared__ double sh[4];
+    double reg = 0.0;
+    for (int l = 0; l < lv.levels; ++l) {
+        const double* p = partials + (int64_t)l * NO_PARTS * 2;
+        const bool in = (int)threadIdx.x < lv.nparts[l];
+        const double a = block_sum_256(in ? p[2 * threadIdx.x] : 0.0, sh);
+        const double b = block_sum_256(in ? p[2 * threadIdx.x + 1] : 0.0, sh);
+        const double n = (double)lv.side[l] * (double)lv.side[l];
+        const double A = a / n, B = b / n;
+        if (threadIdx.x == 0) { stats[2 * l] = A; stats[2 * l + 1] = B; }
+        reg += A * A + B * B;
+    }
+    if (value && threadIdx.x == 0) {
+        const float v = (float)(scale * reg);
+        *value = accumulate ? *value + v : v;
+    }
+}
+
+// Gradient of one level, one thread per element:  g = 2A/N (left + right) + 2B/N (upper + lower) + 1/4 g_parent[y/2, x/2]  (the block
+// mean's adjoint); inner levels keep g in float64 scratch, the finest level writes dx (+)= scale * g.
+template <typename T>
+__global__ __launch_bounds__(256) void reg_level_bwd_kernel(double* __restrict__ gcur, float* __restrict__ dx, const T* __restrict__ x,
+                                                            const double* __restrict__ gparent, const double* __restrict__ stats, int s,
+                                                            double scale, int accumulate) {
+    const double n = (double)s * (double)s;
+    const double ka = 2.0 * stats[0] / n, kb = 2.0 * stats[1] / n;
+    const int64_t total = (int64_t)s * s;
+    const int half = s >> 1;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int y = (int)(i / s), xx = (int)(i % s);
+        const int ym = (y + s - 1) % s, yp = (y + 1) % s, xm = (xx + s - 1) % s, xp = (xx + 1) % s;
+        double g = ka * ((double)x[(int64_t)y * s + xm] + (double)x[(int64_t)y * s + xp])
+                 + kb * ((double)x[(int64_t)ym * s + xx] + (double)x[(int64_t)yp * s + xx]);
+        if (gparent) g += 0.25 * gparent[(int64_t)(y >> 1) * half + (xx >> 1)];
+        if (dx) {
+            const float v = (float)(scale * g);
+            dx[i] = accumulate ? dx[i] + v : v;
+        } else {
+            gcur[i] = g;
+        }
+    }
+}
+
+int reg_levels(int32_t side, RegLevels* lv) {
+    if (side < 2 || side > 32768 || (side & (side - 1))) return 0;
+    int l = 0;
+    for (int32_t s = side;; s >>= 1) {
+        lv->side[l] = s;
+        const int64_t blocks = (int64_t)(s / 2) * (s / 2);
+        int64_t g = mgf_cdiv(blocks, 256);
+        lv->nparts[l] = (int)(g > NO_PARTS ? NO_PARTS : g);
+        ++l;
+        if (s <= 8) break;
+    }
+    lv->levels = l;
+    return l;
+}
+
+// scratch, in doubles: partials [levels][NO_PARTS][2] | stats [levels][2] | the maps of levels 1.. | the gradients of levels 1..
+int64_t reg_pyramid_doubles(const RegLevels& lv) {
+    int64_t t = 0;
+    for (int l = 1; l < lv.levels; ++l) t += (int64_t)lv.side[l] * lv.side[l];
+    return t;
+}
+
+int reg_forward(const float* x, const RegLevels& lv, double* scratch, hipStream_t st) {
+    double* partials = scratch;
+    double* xp = scratch + (int64_t)lv.levels * NO_PARTS * 2 + (int64_t)lv.levels * 2;
+    const double* cur = nullptr;
+    for (int l = 0; l < lv.levels; ++l) {
+        double* next = l + 1 < lv.levels ? xp : nullptr;
+        double* pl = partials + (int64_t)l * NO_PARTS * 2;
+        if (l == 0)
+            hipLaunchKernelGGL(reg_level_fwd_kernel<float>, dim3(lv.nparts[l]), dim3(256), 0, st, pl, next, x, lv.side[l]);
+        else
+            hipLaunchKernelGGL(reg_level_fwd_kernel<double>, dim3(lv.nparts[l]), dim3(256), 0, st, pl, next, cur, lv.side[l]);
+        cur = xp;
+        if (next) xp += (int64_t)lv.side[l + 1] * lv.side[l + 1];
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- normalise
+__device__ __forceinline__ bool step_is_live(const int32_t* step, const int32_t* valid, int steps_total) {
+    if (!step) return true;
+    const int s = *step;
+    return s < steps_total && !(valid && valid[s] == 0);
+}
+
+__global__ __launch_bounds__(256) void norm_partial_kernel(double* __restrict__ partials, const float* __restrict__ x, int64_t numel) {
+    __shared__ double sh[4];
+    double s = 0.0, q = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < numel; i += (int64_t)gridDim.x * 256) {
+        const double v = (double)x[i];
+        s += v;
+        q += v * v;
+    }
+    s = block_sum_256(s, sh);
+    q = block_sum_256(q, sh);
+    if (threadIdx.x == 0) { partials[2 * blockIdx.x] = s; partials[2 * blockIdx.x + 1] = q; }
+}
+
+__global__ __launch_bounds__(256) void norm_apply_kernel(float* __restrict__ x, const double* __restrict__ partials, int nparts, int64_t numel,
+                                                         const int32_t* step, const int32_t* valid, int steps_total) {
+    __shared__ double sh[4];
+    if (!step_is_live(step, valid, steps_total)) return;                     // (uniform over the grid)
+    const bool in = (int)threadIdx.x < nparts;
+    const double s = block_sum_256(in ? partials[2 * threadIdx.x] : 0.0, sh);
+    const double q = block_sum_256(in ? partials[2 * threadIdx.x + 1] : 0.0, sh);
+    const double n = (double)numel;
+    const double mean = s / n;
+    const double var = (q - s * mean) / (n - 1.0);                            // unbiased, torch's default
+    const double inv = 1.0 / sqrt(var);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < numel; i += (int64_t)gridDim.x * 256)
+        x[i] = (float)(((double)x[i] - mean) * inv);
+}
+
+// ---------------------------------------------------------------------------------------------- Adam
+// adam_step_kernel of backward.hip, expression for expression, over a grid; the step count is advanced by a launch of its own behind it
+// (no block may see the new count).
+__global__ __launch_bounds__(256) void adam_elementwise_kernel(float* param, float* m, float* v, const int32_t* t_ctr, const float* grad,
+                                                               const float* lr_table, const int32_t* step, const int32_t* valid, int64_t numel,
+                                                               int steps_total, float beta1, float beta2, float eps, float weight_decay) {
+    const int s = *step;
+    if (s >= steps_total || (valid && valid[s] == 0)) return;
+    const int t = *t_ctr + 1;
+    const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
+    const float step_size = (float)((double)lr_table[s] / bc1);
+    const float bc2_sqrt = (float)sqrt(bc2);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < numel; i += (int64_t)gridDim.x * 256) {
+        float g = grad[i];
+        if (weight_decay != 0.f) g += weight_decay * param[i];
+        const float mi = m[i] + (g - m[i]) * (1.f - beta1);                 // exp_avg.lerp_(grad, 1 - beta1)
+        const float vi = v[i] * beta2 + (1.f - beta2) * g * g;
+        m[i] = mi;
+        v[i] = vi;
+        param[i] -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+    }
+}
+
+__global__ void adam_advance_kernel(int32_t* t_ctr, const int32_t* step, const int32_t* valid, int steps_total) {
+    const int s = *step;
+    if (s >= steps_total || (valid && valid[s] == 0)) return;
+    *t_ctr = *t_ctr + 1;
+}
+
+}  // namespace
+
+extern "C" int mgf_noise_grad_f32(float* dnoise, const float* dpre, const float* strength, int32_t c, int64_t hw, int32_t accumulate,
+                                  mgf_stream_t stream) {
+    MGF_REQUIRE(dnoise && dpre && strength, MGF_EINVAL, "noise_grad: null pointer");
+    MGF_REQUIRE(c >= 1 && hw >= 1, MGF_EINVAL, "noise_grad: bad sizes");
+    MGF_REQUIRE(hw <= ((int64_t)1 << 30), MGF_ETOOBIG, "noise_grad: map too large (%lld pixels)", (long long)hw);
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = hw % 4 == 0 && ((uintptr_t)dpre % 16) == 0 && ((uintptr_t)dnoise % 16) == 0;
+    if (vec) {
+        const int64_t groups = hw / 4;
+        if (groups >= 65536 || c < 16) launch_noise_grad<4, 1>(dnoise, dpre, strength, c, hw, accumulate, st);
+        else if (groups >= 16384 || c < 64) launch_noise_grad<4, 4>(dnoise, dpre, strength, c, hw, accumulate, st);
+        else launch_noise_grad<4, 16>(dnoise, dpre, strength, c, hw, accumulate, st);
+    } else {
+        if (c < 64) launch_noise_grad<1, 1>(dnoise, dpre, strength, c, hw, accumulate, st);
+        else launch_noise_grad<1, 16>(dnoise, dpre, strength, c, hw, accumulate, st);
+    }
+    MGF_CHECK_LAUNCH("noise_grad");
+    return MGF_OK;
+}
+
+extern "C" int64_t mgf_noise_regularize_scratch_bytes(int32_t side) {
+    RegLevels lv;
+    if (!reg_levels(side, &lv)) return 0;
+    return 8 * ((int64_t)lv.levels * NO_PARTS * 2 + (int64_t)lv.levels * 2 + 2 * reg_pyramid_doubles(lv));
+}
+
+extern "C" int mgf_noise_regularize_f32(float* value, const float* x, int32_t side, float scale, int32_t accumulate, void* scratch,
+                                        mgf_stream_t stream) {
+    RegLevels lv;
+    MGF_REQUIRE(value && x && scratch, MGF_EINVAL, "noise_regularize: null pointer");
+    MGF_REQUIRE(reg_levels(side, &lv), MGF_EUNSUPPORTED, "noise_regularize: the side must be a power of two in 2..32768 (got %d)", side);
+    MGF_REQUIRE(((uintptr_t)scratch % 8) == 0, MGF_EINVAL, "noise_regularize: scratch must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    double* sc = (double*)scratch;
+    reg_forward(x, lv, sc, st);
+    hipLaunchKernelGGL(reg_finish_kernel, dim3(1), dim3(256), 0, st, sc + (int64_t)lv.levels * NO_PARTS * 2, value, sc, lv, (double)scale, accumulate);
+    MGF_CHECK_LAUNCH("noise_regularize");
+    return MGF_OK;
+}
+
+extern "C" int mgf_noise_regularize_grad_f32(float* dx, float* value, const float* x, int32_t side, float scale, int32_t accumulate_dx,
+                                             int32_t accumulate_value, void* scratch, mgf_stream_t stream) {
+    RegLevels lv;
+    MGF_REQUIRE(dx && x && scratch, MGF_EINVAL, "noise_regularize_grad: null pointer");
+    MGF_REQUIRE(dx != x, MGF_EINVAL, "noise_regularize_grad: dx must not alias x");
+    MGF_REQUIRE(reg_levels(side, &lv), MGF_EUNSUPPORTED, "noise_regularize_grad: the side must be a power of two in 2..32768 (got %d)", side);
+    MGF_REQUIRE(((uintptr_t)scratch % 8) == 0, MGF_EINVAL, "noise_regularize_grad: scratch must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    double* sc = (double*)scratch;
+    double* stats = sc + (int64_t)lv.levels * NO_PARTS * 2;
+    double* xpyr = stats + (int64_t)lv.levels * 2;
+    double* gpyr = xpyr + reg_pyramid_doubles(lv);
+    reg_forward(x, lv, sc, st);
+    hipLaunchKernelGGL(reg_finish_kernel, dim3(1), dim3(256), 0, st, stats, value, sc, lv, (double)scale, accumulate_value);
+    // offsets of levels 1.. inside the two pyramids
+    int64_t off[16] = {0};
+    for (int l = 2; l < lv.levels; ++l) off[l] = off[l - 1] + (int64_t)lv.side[l - 1] * lv.side[l - 1];
+    for (int l = lv.levels - 1; l >= 0; --l) {
+        const int s = lv.side[l];
+        const int grid = mgf_stream_grid((int64_t)s * s, 256, 4);
+        const double* gparent = l + 1 < lv.levels ? gpyr + off[l + 1] : nullptr;
+        if (l == 0)
+            hipLaunchKernelGGL(reg_level_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (double*)nullptr, dx, x, gparent, stats, s, (double)scale,
+                               accumulate_dx);
+        else
+            hipLaunchKernelGGL(reg_level_bwd_kernel<double>, dim3(grid), dim3(256), 0, st, gpyr + off[l], (float*)nullptr,
+                               (const double*)(xpyr + off[l]), gparent, stats + 2 * l, s, 1.0, 0);
+    }
+    MGF_CHECK_LAUNCH("noise_regularize_grad");
+    return MGF_OK;
+}
+
+extern "C" int64_t mgf_noise_normalize_scratch_bytes(void) { return 8 * NO_PARTS * 2; }
+
+extern "C" int mgf_noise_normalize_f32(float* x, int64_t numel, const int32_t* step, const int32_t* valid, int32_t steps_total, void* scratch,
+                                       mgf_stream_t stream) {
+    MGF_REQUIRE(x && scratch, MGF_EINVAL, "noise_normalize: null pointer");
+    MGF_REQUIRE(numel >= 2, MGF_EINVAL, "noise_normalize: the unbiased std needs at least two elements (got %lld)", (long long)numel);
+    MGF_REQUIRE(step || !valid, MGF_EINVAL, "noise_normalize: a valid table needs the step counter");
+    MGF_REQUIRE(!step || steps_total >= 1, MGF_EINVAL, "noise_normalize: bad steps_total");
+    MGF_REQUIRE(((uintptr_t)scratch % 8) == 0, MGF_EINVAL, "noise_normalize: scratch must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    int64_t g = mgf_cdiv(numel, 256 * 4);
+    const int nparts = (int)(g > NO_PARTS ? NO_PARTS : g);
+    hipLaunchKernelGGL(norm_partial_kernel, dim3(nparts), dim3(256), 0, st, (double*)scratch, x, numel);
+    hipLaunchKernelGGL(norm_apply_kernel, dim3(mgf_stream_grid(numel, 256, 4)), dim3(256), 0, st, x, (const double*)scratch, nparts, numel, step,
+                       valid, steps_total);
+    MGF_CHECK_LAUNCH("noise_normalize");
+    return MGF_OK;
+}
+
+extern "C" int mgf_adam_elementwise_f32(float* param, float* exp_avg, float* exp_avg_sq, int32_t* adam_t, const float* grad, const float* lr_table,
+                                        const int32_t* step, const int32_t* valid, int64_t numel, int32_t steps_total, float beta1, float beta2,
+                                        float eps, float weight_decay, mgf_stream_t stream) {
+    MGF_REQUIRE(param && exp_avg && exp_avg_sq && adam_t && grad && lr_table && step, MGF_EINVAL, "adam_elementwise: null pointer");
+    MGF_REQUIRE(numel >= 1 && steps_total >= 1, MGF_EINVAL, "adam_elementwise: bad sizes");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(adam_elementwise_kernel, dim3(mgf_stream_grid(numel, 256, 4)), dim3(256), 0, st, param, exp_avg, exp_avg_sq,
+                       (const int32_t*)adam_t, grad, lr_table, step, valid, numel, steps_total, beta1, beta2, eps, weight_decay);
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, st, adam_t, step, valid, steps_total);
+    MGF_CHECK_LAUNCH("adam_elementwise");
+    return MGF_OK;
+}

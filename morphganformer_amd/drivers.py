@@ -77,12 +77,22 @@ def save_image(G, img, path, ratio=1.0):
     return path
 
 
-def save_latent_mat(path, w):
-    """`{'w': float32 [1,k,D]}` in MATLAB v5 format, like sio.savemat in the drivers (:201-206)."""
+def noise_mat_key(layer_name):
+    """The .mat key of a layer's optimised noise map: 'synthesis.b64.conv0' -> 'noise_b64_conv0' (MATLAB variable names hold no dots)."""
+    return "noise_" + layer_name.replace("synthesis.", "").replace(".", "_")
+
+
+def save_latent_mat(path, w, noises=None):
+    """`{'w': float32 [1,k,D]}` in MATLAB v5 format, like sio.savemat in the drivers (:201-206).  noises: {layer name: map} of a
+    projection that optimised the noise maps -- stored as [res, res] float32 arrays under noise_mat_key(name) beside 'w'."""
     import scipy.io as sio
     w = np.asarray(w.detach().cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float32)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    sio.savemat(path, {"w": w})
+    out = {"w": w}
+    for name, t in (noises or {}).items():
+        m = np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t, dtype=np.float32)
+        out[noise_mat_key(name)] = m.reshape(m.shape[-2], m.shape[-1])
+    sio.savemat(path, out)
     return path
 
 
@@ -212,7 +222,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                   eps=None, out_prefix=None, batch=DEFAULT_BATCH, use_graph=True, noise_mode="random", use_mse=True, seed=None,
                   landmark_fn=None, mode="literal", weight_decay=0.0, path_to_gen=None, keep_images=64, engine=None,
                   return_engine=False, latent_space="z", landmark_input="float", biometric=None, gamma=1.0, lbp_target=None, pipeline=None,
-                  mdf=None):
+                  mdf=None, optimize_noise=False, noise_init="randn"):
     """One full `projection(...)` call (:135-208).  `target`: [1,3,S,S] from image_transform; `lm_target` [68,2] and either
     `lm_steps` [steps,68,2] (injected landmark detections) or `landmark_fn` (host detector called on every generated image,
     see ProjectionEngine; landmark_input="gray_u8" hands it the drivers' gray uint8 image, built on the device).  mode="literal" is the loop as the reference executes it (best-of-N noisy sampling, `batch` steps per
@@ -241,6 +251,10 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     forward; LPIPS(vgg) and the FaceNet term, whose own matrix work then competes with the generator's, lose 1 - 1.5 %, and with no perceptual term
     there is nothing to overlap, -0.5 %: those stay on one stream).
 
+    optimize_noise / noise_init: gradient mode also descends the generator's per-layer noise maps (GradientProjectionEngine(optimize_noise=True):
+    Adam + noise_normalize_, args.noise_regularize * the regulariser in the total).  The result gains `noises`, the maps of the best step's image;
+    the PNG is rendered with them -- the scored image -- and the .mat holds them beside 'w' (noise_mat_key).
+
     engine: a ProjectionEngine from an earlier call with the same generator, objective, step count and batch (return_engine=True
     hands it out) -- it is re-targeted in place (`ProjectionEngine.retarget`), which keeps its captured hipGraph and workspaces; this is
     how `project_many` walks a list of targets."""
@@ -251,6 +265,8 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
         raise ValueError("engine= (re-targeting) is for literal mode")
     if latent_space not in ("z", "w+") or (latent_space == "w+" and mode != "gradient"):
         raise ValueError("latent_space must be 'z', or 'w+' together with mode='gradient'")
+    if optimize_noise and mode != "gradient":
+        raise ValueError("optimize_noise needs mode='gradient' (the literal loop never back-propagates)")
     if latent_mean is None or latent_std is None:
         gen = None
         if seed is not None:
@@ -279,7 +295,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
         eng = GradientProjectionEngine(G, target, latent_mean, float(latent_std), args, weight_decay=weight_decay, percept=percept,
                                        lm_target=lm_target, lm_steps=lm_steps, eps=eps, noise_mode=noise_mode, use_graph=use_graph,
                                        use_mse=use_mse, landmark_fn=landmark_fn, seed=0 if seed is None else seed, latent_space=latent_space,
-                                       biometric=biometric, gamma=gamma, mdf=mdf)
+                                       biometric=biometric, gamma=gamma, mdf=mdf, optimize_noise=optimize_noise, noise_init=noise_init)
     else:
         eng = ProjectionEngine(G, target, latent_mean, float(latent_std), args, percept=percept, lm_target=lm_target,
                                lm_steps=lm_steps, eps=eps, noise_mode=noise_mode, use_graph=use_graph, batch=batch, use_mse=use_mse,
@@ -287,17 +303,21 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                                biometric=biometric, gamma=gamma, lbp_target=lbp_target, pipeline=pipeline, mdf=mdf)
     w, step, loss, losses = eng.run().result()
     out = {"w": w, "step": step, "loss": loss, "losses": losses}
+    best_noises = None
+    if optimize_noise:
+        best_noises = {name: t.clone() for name, t in eng.best_noises.items()}
+        out["noises"] = best_noises
     if out_prefix is not None:
-        save_latent_mat(f"{out_prefix}.mat", w)
+        save_latent_mat(f"{out_prefix}.mat", w, noises=best_noises)
         if path_to_gen is None:                      # no improvement trail asked for: still leave an image of the result beside the latent
             from .projection import save_best_png
-            out["image"] = save_best_png(G, w, f"{out_prefix}.png", args.ratio)
+            out["image"] = save_best_png(G, w, f"{out_prefix}.png", args.ratio, noises=best_noises)
     if path_to_gen is not None:
         if mode == "literal":
             out["images"] = eng.save_improvements(path_to_gen, args.ratio)
         else:
             from .projection import save_best_png
-            out["images"] = [save_best_png(G, w, os.path.join(path_to_gen, "{:06d}_{:04f}.png".format(step, loss)), args.ratio)]
+            out["images"] = [save_best_png(G, w, os.path.join(path_to_gen, "{:06d}_{:04f}.png".format(step, loss)), args.ratio, noises=best_noises)]
     if return_engine:
         out["engine"] = eng
     return out

@@ -67,6 +67,10 @@ class GeneratorGrad:
         self.z = None
         self.psi = 1.0
         self.debug = None                 # dict -> clones of the intermediate gradients (tests / tools only)
+        # set by the first backward(..., dnoises=...) and kept: every noise layer's pre-activation gradient must then reach memory, so the
+        # fused pass that never stores conv0's (mgf_style_act_fir_bwd_f32) stays off and the partial-sum layout does not flip between calls
+        self.noise_grads = False
+        self._dnoises = None
 
     # ------------------------------------------------------------------ workspace
     def buf(self, role, shape):
@@ -129,7 +133,7 @@ class GeneratorGrad:
         self.max_channels = max(max(lp.cin, lp.cout) for lp in P.layers)
 
     def _want_fir_mode(self):
-        return bool(FUSE_ACT_FIR and FUSE_STYLE_ACT and self.debug is None)
+        return bool(FUSE_ACT_FIR and FUSE_STYLE_ACT and self.debug is None and not self.noise_grads)
 
     @staticmethod
     def _fir_block(l0, l1):
@@ -226,6 +230,29 @@ class GeneratorGrad:
         return img
 
     # ------------------------------------------------------------------ backward
+    def _noise_grad(self, lp, dz):
+        """d(noise map) of layer `lp` from its pre-activation gradient dz [n, c, h, w], which the caller still holds:
+        y = lrelu(c [attention] + noise_strength * noise + bias), so d noise = noise_strength * sum over the channels of dz."""
+        if self._dnoises is None or lp.noise_strength is None:
+            return
+        out = self._dnoises.get(lp.name)
+        if out is None:
+            return
+        n, c, h, w = dz.shape
+        if self.G.last_noise[0] == "none":
+            raise _lib.MgfError("GeneratorGrad: dnoises needs a forward pass that adds noise (noise_mode='none' has no noise input)")
+        _lib.require_gpu(out)
+        assert out.dtype == torch.float32 and out.is_contiguous()
+        L, st = _lib.lib(), _lib.stream_ptr()
+        if out.numel() == h * w:          # one map shared by the batch: the samples are further terms of the same sum
+            _lib.check(L.mgf_noise_grad_f32(out.data_ptr(), dz.data_ptr(), lp.noise_strength.data_ptr(), n * c, h * w, 0, st), "noise_grad")
+        elif out.numel() == n * h * w:    # a map per sample
+            for j in range(n):
+                _lib.check(L.mgf_noise_grad_f32(out.reshape(n, -1)[j].data_ptr(), dz[j].data_ptr(), lp.noise_strength.data_ptr(), c, h * w, 0, st),
+                           "noise_grad")
+        else:
+            raise _lib.MgfError(f"GeneratorGrad: dnoises[{lp.name!r}] must hold one {h}x{w} map, or one per sample (got {tuple(out.shape)})")
+
     def _act_bwd(self, lp, dy, y_out, residual, residual_low=None):
         """d(pre-activation) of one SynthesisLayer from the gradient dy of its output y_out = lrelu(c [attention] + noise + bias) * gain
         + residual (and, for a demodulated layer without attention, the <dz, c> partials of the demodulation gradient)."""
@@ -243,6 +270,7 @@ class GeneratorGrad:
                                                y_out.data_ptr(), _lib.ptr(residual), _lib.ptr(residual_low), w, _lib.ptr(lp.bias),
                                                _lib.ptr(noise), _lib.ptr(lp.noise_strength) if noise is not None else None, noise_n, n, c,
                                                h * w, alpha, gain, st), "layer_act_bwd")
+        self._noise_grad(lp, dz)
         return dz
 
     def _conv_bwd(self, lp, dz, y_out, c_pre, x_in, dT=None):
@@ -320,6 +348,7 @@ class GeneratorGrad:
                                                 _lib.ptr(residual), _lib.ptr(residual_low), w, _lib.ptr(prev.bias), _lib.ptr(noise),
                                                 _lib.ptr(prev.noise_strength) if noise is not None else None, noise_n,
                                                 n, c, h * w, alpha, gain, st), "style_grad_act_bwd")
+        self._noise_grad(prev, dz)
         return (dz, dx) if with_res else dz
 
     def _style_act_fir_bwd(self, lp, g, prev, y_prev):
@@ -343,21 +372,22 @@ class GeneratorGrad:
         g = self._conv_bwd(lp, dz, y_out, c_pre, x_in)
         return self._style_bwd(lp, g, x_in, dx_role)
 
-    def backward_w(self, dimg):
+    def backward_w(self, dimg, dnoises=None):
         """dimg [n,3,R,R] -> dw [n,k,D]: gradient of <img, dimg> with respect to the intermediate latent w (after a forward with
-        per-layer ws: summed over the layer slots, i.e. with respect to a latent set shared by all layers)."""
+        per-layer ws: summed over the layer slots, i.e. with respect to a latent set shared by all layers).  dnoises: see backward()."""
         G, cfg, L = self.G, self.G.cfg, _lib.lib()
-        self._backward_layers(dimg)
+        self._backward_layers(dimg, dnoises)
         _lib.check(L.mgf_latent_grad_gather(self.dw.data_ptr(), self.dwg.data_ptr(), self.n_style_jobs, self.dyc.data_ptr(),
                                             self.n_attn_jobs, G.n, cfg.k, cfg.w_dim, self.psi, _lib.stream_ptr()), "latent_grad_gather")
         return self.dw
 
-    def backward_ws(self, dimg):
+    def backward_ws(self, dimg, dnoises=None):
         """dimg [n,3,R,R] -> dws [n,k,num_ws,D]: the W+ gradient -- every layer's latent gradient lands in its own slot (layer `slot`
         reads ws[:, :, slot] for its style AND its attention values, networks.py:1022-1031,1252-1253; slots are unique per layer, so the
-        scatter has no collisions).  Valid after forward(ws=...) or forward(z): summed over axis 2 it equals backward_w()."""
+        scatter has no collisions).  Valid after forward(ws=...) or forward(z): summed over axis 2 it equals backward_w().
+        dnoises: see backward()."""
         G, cfg = self.G, self.G.cfg
-        self._backward_layers(dimg)
+        self._backward_layers(dimg, dnoises)
         T = cfg.k - 1
         self.dws.zero_()
         self.dws[:, T].index_copy_(1, self.style_slots, self.dwg)                                  # [n, num_ws, D] <- [n, layers, D]
@@ -367,13 +397,27 @@ class GeneratorGrad:
             self.dws.mul_(self.psi)
         return self.dws
 
-    def _backward_layers(self, dimg):
+    def _backward_layers(self, dimg, dnoises=None):
         """The synthesis network's backward pass down to the per-layer latent gradients: dwg [n, layers, D] (style path -> the global
-        component) and dyc [n, attention layers, T, D] (attention values -> the local components)."""
+        component) and dyc [n, attention layers, T, D] (attention values -> the local components); with `dnoises` also every noise
+        layer's d<img, dimg>/d(noise map), written where the layer's pre-activation gradient is at hand."""
         G, P, cfg, L = self.G, self.G.plan, self.G.cfg, _lib.lib()
         _lib.require_gpu(dimg)
         n = G.n
         assert self._n == n, "call forward() first"
+        if dnoises is not None and not self.noise_grads:
+            self.noise_grads = True
+            if self._fir_mode:            # the partial-sum buffers were laid out for the fused pass: lay them out for the stored-dz passes
+                self._alloc(n)
+        self._dnoises = dnoises
+        try:
+            self._backward_layers_body(dimg)
+        finally:
+            self._dnoises = None
+
+    def _backward_layers_body(self, dimg):
+        G, P, cfg, L = self.G, self.G.plan, self.G.cfg, _lib.lib()
+        n = G.n
         assert tuple(dimg.shape) == tuple(G.img.shape) and dimg.dtype == torch.float32
         dimg = dimg.contiguous()
         st = _lib.stream_ptr()
@@ -465,11 +509,16 @@ class GeneratorGrad:
         _lib.check(L.mgf_latent_bwd_multi(self.dwg.data_ptr(), self.style_jobs.data_ptr(), self.n_style_jobs, self.dyc.data_ptr(),
                                           _lib.ptr(self.attn_jobs), self.n_attn_jobs, n, T, D, self.max_channels, st), "latent_bwd_multi")
 
-    def backward(self, dimg):
-        """dimg -> dz [n,k,D] (through the mapping network; forward() must have been called with z)."""
+    def backward(self, dimg, dnoises=None):
+        """dimg -> dz [n,k,D] (through the mapping network; forward() must have been called with z).
+
+        dnoises: optional {layer name: float32 tensor of the layer's map, [res, res] or [1, res * res]}: every named layer that has a
+        noise input also writes d<img, dimg>/d(its noise map) there (mgf_noise_grad_f32 on the pre-activation gradient the pass already
+        holds; with n > 1 samples sharing one map, summed over them; [n, res * res] = a map per sample).  conv_last and ToRGB have no noise.
+        None: nothing beyond the latent gradient is launched."""
         G, cfg, L = self.G, self.G.cfg, _lib.lib()
         assert self.z is not None, "forward() was called with ws=...: use backward_w"
-        dw = self.backward_w(dimg)
+        dw = self.backward_w(dimg, dnoises)
         _lib.check(L.mgf_mapping_backward_saved(self.dz.data_ptr(), dw.data_ptr(), self.z.data_ptr(), G.plan.mapping_blob.data_ptr(),
                                           self.map_scratch.data_ptr(), G.n, cfg.k, cfg.w_dim, cfg.mapping_layers // 2,
                                           int(cfg.normalize_global), _lib.stream_ptr()), "mapping_backward_saved")

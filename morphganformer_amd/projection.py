@@ -74,6 +74,9 @@ class ProjectionArgs:
     # projection_example_v1.py:150-155: a generated image taller than `pool_above` pixels is block-averaged by height // pool_above before
     # the image-space losses (the target is then given at the pooled size, :84-92 resize it to 256); 0 = off (the 1024 drivers)
     pool_above: int = 0
+    # `--noise_regularize` of the drivers (:243): the weight of noise_regularize(noises) (:32-52).  Their loop never calls the function (it never
+    # back-propagates); GradientProjectionEngine(optimize_noise=True) adds noise_regularize * sum over the maps to its total.  Unused otherwise
+    noise_regularize: float = 1e5
 
 
 def get_lr(t, initial_lr, rampdown=0.25, rampup=0.05):
@@ -796,14 +799,26 @@ class GradientProjectionEngine(ProjectionEngine):
     def __init__(self, G, target, latent_mean, latent_std, args: ProjectionArgs = None, percept=None, use_mse=True, lm_target=None,
                  lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, landmark_fn=None, biometric=None,
                  gamma=1.0, wing_kind="wing", landmark_model=None, betas=(0.9, 0.999), adam_eps=1e-8, weight_decay=0.0,
-                 latent_space="z", mdf=None, **ignored):
+                 latent_space="z", mdf=None, optimize_noise=False, noise_init="randn", **ignored):
         """latent_space: "z" -- the drivers' parameter, the gradient runs on through the mapping network -- or "w+": the parameter is the
         per-layer intermediate latent ws [k, num_ws, D] itself (north_star: "backprops into the k-component latent W+"; layer `slot` reads
         ws[:, slot], networks.py:1252-1253), perturbed, descended by Adam and kept best-of exactly like z.  latent_mean is then a w-space
         start -- [k, D] (broadcast over the slots, e.g. latent_stats_w's mean) or [k, num_ws, D] -- and latent_std a w-space scale.  The
         reference has no such driver (its "W+" averages 18 copies of z, projection_example_v2_percept.py:133-162); the oracle is torch autograd
-        + Adam on ws through the CPU restatement (tests/test_hip_gradient.py)."""
+        + Adam on ws through the CPU restatement (tests/test_hip_gradient.py).
+
+        optimize_noise: the generator's per-layer noise inputs become parameters next to the latent, as in the StyleGAN2-style projectors the
+        drivers derive from (they still carry noise_regularize / noise_normalize_ and the --noise_regularize flag, :32-60, :243): the maps are
+        engine-owned tensors (`noise_init`: "randn", seeded, or "const", a copy of every layer's noise_const) the generator runs with
+        (`noise_mode` is then irrelevant), the total gains args.noise_regularize * sum over the maps of the regulariser, and every step the maps take
+        an Adam step with the latent's learning rate and betas followed by noise_normalize_.  `noises` holds the current maps, `best_noises`
+        those of the best step's image ({layer name: [1, res, res]}), both filled inside the launch sequence.  One target per engine."""
         from .grad import GeneratorGrad
+        if noise_init not in ("randn", "const"):
+            raise ValueError(f"noise_init must be 'randn' or 'const' (got {noise_init!r})")
+        if optimize_noise and int(target.shape[0]) > 1:
+            raise _lib.MgfError("GradientProjectionEngine: optimize_noise runs with one target per engine (lockstep targets share one generator "
+                                "forward, whose noise maps are shared by the batch; per-target maps are not built); project the targets one after the other")
         if mdf is not None and not getattr(mdf, "differentiable", False):
             raise _lib.MgfError("GradientProjectionEngine: this MDF loss was built without its backward pass -- build it with "
                                 "mdf.MDFLoss(..., differentiable=True) for gradient mode (ProjectionEngine(mdf=...), the literal loop, takes either)")
@@ -846,6 +861,69 @@ class GradientProjectionEngine(ProjectionEngine):
         self.exp_avg_sq = torch.zeros_like(self.latent_in)
         self.adam_t = torch.zeros(B, dtype=torch.int32, device=dev)
         self.dimg = torch.zeros_like(self.target)
+        self.optimize_noise = bool(optimize_noise)
+        self.noises = self.best_noises = None
+        if self.optimize_noise:
+            self._init_noise(noise_init, seed)
+
+    def _init_noise(self, noise_init, seed):
+        """The noise maps as parameters: ONE flat buffer each for the maps, their gradient, the two Adam moments and the best step's maps
+        (Adam is elementwise: one launch moves all of them), per-layer views for the generator, the backward pass and the per-map kernels."""
+        G, dev, L = self.G, self.device, _lib.lib()
+        layers = [lp for lp in G.plan.layers if lp.noise_strength is not None]
+        total = sum(lp.res * lp.res for lp in layers)
+        z = lambda: torch.zeros(total, dtype=torch.float32, device=dev)
+        self.noise_flat, self.noise_grad, self.noise_m, self.noise_v, self.best_noise_flat = z(), z(), z(), z(), z()
+        if noise_init == "randn":
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed) + 0x6E6F6973)                # (a stream of its own, not the head of the latent's eps stream)
+            self.noise_flat.copy_(torch.randn(total, device=dev, generator=gen))
+        self.noises, self.best_noises, self.dnoises, self.noise_layers = {}, {}, {}, []
+        off = 0
+        for lp in layers:
+            r = lp.res
+            if noise_init == "const":
+                self.noise_flat[off:off + r * r].copy_(lp.noise_const.reshape(-1))
+            self.noises[lp.name] = self.noise_flat[off:off + r * r].view(1, r, r)
+            self.best_noises[lp.name] = self.best_noise_flat[off:off + r * r].view(1, r, r)
+            self.dnoises[lp.name] = self.noise_grad[off:off + r * r].view(1, r, r)
+            self.noise_layers.append((lp.name, r))
+            off += r * r
+        self.noise_adam_t = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.noise_ctr = torch.zeros(1, dtype=torch.int32, device=dev)      # the step counter as it stood before select_best advanced it
+        # the improvement flag of select_best, through its one-slot trail: take_slot[0] = 0 where this step improved, else -1
+        self.noise_take = torch.full([1], -1, dtype=torch.int32, device=dev)
+        self.noise_trail_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.noise_trail_step = torch.full([1], -1, dtype=torch.int32, device=dev)
+        self.noise_trail_loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        nbytes = max(int(L.mgf_noise_regularize_scratch_bytes(r)) for _, r in self.noise_layers)
+        self.noise_reg_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        self.noise_norm_scratch = torch.empty(int(L.mgf_noise_normalize_scratch_bytes()) // 8, dtype=torch.float64, device=dev)
+        self.gg.noise_grads = True
+
+    def _noise_update(self):
+        """After select_best: keep the maps of an improving step (they still are the ones its image was generated with), then move them --
+        Adam on d total / d maps = the generator's d<img, dimg>/d maps (already in noise_grad) + noise_regularize * d reg / d maps, then
+        noise_normalize_ per map; a skipped step moves nothing (every kernel reads the step counter and the `valid` table itself)."""
+        L, st, a = _lib.lib(), _lib.stream_ptr(), self.args
+        _lib.check(L.mgf_keep_improvements(self.best_noise_flat.data_ptr(), self.noise_flat.data_ptr(), self.noise_flat.numel(),
+                                           self.noise_take.data_ptr(), 1, st), "keep_improvements(noise maps)")
+        _lib.check(L.mgf_adam_elementwise_f32(self.noise_flat.data_ptr(), self.noise_m.data_ptr(), self.noise_v.data_ptr(),
+                                              self.noise_adam_t.data_ptr(), self.noise_grad.data_ptr(), self.lr_table.data_ptr(),
+                                              self.noise_ctr.data_ptr(), _lib.ptr(self.valid), self.noise_flat.numel(), self.steps,
+                                              float(self.betas[0]), float(self.betas[1]), self.adam_eps, self.weight_decay, st), "adam_elementwise")
+        for name, r in self.noise_layers:
+            _lib.check(L.mgf_noise_normalize_f32(self.noises[name].data_ptr(), r * r, self.noise_ctr.data_ptr(), _lib.ptr(self.valid), self.steps,
+                                                 self.noise_norm_scratch.data_ptr(), st), "noise_normalize")
+
+    def _noise_regularize(self, has_p):
+        """p_loss (+)= noise_regularize * sum_maps reg and noise_grad += noise_regularize * d reg / d maps, map after map on one stream (the
+        regulariser rides in the float32 p_loss slot like the biometric and MDF terms; select_best forms the total in float64)."""
+        L, st, a = _lib.lib(), _lib.stream_ptr(), self.args
+        for i, (name, r) in enumerate(self.noise_layers):
+            _lib.check(L.mgf_noise_regularize_grad_f32(self.dnoises[name].data_ptr(), self.p_loss.data_ptr(), self.noises[name].data_ptr(), r,
+                                                       float(a.noise_regularize), 1, int(has_p or i > 0), self.noise_reg_scratch.data_ptr(), st),
+                       "noise_regularize_grad")
 
     def _init_multi(self, G, target, latent_mean, latent_std, args, percept, use_mse, lm_target, lm_steps, lm_valid, eps, noise_mode,
                     seed, use_graph, biometric, gamma, wing_kind, ls):
@@ -906,17 +984,23 @@ class GradientProjectionEngine(ProjectionEngine):
             self.dssim_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
 
     def _state(self):
-        return super()._state() + (self.latent_in, self.exp_avg, self.exp_avg_sq, self.adam_t)
+        st = super()._state() + (self.latent_in, self.exp_avg, self.exp_avg_sq, self.adam_t)
+        if self.optimize_noise:
+            st += (self.noise_flat, self.noise_m, self.noise_v, self.noise_adam_t, self.best_noise_flat, self.noise_take, self.noise_trail_count,
+                   self.noise_trail_step, self.noise_trail_loss)
+        return st
 
     def _iteration(self):
         L, st, a, B = _lib.lib(), _lib.stream_ptr(), self.args, self.targets
         # B targets: one flat parameter of B * numel floats, one noise row [B * numel] per step
         _lib.check(L.mgf_latent_perturb(self.latent_n.data_ptr(), self.latent_in.data_ptr(), self.eps.data_ptr(), self.sigma.data_ptr(),
                                         self.step_ctr.data_ptr(), 1, self.steps, B * self.numel, st), "latent_perturb")
+        opt_noise = self.optimize_noise
+        nkw = dict(noise_mode="inject", noises=self.noises) if opt_noise else dict(noise_mode=self.noise_mode)
         if self.latent_space == "w+":
-            img = self.gg.forward(ws=self.latent_n, noise_mode=self.noise_mode)   # [B, k, num_ws, D]: every layer reads its own slot
+            img = self.gg.forward(ws=self.latent_n, **nkw)                        # [B, k, num_ws, D]: every layer reads its own slot
         else:
-            img = self.gg.forward(self.latent_n, noise_mode=self.noise_mode)      # psi lands in `c` in the drivers: no truncation
+            img = self.gg.forward(self.latent_n, **nkw)                           # psi lands in `c` in the drivers: no truncation
         if B == 1:
             self._landmarks(img)                                                  # before Adam: a "no face" step must not move the latent
         per = img.numel() // B
@@ -944,8 +1028,15 @@ class GradientProjectionEngine(ProjectionEngine):
         if self.use_mse and not self.use_dssim:
             _lib.check(L.mgf_mse_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, per, tstride, 1.0, 0,
                                      self.scratch.data_ptr(), st), "mse")
-        dz = self.gg.backward_ws(self.dimg) if self.latent_space == "w+" else self.gg.backward(self.dimg)
+        if opt_noise:
+            dz = self.gg.backward_ws(self.dimg, dnoises=self.dnoises) if self.latent_space == "w+" else self.gg.backward(self.dimg, dnoises=self.dnoises)
+        else:
+            dz = self.gg.backward_ws(self.dimg) if self.latent_space == "w+" else self.gg.backward(self.dimg)
         has_p = self.percept is not None or self.biometric is not None or self.mdf is not None
+        if opt_noise:
+            self._noise_regularize(has_p)
+            has_p = True
+            self.noise_ctr.copy_(self.step_ctr)
         for j in range(B):                   # per-target optimizer step, Wing term and best-of bookkeeping (tiny launches)
             ctr = self.step_ctr[j:]
             valid = None if self.valid is None else (self.valid[j] if B > 1 else self.valid)
@@ -965,8 +1056,25 @@ class GradientProjectionEngine(ProjectionEngine):
                                          self.losses.reshape(B, -1)[j].data_ptr(), self.latent_n[j:].data_ptr(), self.numel,
                                          _lib.ptr(self.p_loss[j:] if has_p else None), _lib.ptr(self.w_loss[j:] if self.use_wing else None),
                                          _lib.ptr(self.mse_loss[j:] if self.use_mse else None), float(a.lamda), float(a.beta),
-                                         ctr.data_ptr(), _lib.ptr(valid), 1, self.steps, None, None, 0, None, None, st), "select_best")
+                                         ctr.data_ptr(), _lib.ptr(valid), 1, self.steps, _lib.ptr(self.noise_take if opt_noise else None),
+                                         _lib.ptr(self.noise_trail_count if opt_noise else None), int(opt_noise),
+                                         _lib.ptr(self.noise_trail_step if opt_noise else None),
+                                         _lib.ptr(self.noise_trail_loss if opt_noise else None), st), "select_best")
+        if opt_noise:
+            self._noise_update()
         return img
+
+    def rewind(self):
+        """Loop state back to step 0.  Like the latent and its Adam moments, the noise maps and theirs stay where the run left them; the
+        best step's maps and the improvement flag's trail are cleared with the best-so-far they belong to."""
+        super().rewind()
+        if self.optimize_noise:
+            self.best_noise_flat.zero_()
+            self.noise_take.fill_(-1)
+            self.noise_trail_count.zero_()
+            self.noise_trail_step.fill_(-1)
+            self.noise_trail_loss.zero_()
+        return self
 
     def run(self, steps=None):
         done = int(self.step_ctr[0].item()) if steps is None else None
@@ -992,14 +1100,17 @@ class GradientProjectionEngine(ProjectionEngine):
         return self.best_latent.cpu().clone(), bs, self.min_loss.cpu().numpy(), self.losses.cpu().numpy()
 
 
-def save_best_png(G, latent, path, ratio=1.0, noise_mode="const"):
-    """Write the image of `latent` as the drivers do (misc.to_pil + crop_max_rectangle, misc.py:94-130; :194-195)."""
+def save_best_png(G, latent, path, ratio=1.0, noise_mode="const", noises=None):
+    """Write the image of `latent` as the drivers do (misc.to_pil + crop_max_rectangle, misc.py:94-130; :194-195).  noises: the per-layer
+    maps to render with (GradientProjectionEngine(optimize_noise=True).best_noises: the saved PNG is then the scored image)."""
     from . import misc
     latent = latent.to(G.device)
+    if noises is not None:
+        noise_mode = "inject"
     if latent.ndim == 4:                       # a W+ result [1, k, num_ws, D] (GradientProjectionEngine(latent_space="w+"))
-        img = G.forward_workspace(ws=latent, noise_mode=noise_mode)[0]
+        img = G.forward_workspace(ws=latent, noise_mode=noise_mode, noises=noises)[0]
     else:
-        img = G.forward_workspace(latent, None, noise_mode=noise_mode)[0]
+        img = G.forward_workspace(latent, None, noise_mode=noise_mode, noises=noises)[0]
     im = misc.crop_max_rectangle(misc.to_pil(img), ratio)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     im.save(path)
