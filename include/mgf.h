@@ -424,6 +424,19 @@ int mgf_wing_loss_f64(double* out, const double* pred, const double* target, int
 /* AdaptiveWingLoss(omega=14, theta=0.5, epsilon=1, alpha=2.1) of adaptive_wing_loss.py:12-39, same row addressing as the wing loss */
 int mgf_adaptive_wing_loss_f64(double* out, const double* pred, const double* target, int32_t n, int64_t numel, double omega, double theta,
                                double epsilon, double alpha, const int32_t* pred_step, int32_t max_row, mgf_stream_t stream);
+/* The two-identity term of morph refinement (gradient mode; csrc/morph_pair.hip) -- the part of a pair objective that does not collapse to one
+ * blended target.  emb [n,width]; ta / tb [width] (t_batch_stride = 0: shared by the samples) or samples t_batch_stride elements apart, as in
+ * mgf_mse_f32; alpha [n] on the device (the weight of tb, merge_morph's convention):
+ *   loss[i] (+)= gamma ((1 - alpha_i) d_a + alpha_i d_b) + delta |d_a - d_b|,   d_t = d(emb[i], t_t)
+ *   metric 0: d = mean_c (e - t)^2 (torch.nn.MSELoss);  metric 1: d = 1 - <e,t> / (max(|e|, 1e-8) max(|t|, 1e-8)), the rule of
+ *             torch.nn.functional.cosine_similarity.  d|x|/dx at 0 is 0 and d|e|/de at e = 0 is 0, as in torch.
+ *   demb (may be NULL) [n,width] = d(the value added to loss[i]) / d emb[i]
+ *   trace (may be NULL) [n][trace_rows][2] float64: row *step (clamped to the table) of sample i receives (d_a, d_b); step is the device step
+ *             counter, read like mgf_wing_loss_f64 reads pred_step.
+ * One workgroup per sample, float32 loads, float64 arithmetic in a fixed order, no atomics (bit-reproducible); any width >= 1. */
+int mgf_embed_pair_loss_f32(float* loss, float* demb, double* trace, const float* emb, const float* ta, const float* tb, const float* alpha,
+                            int32_t n, int32_t width, int64_t t_batch_stride, float gamma, float delta, int32_t metric, int32_t accumulate,
+                            const int32_t* step, int32_t trace_rows, mgf_stream_t stream);
 int mgf_lpips_unit_f32(float* out, const float* f, int32_t n, int32_t c, int64_t hw, mgf_stream_t stream);
 int mgf_lpips_layer_f32(float* out, const float* f0, const float* f1_unit, const float* lin, int32_t n, int32_t c, int64_t hw,
                         int64_t f1_batch_stride, int32_t accumulate, float* scratch, mgf_stream_t stream);

@@ -6,6 +6,8 @@
                                               (1024_example_wing_loss_perceptual_sqz_MSE.py:222-268; argparse names kept)
     python -m morphganformer_amd.cli morph    --model net.pkl --w1 a.mat --w2 b.mat --alphas 0,0.1,...,1 --out out/a+b
                                               (1024_merge_morph_2.py:25-92)
+    python -m morphganformer_amd.cli morph    ... --refine --image-a a.png --image-b b.png --biometric iresnet50 --id-balance 0.5
+                                              (each blend descended against both subjects: <out>_a0.50_refined.mat / .png)
 
 `--gpus` pins the visible device like the scripts' CUDA_VISIBLE_DEVICES line.  The reference detects landmarks with dlib on the
 target and on every generated image; dlib is a closed third-party dependency, so `project` takes them from `--landmarks`
@@ -102,6 +104,92 @@ def _loop_arguments(p):
     p.add_argument("--mdf-random", action="store_true", help="seeded random discriminators instead of --mdf (smoke runs only)")
 
 
+def _refine_arguments(m):
+    """`morph --refine`: descend every blend against both contributing images (drivers.refine_morph).  Without --refine none of these is read."""
+    m.add_argument("--refine", action="store_true",
+                   help="after blending, descend each blend so that its image matches BOTH subjects (gradient mode with a target pair): "
+                        "<out>_a0.50_refined.mat / .png beside the linear morph's files; needs --image-a and --image-b")
+    m.add_argument("--image-a", type=str, default=None, help="--refine: the image --w1 was projected from (weighted 1 - alpha)")
+    m.add_argument("--image-b", type=str, default=None, help="--refine: the image --w2 was projected from (weighted alpha)")
+    m.add_argument("--id-balance", type=float, default=0.0, help="--refine: weight of |d_a - d_b|, the balance of the two identity distances (needs --biometric)")
+    m.add_argument("--id-metric", choices=["mse", "cosine"], default="mse",
+                   help="--refine: identity distance -- mse = mean squared embedding difference (the projection's term), cosine = 1 - cosine similarity")
+    m.add_argument("--size", type=int, default=1024)
+    m.add_argument("--step", type=int, default=5000)
+    m.add_argument("--lr", type=float, default=0.01)
+    m.add_argument("--lamda", type=float, default=0.01)
+    m.add_argument("--beta", type=float, default=1)
+    m.add_argument("--noise", type=float, default=0.05)
+    m.add_argument("--n_mean_latent", type=int, default=10000)
+    m.add_argument("--percept_weight", type=float, default=1.0)
+    m.add_argument("--pixel-term", choices=["mse", "dssim"], default="mse")
+    m.add_argument("--no-mse", action="store_true")
+    m.add_argument("--latent-space", choices=["auto", "z", "w+"], default="auto",
+                   help="--refine: the space of --w1 / --w2 (auto = by their shape: [1,k,D] is z, [1,k,num_ws,D] is W+)")
+    m.add_argument("--no-lockstep", action="store_true", help="--refine: one engine per alpha instead of all alphas in one")
+    m.add_argument("--net", type=str, default="squeeze", choices=["squeeze", "vgg", "alex"], help="LPIPS backbone")
+    m.add_argument("--no-lpips", action="store_true")
+    m.add_argument("--lpips-backbone", type=str, default=None, metavar="STATE_DICT")
+    m.add_argument("--lpips-random-backbone", action="store_true")
+    m.add_argument("--biometric", type=str, default="none", choices=["none", "facenet", "iresnet18", "iresnet34", "iresnet50", "iresnet100", "mobilefacenet"])
+    m.add_argument("--gamma", type=float, default=1.0, help="coefficient of the biometric term")
+    m.add_argument("--biometric-weights", type=str, default=None, metavar="STATE_DICT")
+    m.add_argument("--biometric-random", action="store_true")
+    m.add_argument("--seed", type=int, default=None)
+
+
+def _refine(a, G, alphas):
+    """`morph --refine` (drivers.refine_morph on the command line's objective)."""
+    import numpy as np
+    import torch
+    from . import drivers
+    from .projection import ProjectionArgs
+    w1, w2 = drivers.load_latent_mat(a.w1), drivers.load_latent_mat(a.w2)
+    space = "w+" if w1.ndim == 4 else "z"
+    if a.latent_space not in ("auto", space):
+        raise SystemExit(f"morph --refine: --latent-space {a.latent_space} but {a.w1} holds a {space} latent {w1.shape}")
+    args = ProjectionArgs(step=a.step, lamda=a.lamda, beta=a.beta, lr=a.lr, noise=a.noise, n_mean_latent=a.n_mean_latent, ratio=a.ratio,
+                          percept_weight=a.percept_weight, pixel_term=a.pixel_term)
+    percept = None
+    if not a.no_lpips:
+        if a.lpips_backbone is None and not a.lpips_random_backbone:
+            raise SystemExit("morph --refine: the LPIPS term needs the torchvision backbone weights: --lpips-backbone <state dict> "
+                             "(or --no-lpips / --lpips-random-backbone)")
+        from .lpips import PerceptualLoss, load_backbone_state
+        state = load_backbone_state(a.lpips_backbone) if a.lpips_backbone else None
+        if state is None:
+            print("WARNING: LPIPS runs on seeded random backbone weights (--lpips-random-backbone); the term is not a perceptual distance")
+        percept = PerceptualLoss(model="net-lin", net=a.net, use_gpu=True, device=G.device, backbone_state=state, allow_random_backbone=state is None)
+    biometric = None
+    if a.biometric != "none":
+        if a.biometric_weights is None and not a.biometric_random:
+            raise SystemExit(f"morph --refine: --biometric {a.biometric} needs the embedder's weights: --biometric-weights <state dict> (or --biometric-random)")
+        from .iresnet import BiometricLoss
+        state = None
+        if a.biometric_weights:
+            if a.biometric_weights.endswith(".npz"):
+                state = dict(np.load(a.biometric_weights))
+            else:
+                state = torch.load(a.biometric_weights, map_location="cpu", weights_only=True)
+                state = state.get("state_dict", state)
+        else:
+            print(f"WARNING: the biometric term runs on seeded random {a.biometric} weights (--biometric-random); it is not a face embedding")
+        biometric = BiometricLoss(a.biometric, state=state, n=1 if a.no_lockstep else len(alphas), device=G.device)
+    elif a.id_balance != 0.0:
+        raise SystemExit("morph --refine: --id-balance weighs the two identity distances: it needs --biometric")
+    if percept is None and a.no_mse and biometric is None:
+        raise SystemExit("morph --refine: every term of the objective is switched off")
+    ta = drivers.image_transform(a.image_a, size=a.size, device=G.device)
+    tb = drivers.image_transform(a.image_b, size=a.size, device=G.device)
+    res = drivers.refine_morph(G, w1, w2, ta, tb, alphas, lockstep=not a.no_lockstep, args=args, percept=percept, biometric=biometric,
+                               gamma=a.gamma, id_balance=a.id_balance, id_metric=a.id_metric, seed=a.seed, use_mse=not a.no_mse,
+                               out_prefix=a.out, ratio=a.ratio)
+    for r in res:
+        ids = "" if r["id_distances"] is None else "  d_a {:.6f}  d_b {:.6f}".format(*r["id_distances"])
+        print(f"alpha {r['alpha']:.2f}: best step {r['best_step']}  loss {r['best_loss']:.6f} (start {r['losses'][0]:.6f}){ids}")
+    return 0
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="morphganformer_amd", description="MI355X latent-projection / GANformer drivers")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -140,6 +228,7 @@ def build_parser():
     m.add_argument("--gpus", type=str, default="0")
     m.add_argument("--ratio", type=float, default=1.0)
     m.add_argument("--truncation_psi", type=float, default=0.7)
+    _refine_arguments(m)
     mf = sub.add_parser("merge-files", help="Fold a results tree <src>/<version>/<variant>/<id>/<name>/ over its variants (1024_merge_files.py); no model, no GPU")
     mf.add_argument("--src", type=str, required=True)
     mf.add_argument("--dst", type=str, required=True)
@@ -241,9 +330,11 @@ def main(argv=None):
         return 0
     if a.cmd == "morph":
         alphas = [float(v) for v in a.alphas.split(",")]
+        if a.refine and (a.image_a is None or a.image_b is None):
+            raise SystemExit("morph --refine needs the two contributing images: --image-a and --image-b")
         drivers.merge_morph(G, drivers.load_latent_mat(a.w1), drivers.load_latent_mat(a.w2), alphas, a.truncation_psi,
                             out_prefix=a.out, ratio=a.ratio)
-        return 0
+        return _refine(a, G, alphas) if a.refine else 0
     # project
     from .lpips import PerceptualLoss
     args = ProjectionArgs(step=a.step, lamda=a.lamda, beta=a.beta, lr=a.lr, lr_rampup=a.lr_rampup, lr_rampdown=a.lr_rampdown,

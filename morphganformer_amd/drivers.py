@@ -5,6 +5,7 @@
   generate_images   z ~ N(0,1) -> G(z, psi) -> PNG           (1024_generate.py:19-41)
   merge_morph       (1-a) w1 + a w2 -> G(., psi) -> JPG+.mat (1024_merge_morph_2.py:83-92; the reference hard-codes a = 0.5,
                     BASELINE config 4 sweeps 11 values)
+  refine_morph      the blend descended against BOTH contributing subjects (gradient mode with a target pair; no reference script)
   project_image     latent statistics + one ProjectionEngine run + best-of PNG / .mat   (:135-208, :246-268)
   second_stage      a projection initialised from an earlier result (edit_MSE.py pattern, BASELINE config 5)
   warp_morph        landmark-Delaunay warp of a morph onto the averaged landmarks (1024_warp_morphs.py:78-113,163-210)
@@ -142,7 +143,7 @@ def merge_morph(G, w1, w2, alphas=(0.5,), truncation_psi=0.7, noise_mode="random
     a2 = np.asarray(w2.detach().cpu() if isinstance(w2, torch.Tensor) else w2, dtype=np.float32)
     if a1.shape != a2.shape:
         raise ValueError(f"merge_morph: the two latents differ in shape: {a1.shape} vs {a2.shape}")
-    blend = lambda a: (0.5 * a1 + 0.5 * a2) if a == 0.5 else (np.float32(1.0 - a) * a1 + np.float32(a) * a2)
+    blend = lambda a: _blend_latents(a1, a2, a)
     lat, imgs = [], []
     sweep = render_latent(G, np.concatenate([blend(a) for a in alphas]), truncation_psi, noise_mode) if batched and len(alphas) > 1 else None
     for j, a in enumerate(alphas):
@@ -155,6 +156,85 @@ def merge_morph(G, w1, w2, alphas=(0.5,), truncation_psi=0.7, noise_mode="random
         lat.append(dw)
         imgs.append(img[0].clone())
     return np.stack(lat), torch.stack(imgs)
+
+
+def _blend_latents(a1, a2, a):
+    """merge_morph's latent blend in its float32 numpy arithmetic (`0.5 * w1 + 0.5 * w2` on loadmat arrays, 1024_merge_morph_2.py:83)."""
+    return (0.5 * a1 + 0.5 * a2) if a == 0.5 else (np.float32(1.0 - a) * a1 + np.float32(a) * a2)
+
+
+def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, args: ProjectionArgs = None, percept=None, biometric=None,
+                 gamma=1.0, id_balance=0.0, id_metric="mse", latent_std=None, eps=None, seed=None, use_graph=True, noise_mode="random",
+                 use_mse=True, lm_target=None, lm_target_b=None, lm_steps=None, weight_decay=0.0, mode="gradient", out_prefix=None, ratio=None):
+    """Morph refinement: for every alpha start at merge_morph's blend (1 - a) w1 + a w2 (the same float32 arithmetic) and descend it so that
+    the image matches BOTH contributing subjects -- target_a weighted 1 - a, target_b weighted a: perceptually, in pixels and in identity
+    space, the two identity distances kept in balance by id_balance |d_a - d_b| (GradientProjectionEngine(target_b=...) has the objective).
+    w1 / w2: [1,k,D] z latents or [1,k,num_ws,D] W+ latents (what the `.mat` files hold; the latent space follows their shape);
+    target_a / target_b: [1,3,S,S].  lockstep=True refines all alphas in ONE engine (B lockstep pairs, one generator forward / backward per
+    step); False runs one engine per alpha on the same noise stream.  latent_std: the perturbation scale around the start (default: the
+    latent statistics' scale, as for a projection).  lm_target / lm_target_b [68,2] and lm_steps [steps,68,2] add the Wing term against the
+    blended landmarks.  Returns one dict per alpha: alpha, w_start (numpy), w (best latent, [1,k,D] or W+), losses, best_step, best_loss,
+    id_distances ((d_a, d_b) at the best step; None without a biometric term).  out_prefix: `<prefix>_a{alpha:.2f}_refined.mat / .png`, the
+    image rendered like a projection result (no truncation)."""
+    if mode != "gradient":
+        raise ValueError(f"refine_morph descends the objective: mode must be 'gradient' (got {mode!r}; the literal loop never moves the latent)")
+    a1 = np.asarray(w1.detach().cpu() if isinstance(w1, torch.Tensor) else w1, dtype=np.float32)
+    a2 = np.asarray(w2.detach().cpu() if isinstance(w2, torch.Tensor) else w2, dtype=np.float32)
+    if a1.shape != a2.shape:
+        raise ValueError(f"refine_morph: the two latents differ in shape: {a1.shape} vs {a2.shape}")
+    if a1.ndim not in (3, 4) or a1.shape[0] != 1:
+        raise ValueError(f"refine_morph: latents must be [1,k,D] or [1,k,num_ws,D] (got {a1.shape})")
+    alphas = [float(a) for a in alphas]
+    if not alphas or not all(0.0 <= a <= 1.0 for a in alphas):
+        raise ValueError(f"refine_morph: alphas must lie in [0, 1] (got {alphas})")
+    if tuple(target_a.shape) != tuple(target_b.shape) or target_a.shape[0] != 1:
+        raise ValueError(f"refine_morph: target_a and target_b must both be [1,3,S,S] (got {tuple(target_a.shape)} and {tuple(target_b.shape)})")
+    from .projection import save_best_png
+    args = args or ProjectionArgs()
+    space = "w+" if a1.ndim == 4 else "z"
+    starts = [_blend_latents(a1, a2, a) for a in alphas]
+    B = len(alphas)
+    dev = G.device
+    if latent_std is None:
+        gen = None
+        if seed is not None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(seed)
+        _, latent_std = (latent_stats_w if space == "w+" else latent_stats)(G, args.n_mean_latent, dev, generator=gen)
+    ls = tuple(a1.shape[1:])
+    if eps is None:                      # one stream for the whole sweep: lockstep or not, alpha j sees the same noise
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(0 if seed is None else seed)
+        eps = torch.randn(args.step, B, *ls, device=dev, generator=gen)
+    eps = eps.to(dev).float().reshape(-1, B, *ls)
+
+    def run(js):
+        n = len(js)
+        rep = lambda t: t.expand(n, *t.shape[1:]).contiguous()
+        lm_kw = {}
+        if lm_target is not None:
+            tile = lambda x: np.asarray(x, dtype=np.float64) if n == 1 else np.stack([np.asarray(x, dtype=np.float64)] * n)
+            lm_kw = dict(lm_target=tile(lm_target), lm_steps=tile(lm_steps), lm_target_b=None if lm_target_b is None else tile(lm_target_b))
+        eng = GradientProjectionEngine(G, rep(target_a), torch.from_numpy(np.concatenate([starts[j] for j in js])).to(dev), float(latent_std), args,
+                                       weight_decay=weight_decay, percept=percept, eps=eps[:, js].contiguous(), noise_mode=noise_mode,
+                                       use_graph=use_graph, use_mse=use_mse, latent_space=space, biometric=biometric, gamma=gamma,
+                                       target_b=rep(target_b), morph_alpha=[alphas[j] for j in js], id_balance=id_balance, id_metric=id_metric,
+                                       **lm_kw)
+        w, step, loss, losses = eng.run().result()
+        trace = None if eng.id_trace is None else eng.id_trace.cpu().numpy()
+        if n == 1:
+            w, step, loss, losses = w, [step], [loss], losses[None]
+        return [dict(alpha=alphas[j], w_start=starts[j], w=w[i:i + 1].clone(), losses=np.asarray(losses[i]), best_step=int(step[i]),
+                     best_loss=float(loss[i]), id_distances=None if trace is None else (float(trace[i, int(step[i]), 0]), float(trace[i, int(step[i]), 1])))
+                for i, j in enumerate(js)]
+
+    out = run(list(range(B))) if lockstep else [r for j in range(B) for r in run([j])]
+    if out_prefix is not None:
+        for r in out:
+            tag = f"{out_prefix}_a{r['alpha']:.2f}_refined"
+            save_latent_mat(tag + ".mat", r["w"])
+            r["image"] = save_best_png(G, r["w"], tag + ".png", args.ratio if ratio is None else ratio)
+    return out
 
 
 def merge_morph_tree(G, src_path, dst_path, truncation_psi=0.7, ratio=1.0, noise_mode="random"):

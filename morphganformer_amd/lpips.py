@@ -532,6 +532,7 @@ class PerceptualLoss(torch.nn.Module):
         self._stats = {}
         self._target_taps = None
         self._target_n = 1
+        self.pair_offset = None           # [B] float32 = alpha (1 - alpha) LPIPS(Ta, Tb) while a target pair is set (set_target_pair)
         self._last, self._last_hw = None, None
         # the one-pass stem exists for SqueezeNet's first three layers; MGF_LPIPS_STEM=0 (tuning hook) keeps them separate
         self.fused_stem = net == "squeeze" and os.environ.get("MGF_LPIPS_STEM", "1") != "0"
@@ -578,6 +579,41 @@ class PerceptualLoss(torch.nn.Module):
                 continue                            # the stem already wrote tap 0 normalised
             _lib.check(L.mgf_lpips_unit_f32(t.data_ptr(), t.data_ptr(), n, t.shape[1], t.shape[2] * t.shape[3], st), "lpips_unit")
         self._target_taps = outs
+        self.pair_offset = None                     # a single target again: no constant to add (set_target_pair sets it afterwards)
+
+    def set_target_pair(self, target_a, target_b, alpha):
+        """Two targets per candidate, target_b weighted by alpha and target_a by 1 - alpha (drivers.merge_morph's convention).  With unit taps
+        u_a, u_b every tap's term is quadratic in the candidate's unit tap u_x, so for weights that sum to one
+            (1 - alpha) LPIPS(x, Ta) + alpha LPIPS(x, Tb) = sum_taps mean_hw sum_c lin_c (u_x - u)^2 + alpha (1 - alpha) LPIPS(Ta, Tb),
+        u = (1 - alpha) u_a + alpha u_b: the cached taps become u (the tap kernels take the target map as data; nothing in them needs it to
+        have unit norm) and `pair_offset` [B] holds the constant.  `distance_into` / `grad_into` then run exactly as for one target -- the caller
+        adds pair_offset.  targets: [1,3,H,W], or [B,...] for B lockstep pairs; alpha: a float or B of them.  alpha exactly 0 or 1 keeps that
+        target's taps as they are (a copy, no arithmetic).  Same geometry as before: taps and offset are rewritten in place (a captured
+        hipGraph keeps reading them)."""
+        _lib.require_gpu(target_a, target_b)
+        if tuple(target_a.shape) != tuple(target_b.shape):
+            raise ValueError(f"set_target_pair: the two targets differ in shape: {tuple(target_a.shape)} vs {tuple(target_b.shape)}")
+        n = int(target_a.shape[0])
+        al = np.asarray(alpha.detach().cpu() if isinstance(alpha, torch.Tensor) else alpha, dtype=np.float64).reshape(-1)
+        if al.size not in (1, n) or not np.all((al >= 0.0) & (al <= 1.0)):
+            raise ValueError(f"set_target_pair: alpha must be one value or {n} values in [0, 1] (got {alpha!r})")
+        al = np.array(np.broadcast_to(al, (n,)))
+        buf = getattr(self, "_pair_offset_buf", None)
+        if buf is None or buf.numel() != n:
+            buf = self._pair_offset_buf = torch.zeros(n, dtype=torch.float32, device=self.device_)
+        self.set_target(target_b)
+        ub = [t.clone() for t in self._target_taps]
+        self.distance_into(buf, target_a.float().contiguous())                  # LPIPS(Ta, Tb), per pair, through the distance kernels
+        buf.mul_(torch.as_tensor(al * (1.0 - al), dtype=torch.float32, device=self.device_))
+        self.set_target(target_a)                                               # in place when the geometry is unchanged
+        for t, b in zip(self._target_taps, ub):
+            for i in range(n):
+                a = float(al[i])
+                if a == 1.0:
+                    t[i].copy_(b[i])
+                elif a != 0.0:
+                    t[i].mul_(1.0 - a).add_(b[i], alpha=a)
+        self.pair_offset = buf
 
     def grad_into(self, dimg, scale=1.0, accumulate=False):
         """dimg (+)= d(scale * distance)/d(pred) for the pred of the latest `distance_into(..., keep_taps=True)` call

@@ -794,12 +794,19 @@ class GradientProjectionEngine(ProjectionEngine):
     `target` may hold B > 1 images: B independent projections (own latent, Adam state, noise stream, landmarks, best-so-far)
     advance in lockstep through ONE generator forward/backward per step -- the batch that lifts the 4x4..64x64 layers off
     their batch-1 latency floor (BASELINE configs 3 and 5 are batches of independent targets).  lm_target is then [B,68,2],
-    lm_steps [B,steps,68,2], lm_valid [B,steps], eps [steps,B,k,D]; `result()` returns per-target lists."""
+    lm_steps [B,steps,68,2], lm_valid [B,steps], eps [steps,B,k,D]; `result()` returns per-target lists.
+
+    target_b (morph refinement): every projection matches TWO identities, `target` weighted 1 - morph_alpha and target_b weighted morph_alpha
+    (merge_morph's convention; a float or one value per pair):
+        total = percept_weight [(1-a) LPIPS(x,Ta) + a LPIPS(x,Tb)] + beta [(1-a) P(x,Ta) + a P(x,Tb)] + lamda Wing
+                + gamma [(1-a) d_a + a d_b] + id_balance |d_a - d_b|,     d_t = d(embed(x), embed(T_t)), id_metric "mse" or "cosine"
+    lm_target_b blends the Wing term's target landmarks the same way; `id_trace` [B,steps,2] holds (d_a, d_b) per step.  See _init_pair."""
 
     def __init__(self, G, target, latent_mean, latent_std, args: ProjectionArgs = None, percept=None, use_mse=True, lm_target=None,
                  lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, landmark_fn=None, biometric=None,
                  gamma=1.0, wing_kind="wing", landmark_model=None, betas=(0.9, 0.999), adam_eps=1e-8, weight_decay=0.0,
-                 latent_space="z", mdf=None, optimize_noise=False, noise_init="randn", **ignored):
+                 latent_space="z", mdf=None, optimize_noise=False, noise_init="randn", target_b=None, morph_alpha=0.5, id_balance=0.0,
+                 id_metric="mse", lm_target_b=None, **ignored):
         """latent_space: "z" -- the drivers' parameter, the gradient runs on through the mapping network -- or "w+": the parameter is the
         per-layer intermediate latent ws [k, num_ws, D] itself (north_star: "backprops into the k-component latent W+"; layer `slot` reads
         ws[:, slot], networks.py:1252-1253), perturbed, descended by Adam and kept best-of exactly like z.  latent_mean is then a w-space
@@ -814,6 +821,10 @@ class GradientProjectionEngine(ProjectionEngine):
         an Adam step with the latent's learning rate and betas followed by noise_normalize_.  `noises` holds the current maps, `best_noises`
         those of the best step's image ({layer name: [1, res, res]}), both filled inside the launch sequence.  One target per engine."""
         from .grad import GeneratorGrad
+        pair = self._pair_arguments(target, target_b, morph_alpha, id_balance, id_metric, biometric, mdf, optimize_noise, lm_target, lm_target_b)
+        if pair is not None:
+            # the pixel target of the MSE term and the Wing term's landmarks are the blends: what the single-target code below is handed
+            target, lm_target = pair["blend"], pair["lm_blend"]
         if noise_init not in ("randn", "const"):
             raise ValueError(f"noise_init must be 'randn' or 'const' (got {noise_init!r})")
         if optimize_noise and int(target.shape[0]) > 1:
@@ -865,6 +876,87 @@ class GradientProjectionEngine(ProjectionEngine):
         self.noises = self.best_noises = None
         if self.optimize_noise:
             self._init_noise(noise_init, seed)
+        self.pair, self.id_trace = pair, None
+        if pair is not None:
+            self._init_pair(float(id_balance), id_metric)
+
+    @staticmethod
+    def _pair_arguments(target, target_b, morph_alpha, id_balance, id_metric, biometric, mdf, optimize_noise, lm_target, lm_target_b):
+        """Checks of the two-identity objective, and its blended single-target inputs.  None without target_b."""
+        if target_b is None:
+            if lm_target_b is not None or float(id_balance) != 0.0:
+                raise ValueError("GradientProjectionEngine: lm_target_b and id_balance belong to a target pair: pass target_b")
+            return None
+        if mdf is not None:
+            raise _lib.MgfError("GradientProjectionEngine: target_b (morph refinement) does not combine with mdf=: the MDF loss is not a sum of "
+                                "quadratic terms against stored target activations, so it would need a second evaluation per step, which is not built")
+        if optimize_noise:
+            raise _lib.MgfError("GradientProjectionEngine: target_b (morph refinement) does not combine with optimize_noise=True (noise maps fitted "
+                                "to two images at once are not built)")
+        if float(id_balance) != 0.0 and biometric is None:
+            raise ValueError("GradientProjectionEngine: id_balance weighs |d_a - d_b| of the biometric term: pass biometric= with it")
+        if float(id_balance) < 0.0:
+            raise ValueError(f"GradientProjectionEngine: id_balance must be >= 0 (got {id_balance})")
+        if id_metric not in ("mse", "cosine"):
+            raise ValueError(f"GradientProjectionEngine: id_metric must be 'mse' or 'cosine' (got {id_metric!r})")
+        _lib.require_gpu(target, target_b)
+        if tuple(target_b.shape) != tuple(target.shape):
+            raise ValueError(f"GradientProjectionEngine: target and target_b do not pair up: {tuple(target.shape)} vs {tuple(target_b.shape)}")
+        B = int(target.shape[0])
+        al = np.asarray(morph_alpha.detach().cpu() if isinstance(morph_alpha, torch.Tensor) else morph_alpha, dtype=np.float64).reshape(-1)
+        if al.size not in (1, B):
+            raise ValueError(f"GradientProjectionEngine: morph_alpha must be one value or one per pair ({B}), got {al.size}")
+        if not np.all((al >= 0.0) & (al <= 1.0)):
+            raise ValueError(f"GradientProjectionEngine: morph_alpha must lie in [0, 1] (got {al.tolist()}): the objective's reduction to one "
+                             "blended target holds for convex weights only")
+        al = np.array(np.broadcast_to(al, (B,)))
+        ta = target.detach().float().clone(memory_format=torch.contiguous_format)
+        tb = target_b.detach().float().clone(memory_format=torch.contiguous_format)
+        blend = torch.empty_like(ta)
+        for j in range(B):                  # alpha exactly 0 or 1: that target's own bits (the end points equal the single-target engine)
+            a = float(al[j])
+            blend[j] = ta[j] if a == 0.0 else (tb[j] if a == 1.0 else ta[j] * (1.0 - a) + tb[j] * a)
+        lm_blend = lm_target
+        if lm_target_b is not None:
+            if lm_target is None:
+                raise ValueError("GradientProjectionEngine: lm_target_b needs lm_target (the first identity's landmarks)")
+            la, lb = np.asarray(lm_target, dtype=np.float64), np.asarray(lm_target_b, dtype=np.float64)
+            if la.shape != lb.shape:
+                raise ValueError(f"GradientProjectionEngine: lm_target and lm_target_b do not pair up: {la.shape} vs {lb.shape}")
+            w = al.reshape((B,) + (1,) * (la.ndim - 1)) if (B > 1 or la.ndim == 3) else float(al[0])
+            lm_blend = (1.0 - w) * la + w * lb
+        return dict(ta=ta, tb=tb, alpha=al, blend=blend, lm_blend=lm_blend)
+
+    def _init_pair(self, id_balance, id_metric):
+        """Two identities per projection (morph refinement).  Every quadratic term against (Ta weighted 1 - alpha, Tb weighted alpha) equals
+        the same term against one blended target plus a constant, so LPIPS, MSE and their backward run once per step on blends -- the cached
+        unit taps (PerceptualLoss.set_target_pair) and the pixel blend `self.target` -- and the constants are added on the device; DSSIM is
+        evaluated against both targets; the identity term (balance |d_a - d_b|, cosine metric) is mgf_embed_pair_loss_f32."""
+        P, a, dev, B = self.pair, self.args, self.device, self.targets
+        L, st = _lib.lib(), _lib.stream_ptr()
+        al = P["alpha"]
+        self.pair_alpha = torch.as_tensor(al, dtype=torch.float32, device=dev)
+        if self.percept is not None:
+            self.percept.set_target_pair(P["ta"], P["tb"], al)
+            self.pair_p_off = self.percept.pair_offset * float(a.percept_weight)          # percept_weight * alpha (1 - alpha) LPIPS(Ta, Tb)
+        if self.use_mse and not self.use_dssim:
+            per = P["ta"].numel() // B
+            self.pair_mse_off = torch.zeros(B, dtype=torch.float32, device=dev)
+            _lib.check(L.mgf_mse_f32(self.pair_mse_off.data_ptr(), P["ta"].data_ptr(), P["tb"].data_ptr(), B, per, per, 1.0, 0,
+                                     self.scratch.data_ptr(), st), "mse(target pair)")
+            self.pair_mse_off.mul_(torch.as_tensor(al * (1.0 - al), dtype=torch.float32, device=dev))      # select_best multiplies by beta
+        if self.use_dssim:
+            self.pair_dssim = torch.zeros(2, B, dtype=torch.float32, device=dev)
+            self.pair_w = torch.as_tensor(np.stack([1.0 - al, al]), dtype=torch.float32, device=dev)
+        if self.biometric is not None:
+            self.biometric.set_target_pair(P["ta"], P["tb"], al, id_balance=id_balance, metric=id_metric)
+            self.id_trace = torch.full([B, self.steps, 2], float("nan"), dtype=torch.float64, device=dev)
+            self.biometric.pair_trace = (self.id_trace, self.step_ctr)
+
+    def retarget(self, *args, **kw):
+        if getattr(self, "pair", None) is not None:
+            raise _lib.MgfError("GradientProjectionEngine: an engine built on a target pair is not re-targeted; build a fresh one")
+        return super().retarget(*args, **kw)
 
     def _init_noise(self, noise_init, seed):
         """The noise maps as parameters: ONE flat buffer each for the maps, their gradient, the two Adam moments and the best step's maps
@@ -985,6 +1077,8 @@ class GradientProjectionEngine(ProjectionEngine):
 
     def _state(self):
         st = super()._state() + (self.latent_in, self.exp_avg, self.exp_avg_sq, self.adam_t)
+        if getattr(self, "id_trace", None) is not None:
+            st += (self.id_trace,)
         if self.optimize_noise:
             st += (self.noise_flat, self.noise_m, self.noise_v, self.noise_adam_t, self.best_noise_flat, self.noise_take, self.noise_trail_count,
                    self.noise_trail_step, self.noise_trail_loss)
@@ -1005,7 +1099,17 @@ class GradientProjectionEngine(ProjectionEngine):
             self._landmarks(img)                                                  # before Adam: a "no face" step must not move the latent
         per = img.numel() // B
         tstride = per if B > 1 else 0
-        if self.use_dssim:                   # dimg = beta * d dssim / d img and the unscaled value, one pass (the continuous DSSIM, see ProjectionArgs)
+        pair = self.pair
+        if self.use_dssim and pair is not None:
+            # DSSIM is not quadratic in the image: both targets, sample by sample (the weight is the sample's own), gradients accumulated
+            c, h, w = img.shape[1:]
+            for t, tgt in enumerate((pair["ta"], pair["tb"])):
+                for j in range(B):
+                    wt = float(pair["alpha"][j]) if t else 1.0 - float(pair["alpha"][j])
+                    _lib.check(L.mgf_dssim_grad_f32(self.dimg[j:].data_ptr(), self.pair_dssim[t, j:].data_ptr(), img[j:].data_ptr(), tgt[j:].data_ptr(),
+                                                    1, c, h, w, 0, 255.0, float(a.beta) * wt, t, 0, self.dssim_scratch.data_ptr(), st), "dssim_grad")
+            torch.sum(self.pair_dssim * self.pair_w, 0, out=self.mse_loss)
+        elif self.use_dssim:                 # dimg = beta * d dssim / d img and the unscaled value, one pass (the continuous DSSIM, see ProjectionArgs)
             c, h, w = img.shape[1:]
             _lib.check(L.mgf_dssim_grad_f32(self.dimg.data_ptr(), self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, c, h, w, tstride,
                                             255.0, float(a.beta), 0, 0, self.dssim_scratch.data_ptr(), st), "dssim_grad")
@@ -1019,7 +1123,9 @@ class GradientProjectionEngine(ProjectionEngine):
             self.percept.grad_into(self.dimg, scale=float(a.percept_weight), accumulate=True)
             if a.percept_weight != 1.0:
                 self.p_loss.mul_(float(a.percept_weight))
-        if self.biometric is not None:      # rides in the p_loss slot, like the literal loop
+            if pair is not None:            # the constant the blended taps leave out: `losses` holds the pair objective, not a shifted one
+                self.p_loss.add_(self.pair_p_off)
+        if self.biometric is not None:      # rides in the p_loss slot, like the literal loop (a target pair: one launch of the pair kernel)
             self.biometric.distance_into(self.p_loss, img, scale=self.gamma, accumulate=self.percept is not None)
             self.biometric.grad_into(self.dimg, scale=self.gamma, accumulate=True)
         if self.mdf is not None:            # p_loss (+)= MDF, dimg += d MDF / d img (1024_example_mdfloss.py:165 without the detach)
@@ -1028,6 +1134,8 @@ class GradientProjectionEngine(ProjectionEngine):
         if self.use_mse and not self.use_dssim:
             _lib.check(L.mgf_mse_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, per, tstride, 1.0, 0,
                                      self.scratch.data_ptr(), st), "mse")
+            if pair is not None:
+                self.mse_loss.add_(self.pair_mse_off)
         if opt_noise:
             dz = self.gg.backward_ws(self.dimg, dnoises=self.dnoises) if self.latent_space == "w+" else self.gg.backward(self.dimg, dnoises=self.dnoises)
         else:
@@ -1068,6 +1176,8 @@ class GradientProjectionEngine(ProjectionEngine):
         """Loop state back to step 0.  Like the latent and its Adam moments, the noise maps and theirs stay where the run left them; the
         best step's maps and the improvement flag's trail are cleared with the best-so-far they belong to."""
         super().rewind()
+        if getattr(self, "id_trace", None) is not None:
+            self.id_trace.fill_(float("nan"))
         if self.optimize_noise:
             self.best_noise_flat.zero_()
             self.noise_take.fill_(-1)
