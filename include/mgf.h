@@ -244,6 +244,18 @@ int mgf_tconv3x3s2_border_f32(float* t, const float* x, const float* wp, const f
                               int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t cout_pad, int64_t t_pitch, int64_t t_plane,
                               int64_t t_batch, int64_t out_scale_stride, mgf_stream_t stream);
 
+/* The up-sampling half of a synthesis block in ONE launch (csrc/tconv_blur.hip): the stride-2 transposed 3x3 conv above (border row and
+ * column included), the separable 4-tap blur with padding 1 that follows it, and the epilogue:
+ *   y[n, co, 0..2h-1, 0..2w-1] = epilogue( gain * blur4x4( tconv3x3s2( in_scale[n,ci] x ) * out_scale[n,co] ) )
+ * i.e. mgf_conv_taps_f32 (4-group mode) + mgf_tconv3x3s2_border_f32 + mgf_upfirdn2d(up 1, pad 1, separable) without the [2h+1, 2w+1]
+ * intermediate.  wp: the packed tap image of mgf_pack_conv_weights; f1d: the 4 taps of the 1-D filter whose outer product is the blur
+ * (device pointer); y [n, cout, 2h, y_pitch] with y_plane / y_batch elements between channels / samples.  Epilogue: noise (shared or
+ * per sample, device-side strength), bias, linear / leaky ReLU, gain; a residual is refused.  Any h, w >= 1; cin % 8 == 0 and
+ * cout % 32 == 0, MGF_EUNSUPPORTED otherwise.  float32 on v_mfma_f32_32x32x2_f32, deterministic, a sample's result independent of n. */
+int mgf_tconv3x3s2_blur_f32(float* y, const float* x, const float* wp, const float* in_scale, const float* out_scale, const float* f1d,
+                            float gain, int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t cout_pad, int64_t y_pitch,
+                            int64_t y_plane, int64_t y_batch, int64_t out_scale_stride, const mgf_epilogue* ep, mgf_stream_t stream);
+
 /* The stride-2 transposed 3x3 conv of mgf_conv_taps_f32's tconv launch (t[n, co, 2i+kh, 2j+kw] += w[kh,kw] x[n, ci, i, j], x scaled by
  * in_scale [n,cin] | NULL, the sum by out_scale | NULL) in polyphase Winograd form (csrc/wino_tconv.hip: 25 products per 2x2 input block
  * instead of 36).  Writes rows / columns 0 .. 2h-1 / 2w-1 of t [n, cout, 2h+1, pitch] (t_plane, t_batch elements between channels /

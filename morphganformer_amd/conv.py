@@ -541,6 +541,75 @@ def tconv3x3s2_forward(x, pc: PackedConv, in_scale=None, out_scale=None, out=Non
     return out[:, :, :, :ow]
 
 
+TCONV_BLUR = os.environ.get("MGF_TCONV_BLUR", "1") != "0"                 # 0 = transposed conv, border and blur as three launches
+# fewest workgroups the fused launch takes: it cuts its (sample, strip, channel tile, row step) list into at most 512 ranges, two per
+# CU, so 512 = "the launch fills the chip" (tools/tconv_blur_micro.py, profiles/tconv_blur_micro.txt); tests set it to 0 to force the
+# path on small generators
+TCONV_BLUR_MIN_WGS = 512
+# deepest input the fused launch takes.  What it saves (the blur's pass over t and y) grows with cout alone, what it costs (12.5 % more
+# matrix work for the halo columns of 256- and 512-wide maps, the extra step per strip and per workgroup) with cin * cout: at 32 samples
+# 64 -> 32 channels at 512^2 is 795 us faster than the three launches (4044 against 4839), 128 -> 64 at 256^2 is at parity (3473 against
+# 3501, inside the spread) and keeps them (profiles/tconv_blur_micro.txt)
+TCONV_BLUR_MAX_CIN = 64
+
+
+def tconv_blur_wgs(n, h, w, cout) -> int:
+    """Workgroups of the fused launch (csrc/tconv_blur.hip): one per range of row steps of 30-column strips, at most two per CU."""
+    return min(512, n * -(-w // 30) * (cout // 32) * ((2 * h + 2 + 15) // 16))
+
+
+def fir_factor(f2d: torch.Tensor):
+    """The 1-D taps a [4] of a 4x4 blur that is their outer product (setup_filter's result for 1-D taps), or None."""
+    f = f2d.detach().double().cpu()
+    if tuple(f.shape) != (4, 4) or not float(f[0, 0]) > 0:
+        return None
+    a = f[:, 0] / f[0, 0].sqrt()
+    if not torch.allclose(torch.outer(a, a), f, rtol=1e-6, atol=0):
+        return None
+    return a.float().to(f2d.device)
+
+
+def tconv_blur_ok(n, cin, h, w, cout, out, f1d, epilogue=None, bf=None) -> bool:
+    """The fused transposed conv + blur launch (csrc/tconv_blur.hip) serves float32 calls with whole 8-channel chunks and 32-channel tiles,
+    a separable 4-tap filter, no residual, a leaky-ReLU slope in [0, 1], at most TCONV_BLUR_MAX_CIN input channels and at least TCONV_BLUR_MIN_WGS workgroups; the switches are
+    read at call time."""
+    if not TCONV_BLUR or bf is not None or f1d is None or cin % 8 != 0 or cout % 32 != 0 or cin > TCONV_BLUR_MAX_CIN:
+        return False
+    if epilogue is not None and (epilogue.residual or (epilogue.act == _lib.ACT_IDS["lrelu"] and not 0.0 <= epilogue.alpha <= 1.0)
+                                 or epilogue.act not in (0, _lib.ACT_IDS["linear"], _lib.ACT_IDS["lrelu"])):
+        return False
+    st = out.stride()
+    if out.dim() != 4 or st[3] != 1 or st[1] >= 1 << 28 or cin * h * w >= 1 << 28 or st[0] % 2 or st[1] % 2 or st[2] % 2 or out.data_ptr() % 8:
+        return False
+    return tconv_blur_wgs(n, h, w, cout) >= TCONV_BLUR_MIN_WGS
+
+
+def tconv3x3s2_blur_forward(x, pc: PackedConv, f1d, gain, in_scale=None, out_scale=None, epilogue=None, out=None, t=None, f2d=None,
+                            bf=None, wt=None):
+    """y = epilogue(gain * blur4x4(tconv3x3s2(in_scale x) * out_scale)), [n, cout, 2h, 2w]: the up-sampling half of a synthesis block.
+    One fused launch where tconv_blur_ok accepts; today's three launches through the workspace t [n, cout, 2h+1, pitch] (and the 2-D
+    filter f2d, the outer product of f1d) otherwise."""
+    _lib.require_gpu(x, pc.wp, in_scale, out_scale, out, f1d)
+    assert pc.kh == 3 and pc.kw == 3 and x.dtype == torch.float32 and x.is_contiguous()
+    n, cin, h, w = x.shape
+    if out is None:
+        out = torch.empty([n, pc.cout, 2 * h, 2 * w], dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == (n, pc.cout, 2 * h, 2 * w) and out.dtype == torch.float32
+    if tconv_blur_ok(n, cin, h, w, pc.cout, out, f1d, epilogue, bf):
+        sy = out.stride()
+        os_stride = 0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0
+        rc = _lib.lib().mgf_tconv3x3s2_blur_f32(out.data_ptr(), x.data_ptr(), pc.wp.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale),
+                                                f1d.data_ptr(), float(gain), n, cin, h, w, pc.cout, pc.cout_pad, sy[2], sy[1], sy[0],
+                                                os_stride, C.byref(epilogue) if epilogue is not None else None, _lib.stream_ptr())
+        if rc != -2:                                   # MGF_EUNSUPPORTED: the three launches below
+            _lib.check(rc, "tconv3x3s2_blur")
+            return out
+    if f2d is None:
+        f2d = torch.outer(f1d, f1d)
+    tt = tconv3x3s2_forward(x, pc, in_scale=in_scale, out_scale=out_scale, out=t, bf=bf, wt=wt)
+    return upfirdn_into(out, tt, f2d, up=1, pad=(1, 1, 1, 1), gain=gain, epilogue=epilogue, separable=True)
+
+
 def upfirdn_into(y, x, f2d, up=1, pad=(0, 0, 0, 0), gain=1.0, flip=False, epilogue=None, separable=False, down=1):
     """mgf_upfirdn2d on arbitrary-stride 4-D views (x may be the padded-pitch transposed-conv workspace).
     separable=True asserts that f2d is an outer product (every setup_filter([taps]) result is) -> MGF_FILTER_SEPARABLE hint."""

@@ -136,6 +136,7 @@ class SynthesisPlan:
         self.mapping_blob = t32(pack_mapping_params(sd, cfg))
         self.const = t32(f64("synthesis.b4.const"))
         self.fir = t32(f64(f"synthesis.b{cfg.block_resolutions[-1]}.resample_kernel"))
+        self.fir1 = cv.fir_factor(self.fir)         # its 1-D taps (None if it is no outer product): the fused transposed conv + blur launch
         # the resample filter every checkpoint of the reference has (networks.py:1113, resample_kernel = [1,3,3,1]): the form-3 Winograd
         # epilogue up-samples the resnet skip branch with it in place (hard-wired taps), any other filter keeps the separate FIR pass
         self.fir_is_1331 = bool(np.allclose(f64(f"synthesis.b{cfg.block_resolutions[-1]}.resample_kernel"),
@@ -716,7 +717,14 @@ class Generator:
                                 noise_n=noise_n, act="lrelu", alpha=0.2, gain=lp.act_gain, residual=residual)
         has_att = lp.attn is not None
         s, d = self._s(lp), self._d(lp)
-        if lp.kind == "tconv":
+        if (lp.kind == "tconv" and not has_att and self.taps is None and lp.pcb is None
+                and cv.tconv_blur_ok(n, x.shape[1], x.shape[2], x.shape[3], lp.cout, B[key], self.plan.fir1, ep)
+                and not (lp.wino_t is not None and cv.tconv_winograd_ok(n, x.shape[1], x.shape[2], x.shape[3], lp.cout, B["t"]))):
+            # transposed conv, its border, the blur and the epilogue in one launch (csrc/tconv_blur.hip): B["t"] is not touched; the
+            # deep-K layers that take the polyphase Winograd launch keep it
+            y = cv.tconv3x3s2_blur_forward(x, lp.pc, self.plan.fir1, 4.0, in_scale=s, out_scale=d, epilogue=ep, out=B[key], t=B["t"],
+                                           f2d=self.plan.fir, wt=lp.wino_t)
+        elif lp.kind == "tconv":
             t = cv.tconv3x3s2_forward(x, lp.pc, in_scale=s, out_scale=d, out=B["t"], bf=lp.pcb, wt=lp.wino_t)
             # plan.fir is the outer product of the 1-D resample kernel (networks.py:1113 / upfirdn2d.setup_filter): separable
             y = cv.upfirdn_into(B[key], t, self.plan.fir, up=1, pad=(1, 1, 1, 1), gain=4.0, epilogue=None if has_att else ep,
