@@ -462,6 +462,25 @@ int mgf_lpips_layer_f32(float* out, const float* f0, const float* f1_unit, const
 int mgf_lpips_stem_f32(float* pooled, const float* x, const float* w, const float* b, float* feat_out, const float* feat_ref,
                        const float* lin, float* out, int32_t n, int32_t h, int32_t w_in, int32_t accumulate, float* scratch,
                        mgf_stream_t stream);
+/* Spatial LPIPS: PNetLin.forward with spatial=True (lpips/networks_basic.py:20-24,75-76,85-87) returns a map instead of a number.
+ *   lpips_layer_map:    map[i,p] = sum_c lin[c] * (f0[i,c,p]/(|f0[i,:,p]|+1e-10) - f1_unit[.,c,p])^2, map: [n,hw] -- mgf_lpips_layer_f32 before its
+ *                       spatial mean: same operands, same limits, the same statements per pixel (identical images give an all-zero map exactly;
+ *                       a pixel whose channels are all zero gives a finite value); no scratch, one launch.
+ *   lpips_upsample_sum: out[i,y,x] (+)= sum_l bilinear(maps[l][i])(y,x), out: [n,H,H], maps[l]: [n,sides[l],sides[l]] -- upsample() of
+ *                       networks_basic.py:20-24 on every tap and the sum of :85-87 in one launch.  maps / sides are HOST arrays of ntaps <= 8
+ *                       device pointers / side lengths, handed to the kernel by value (no allocation, copy or sync: capturable).  Sampling is
+ *                       torch's nn.Upsample(scale_factor=H/side, mode='bilinear', align_corners=False) rule per axis, float32:
+ *                         r = (float)(1.0 / ((double)H / side));  s = max(r * (dst + 0.5f) - 0.5f, 0);  i0 = min((int)s, side - 1);
+ *                         i1 = min(i0 + 1, side - 1);  l1 = clamp(s - i0, 0, 1);  l0 = 1 - l1
+ *                       and a pixel's value is  acc = accumulate ? out : 0;  for l in tap order:
+ *                         acc += ly0 * (lx0 * m[y0][x0] + lx1 * m[y0][x1]) + ly1 * (lx0 * m[y1][x0] + lx1 * m[y1][x1])
+ *                       (the two parentheses, their weighted sum and the addition to acc are four statements; multiply-adds fuse inside a
+ *                       statement only).  Any H >= 1; rows
+ *                       whose length is no multiple of 4, or an `out` that is not 16-byte aligned, take scalar stores of the same values. */
+int mgf_lpips_layer_map_f32(float* map, const float* f0, const float* f1_unit, const float* lin, int32_t n, int32_t c, int64_t hw,
+                            int64_t f1_batch_stride, mgf_stream_t stream);
+int mgf_lpips_upsample_sum_f32(float* out, const float* const* maps, const int32_t* sides, int32_t ntaps, int32_t n, int32_t H,
+                               int32_t accumulate, mgf_stream_t stream);
 /* y = max over a ksize x ksize window (2 or 3), stride 2, floor mode: out = (in - ksize)/2 + 1
  * (torchvision vgg16 features[4,9,16,23]: MaxPool2d(2,2); alexnet features[2,5]: MaxPool2d(3,2)) */
 int mgf_maxpool_s2_floor_f32(float* y, const float* x, int32_t nc, int32_t in_h, int32_t in_w, int32_t ksize, mgf_stream_t stream);

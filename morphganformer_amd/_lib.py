@@ -124,7 +124,9 @@ _SIGS = {
     "mgf_lpips_unit_f32": (C.c_int, [vp, vp, i32, i32, i64, vp]),
     "mgf_lpips_layer_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, i64, i32, vp, vp]),
     "mgf_lpips_stem_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
-    "mgf_channel_affine_prelu_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, vp]),
+    "mgf_lpips_layer_map_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, i64, vp]),
+    "mgf_lpips_upsample_sum_f32": (C.c_int, [vp, C.POINTER(vp), C.POINTER(i32), i32, i32, i32, i32, vp]),
+    "mgf_channel_affine_prelu_f32":(C.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, vp]),
     "mgf_linear_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "mgf_resize_bilinear_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "mgf_spatial_mean_f32": (C.c_int, [vp, vp, i32, i64, vp]),

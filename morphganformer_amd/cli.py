@@ -8,6 +8,8 @@
                                               (1024_merge_morph_2.py:25-92)
     python -m morphganformer_amd.cli morph    ... --refine --image-a a.png --image-b b.png --biometric iresnet50 --id-balance 0.5
                                               (each blend descended against both subjects: <out>_a0.50_refined.mat / .png)
+    python -m morphganformer_amd.cli lpips-map --image-a a.png --image-b b.png --out maps/a_vs_b --lpips-backbone squeeze.pth
+                                              (where the two images differ: PNetLin(spatial=True), lpips/networks_basic.py:75-76; no model)
 
 `--gpus` pins the visible device like the scripts' CUDA_VISIBLE_DEVICES line.  The reference detects landmarks with dlib on the
 target and on every generated image; dlib is a closed third-party dependency, so `project` takes them from `--landmarks`
@@ -207,6 +209,8 @@ def build_parser():
     p.add_argument("--image", type=str, required=True)
     p.add_argument("--landmarks", type=str, default=None)
     p.add_argument("--path_to_gen", type=str, default="images/projection/")
+    p.add_argument("--lpips-map", action="store_true",
+                   help="also write <path_to_gen>/best_lpips_map.npy / .png: the spatial LPIPS map of the best latent's image against the target")
     _loop_arguments(p)
 
     q = sub.add_parser("morph-pairs", help="Project both images of every CSV pair and render their latent morph "
@@ -256,7 +260,38 @@ def build_parser():
                    help="facenet_pytorch's InceptionResnetV1 state dict (.pth / .npz) -- what the reference fetches with pretrained='vggface2'")
     e.add_argument("--biometric-random", action="store_true", help="seeded random embedder weights (smoke runs only)")
     e.add_argument("--gpus", type=str, default="0")
+    lm = sub.add_parser("lpips-map", help="The spatial LPIPS map of two image files (PNetLin(spatial=True)): <out>.npy (float32 [N,N]) and <out>.png "
+                                          "(gray, white = --vmax or the map's maximum); no model")
+    lm.add_argument("--image-a", type=str, required=True)
+    lm.add_argument("--image-b", type=str, required=True)
+    lm.add_argument("--out", type=str, required=True, help="output prefix")
+    lm.add_argument("--size", type=int, default=1024, help="both images are resized / centre-cropped to this side, like a projection target")
+    lm.add_argument("--net", type=str, default="squeeze", choices=["squeeze", "vgg", "alex"], help="LPIPS backbone")
+    lm.add_argument("--lpips-backbone", type=str, default=None, metavar="STATE_DICT")
+    lm.add_argument("--lpips-random-backbone", action="store_true")
+    lm.add_argument("--vmax", type=float, default=None, help="the map value drawn white (default: the map's maximum)")
+    lm.add_argument("--gpus", type=str, default="0")
     return ap
+
+
+def _lpips_map(a):
+    from . import drivers
+    from .lpips import PerceptualLoss, load_backbone_state
+    if a.lpips_backbone is None and not a.lpips_random_backbone:
+        raise SystemExit(f"{a.cmd}: the LPIPS term needs the torchvision backbone weights: --lpips-backbone <state dict> "
+                         "(or --no-lpips / --lpips-random-backbone)")
+    state = load_backbone_state(a.lpips_backbone) if a.lpips_backbone else None
+    if state is None:
+        print("WARNING: LPIPS runs on seeded random backbone weights (--lpips-random-backbone); the term is not a perceptual distance")
+    percept = PerceptualLoss(model="net-lin", net=a.net, spatial=True, use_gpu=True, device="cuda", backbone_state=state,
+                             allow_random_backbone=state is None)
+    img_a = drivers.image_transform(a.image_a, size=a.size, device="cuda")
+    img_b = drivers.image_transform(a.image_b, size=a.size, device="cuda")
+    m = drivers.lpips_map(percept, img_a, img_b)
+    for path in drivers.save_lpips_map(m, a.out, vmax=a.vmax):
+        print(path)
+    print(f"mean {float(m.mean()):.6f}  max {float(m.max()):.6f}")
+    return 0
 
 
 def _extract_facenet(a):
@@ -309,6 +344,8 @@ def main(argv=None):
         torch.cuda.set_device(int(os.environ["LOCAL_RANK"]))
     if a.cmd == "extract-facenet":                          # no generator involved
         return _extract_facenet(a)
+    if a.cmd == "lpips-map":                                # two image files, no generator
+        return _lpips_map(a)
     from . import drivers, loader
     from .projection import ProjectionArgs
 
@@ -350,8 +387,10 @@ def main(argv=None):
         state = load_backbone_state(a.lpips_backbone) if a.lpips_backbone else None
         if state is None:
             print("WARNING: LPIPS runs on seeded random backbone weights (--lpips-random-backbone); the term is not a perceptual distance")
-        percept = PerceptualLoss(model="net-lin", net=a.net, use_gpu=True, device=G.device, backbone_state=state,
-                                 allow_random_backbone=state is None)
+        percept = PerceptualLoss(model="net-lin", net=a.net, spatial=bool(getattr(a, "lpips_map", False)), use_gpu=True, device=G.device,
+                                 backbone_state=state, allow_random_backbone=state is None)
+    elif getattr(a, "lpips_map", False):
+        raise SystemExit(f"{a.cmd}: --lpips-map is the map of the LPIPS term: drop --no-lpips")
     biometric = None
     if a.biometric != "none":
         if a.biometric_weights is None and not a.biometric_random:
@@ -419,7 +458,7 @@ def main(argv=None):
     res = drivers.project_image(G, target, lm_t, lm_s, args=args, percept=percept, batch=a.batch, seed=a.seed,
                                 out_prefix=os.path.join(a.path_to_gen, stem), mode=a.mode, path_to_gen=a.path_to_gen,
                                 keep_images=a.keep_images, latent_space=space, biometric=biometric, gamma=a.gamma, use_mse=not a.no_mse, pipeline=None if a.pipeline < 0 else (bool(a.pipeline) and a.mode == "literal"),
-                                lbp_target=lbp_target, mdf=mdf, optimize_noise=a.optimize_noise, noise_init=a.noise_init)
+                                lbp_target=lbp_target, mdf=mdf, optimize_noise=a.optimize_noise, noise_init=a.noise_init, lpips_map=a.lpips_map)
     print(f"best step {res['step']}  loss {res['loss']:.6f}")
     return 0
 

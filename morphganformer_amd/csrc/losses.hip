@@ -71,13 +71,15 @@ __global__ __launch_bounds__(256) void mse_partial_kernel(float* scratch, const 
 // ONE sweep over HBM: each thread keeps its <= CPT channel values in registers, the squared norms meet in LDS in a fixed order
 // (bit-reproducible), then the registers are either written back unit-normalised (UNIT_OUT: the reference image's taps, once
 // per target) or compared with the stored unit-normalised reference taps and reduced to one partial per workgroup.
-template <int PXB, int CPT, bool UNIT_OUT, bool STATS = false>
+// MAP (spatial LPIPS, networks_basic.py:75-76): the per-pixel distance itself is the result -- the G lane groups' d meet in LDS, are added in
+// group order and lane group 0 stores one float per pixel to `stats` (here the [n][hw] map); no partial sums, no finish launch.
+template <int PXB, int CPT, bool UNIT_OUT, bool STATS = false, bool MAP = false>
 __global__ __launch_bounds__(256) void lpips_layer_kernel(float* scratch, float* unit_out, const float* f0, const float* f1u,
                                                            const float* lin, int c, int64_t hw, int64_t f1_stride, int nsamp, int nblk,
                                                            int xcd_per, float* stats) {
     constexpr int G = 256 / PXB;
     __shared__ float red[G][PXB];
-    __shared__ float redb[STATS ? G : 1][PXB], redc[STATS ? G : 1][PXB];      // STATS: the two other per-pixel sums the gradient needs
+    __shared__ float redb[(STATS || MAP) ? G : 1][PXB], redc[STATS ? G : 1][PXB];      // STATS: the two other per-pixel sums the gradient needs
     __shared__ float sm[4];
     const int px = threadIdx.x % PXB, grp = threadIdx.x / PXB;
     // work order: XCD b % 8 walks a contiguous item range with the SAMPLE as the fastest index -- the n candidates of a pixel block read
@@ -151,13 +153,24 @@ __global__ __launch_bounds__(256) void lpips_layer_kernel(float* scratch, float*
             so[0] = na; so[hw] = sb; so[2 * hw] = sc;
         }
     }
+    if (MAP) {
+        redb[grp][px] = d;
+        __syncthreads();
+        if (grp == 0 && valid) {
+            float sd = 0.f;
+#pragma unroll
+            for (int g = 0; g < G; ++g) sd += redb[g][px];
+            stats[(int64_t)nn * hw + i] = sd;
+        }
+        return;
+    }
     const float acc = block_sum_256(valid ? d : 0.f, sm);
     if (threadIdx.x == 0) scratch[(int64_t)nn * RED_BLOCKS + blk] = acc;
 }
 
 template <bool UNIT_OUT>
 int launch_lpips_layer(float* scratch, float* unit_out, const float* f0, const float* f1u, const float* lin, int n, int c, int64_t hw,
-                       int64_t f1_stride, hipStream_t st, int* grid_out, float* stats = nullptr) {
+                       int64_t f1_stride, hipStream_t st, int* grid_out, float* stats = nullptr, float* map = nullptr) {
     // 64 pixels per workgroup (256-byte segments) whenever that still yields >= 4 workgroups per CU, 16 for the small deep taps
     static const int pxb_env = [] { const char* e = mgf_knob("MGF_LPIPS_PXB"); return e ? atoi(e) : 0; }();      // tuning hook: 16 | 32 | 64
     // (re-tuned on buffer addressing, 32 x {128 @ 255^2, 256 @ 127^2, 384 @ 63^2, 512 @ 63^2}, us for 64 / 32 / 16-pixel blocks:
@@ -177,7 +190,10 @@ int launch_lpips_layer(float* scratch, float* unit_out, const float* f0, const f
     *grid_out = (int)grid64;
 #define MGF_LPIPS_LAUNCH(PXB, CPT)                                                                                                            \
     do {                                                                                                                                      \
-        if (!UNIT_OUT && stats)                                                                                                               \
+        if (!UNIT_OUT && map)                                                                                                                 \
+            hipLaunchKernelGGL((lpips_layer_kernel<PXB, CPT, false, false, true>), grid, dim3(256), 0, st, scratch, unit_out, f0, f1u, lin, c, \
+                               hw, f1_stride, n, (int)grid64, xcd_per, map);                                                                  \
+        else if (!UNIT_OUT && stats)                                                                                                          \
             hipLaunchKernelGGL((lpips_layer_kernel<PXB, CPT, false, true>), grid, dim3(256), 0, st, scratch, unit_out, f0, f1u, lin, c, hw,    \
                                f1_stride, n, (int)grid64, xcd_per, stats);                                                                    \
         else                                                                                                                                  \
@@ -554,6 +570,108 @@ extern "C" int mgf_lpips_finish_taps_f32(float* out, const float* scratch, int64
     for (int t = 0; t < ntaps; ++t) MGF_REQUIRE(nparts[t] >= 1 && nparts[t] <= RED_BLOCKS, MGF_EINVAL, "lpips_finish_taps: bad partial count");
     hipLaunchKernelGGL(finish_multi_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, out, scratch, set_stride_floats, ntaps, fs, accumulate);
     MGF_CHECK_LAUNCH("lpips_finish_taps");
+    return MGF_OK;
+}
+
+// ---- spatial LPIPS (PNetLin.forward with spatial=True, lpips/networks_basic.py:20-24,75-76,85-87): the per-pixel tap distance, and the taps'
+// maps up-sampled bilinearly to the image size and summed
+extern "C" int mgf_lpips_layer_map_f32(float* map, const float* f0, const float* f1_unit, const float* lin, int32_t n, int32_t c, int64_t hw,
+                                       int64_t f1_batch_stride, mgf_stream_t stream) {
+    MGF_REQUIRE(map && f0 && f1_unit && lin && n >= 1 && n <= 65535 && c >= 1 && hw >= 1, MGF_EINVAL, "lpips_layer_map: bad arguments");
+    int grid = 0;
+    const int rc = launch_lpips_layer<false>(nullptr, nullptr, f0, f1_unit, lin, n, c, hw, f1_batch_stride, (hipStream_t)stream, &grid, nullptr, map);
+    if (rc != MGF_OK) return rc;
+    MGF_CHECK_LAUNCH("lpips_layer_map");
+    return MGF_OK;
+}
+
+namespace {
+
+// the tap table travels in the kernel arguments (by value, like RegLevels of csrc/noise_opt.hip): nothing to allocate, copy or wait for
+struct UpTaps { const float* map[8]; int side[8]; float rscale[8]; };
+
+// torch's source index and weight of one axis (UpSample.h: area_pixel_compute_source_index + guard_index_and_lambda, align_corners=False)
+__device__ __forceinline__ void up_axis(float rscale, int dst, int side, int& i0, int& i1, float& l0, float& l1) {
+    float s = rscale * ((float)dst + 0.5f) - 0.5f;
+    s = s < 0.f ? 0.f : s;
+    i0 = min((int)s, side - 1);
+    i1 = min(i0 + 1, side - 1);
+    l1 = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
+    l0 = 1.f - l1;
+}
+
+// grid = (column blocks, H rows, n).  A thread owns 4 consecutive pixels of one output row (VEC: one 16-byte store; else -- H % 4 != 0 or an
+// unaligned `out` -- four guarded scalar stores of the same values); the row is uniform in a workgroup, so every tap's row indices and row
+// weights are scalars.  The tap loop is unrolled over the table, so the table never leaves the scalar registers.
+template <bool VEC>
+__global__ __launch_bounds__(256) void lpips_upsample_sum_kernel(float* __restrict__ out, UpTaps t, int ntaps, int H, int accumulate) {
+    const int x0 = 4 * (int)(blockIdx.x * 256 + threadIdx.x);
+    if (x0 >= H) return;
+    const int y = blockIdx.y;
+    float* o = out + ((int64_t)blockIdx.z * H + y) * H + x0;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (accumulate) {
+        if (VEC) {
+            const float4 p = *reinterpret_cast<const float4*>(o);
+            acc[0] = p.x; acc[1] = p.y; acc[2] = p.z; acc[3] = p.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x0 + k < H) acc[k] = o[k];
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < 8; ++l) {
+        if (l >= ntaps) break;
+        const int side = t.side[l];
+        const float rs = t.rscale[l];
+        const float* m = t.map[l] + (int64_t)blockIdx.z * side * side;
+        int ya, yb;
+        float ly0, ly1;
+        up_axis(rs, y, side, ya, yb, ly0, ly1);
+        const float* ra = m + (int64_t)ya * side;
+        const float* rb = m + (int64_t)yb * side;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int xa, xb;
+            float lx0, lx1;
+            up_axis(rs, min(x0 + k, H - 1), side, xa, xb, lx0, lx1);
+            const float top = lx0 * ra[xa] + lx1 * ra[xb];
+            const float bot = lx0 * rb[xa] + lx1 * rb[xb];
+            const float v = ly0 * top + ly1 * bot;
+            acc[k] += v;
+        }
+    }
+    if (VEC) {
+        *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x0 + k < H) o[k] = acc[k];
+    }
+}
+
+}  // namespace
+
+extern "C" int mgf_lpips_upsample_sum_f32(float* out, const float* const* maps, const int32_t* sides, int32_t ntaps, int32_t n, int32_t H,
+                                          int32_t accumulate, mgf_stream_t stream) {
+    MGF_REQUIRE(out && maps && sides && ntaps >= 1 && ntaps <= 8 && n >= 1 && n <= 65535 && H >= 1 && H <= 65535, MGF_EINVAL,
+                "lpips_upsample_sum: bad arguments (1..8 taps, n and H in 1..65535)");
+    UpTaps t;
+    for (int l = 0; l < 8; ++l) {
+        const bool on = l < ntaps;
+        MGF_REQUIRE(!on || (maps[l] && sides[l] >= 1 && sides[l] <= 32768), MGF_EINVAL, "lpips_upsample_sum: tap %d: bad map or side", l);
+        t.map[l] = on ? maps[l] : nullptr;
+        t.side[l] = on ? sides[l] : 1;
+        // torch keeps the scale factor it was given: the source step is 1 / (H / side), rounded to float (UpSample.h compute_scales_value)
+        t.rscale[l] = on ? (float)(1.0 / ((double)H / (double)sides[l])) : 0.f;
+    }
+    const dim3 grid((unsigned)mgf_cdiv(mgf_cdiv(H, 4), 256), (unsigned)H, (unsigned)n);
+    if (H % 4 == 0 && ((uintptr_t)out & 15) == 0)
+        hipLaunchKernelGGL(lpips_upsample_sum_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, out, t, ntaps, H, accumulate);
+    else
+        hipLaunchKernelGGL(lpips_upsample_sum_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, out, t, ntaps, H, accumulate);
+    MGF_CHECK_LAUNCH("lpips_upsample_sum");
     return MGF_OK;
 }
 

@@ -7,6 +7,8 @@
                     BASELINE config 4 sweeps 11 values)
   refine_morph      the blend descended against BOTH contributing subjects (gradient mode with a target pair; no reference script)
   project_image     latent statistics + one ProjectionEngine run + best-of PNG / .mat   (:135-208, :246-268)
+  lpips_map / save_lpips_map    the spatial LPIPS map of an image against a target (PNetLin(spatial=True), lpips/networks_basic.py:75-76) and its
+                    .npy / gray .png files
   second_stage      a projection initialised from an earlier result (edit_MSE.py pattern, BASELINE config 5)
   warp_morph        landmark-Delaunay warp of a morph onto the averaged landmarks (1024_warp_morphs.py:78-113,163-210)
 
@@ -294,6 +296,40 @@ def merge_files(src_path, dst_path):
     return out
 
 
+def lpips_map(percept, img, target):
+    """Where `img` departs from `target`: the [N,1,H,W] map of a lpips.PerceptualLoss(spatial=True) (PNetLin.forward with spatial=True,
+    lpips/networks_basic.py:75-76,85-87).  img: [N,3,H,H] in [-1,1]; target: [1,3,H,H] (shared) or [N,3,H,H]."""
+    if percept is None or not getattr(percept, "spatial", False):
+        raise ValueError("lpips_map needs a lpips.PerceptualLoss built with spatial=True")
+    return percept(img, target)
+
+
+def save_lpips_map(map, path, vmax=None):
+    """`path + '.npy'`: the map as float32 [H,W]; `path + '.png'`: gray uint8 round(255 * min(map / vmax, 1)), vmax = the map's maximum
+    unless given (an all-zero map gives an all-zero PNG).  map: [1,1,H,W] / [H,W], tensor or array.  Returns the two paths."""
+    from PIL import Image
+    m = np.asarray(map.detach().cpu() if isinstance(map, torch.Tensor) else map, dtype=np.float32)
+    m = m.reshape(m.shape[-2], m.shape[-1])
+    top = float(m.max()) if vmax is None else float(vmax)
+    scaled = np.minimum(m.astype(np.float64) / top, 1.0) if top > 0 else np.zeros(m.shape)
+    u8 = np.clip(np.rint(255.0 * scaled), 0, 255).astype(np.uint8)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.save(path + ".npy", m)
+    Image.fromarray(u8).save(path + ".png")
+    return path + ".npy", path + ".png"
+
+
+def _best_lpips_map(G, percept, w, target, noises):
+    """The map of the best latent's image -- rendered as projection.save_best_png renders it -- against the target."""
+    w = w.to(G.device)
+    mode = "inject" if noises is not None else "const"
+    if w.ndim == 4:
+        img = G.forward_workspace(ws=w, noise_mode=mode, noises=noises)[0]
+    else:
+        img = G.forward_workspace(w, None, noise_mode=mode, noises=noises)[0]
+    return lpips_map(percept, img.float(), target)[0, 0]
+
+
 DEFAULT_BATCH = 32       # loop steps per generator forward in literal mode: the configuration bench.py times (1.6 GB of activations per step at 1024^2;
                          # measured 20 .. 64: 32 is the fastest, 25 -- the round-2 figure -- 1.5 - 3 % behind)
 
@@ -302,7 +338,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                   eps=None, out_prefix=None, batch=DEFAULT_BATCH, use_graph=True, noise_mode="random", use_mse=True, seed=None,
                   landmark_fn=None, mode="literal", weight_decay=0.0, path_to_gen=None, keep_images=64, engine=None,
                   return_engine=False, latent_space="z", landmark_input="float", biometric=None, gamma=1.0, lbp_target=None, pipeline=None,
-                  mdf=None, optimize_noise=False, noise_init="randn"):
+                  mdf=None, optimize_noise=False, noise_init="randn", lpips_map=False):
     """One full `projection(...)` call (:135-208).  `target`: [1,3,S,S] from image_transform; `lm_target` [68,2] and either
     `lm_steps` [steps,68,2] (injected landmark detections) or `landmark_fn` (host detector called on every generated image,
     see ProjectionEngine; landmark_input="gray_u8" hands it the drivers' gray uint8 image, built on the device).  mode="literal" is the loop as the reference executes it (best-of-N noisy sampling, `batch` steps per
@@ -335,6 +371,11 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     Adam + noise_normalize_, args.noise_regularize * the regulariser in the total).  The result gains `noises`, the maps of the best step's image;
     the PNG is rendered with them -- the scored image -- and the .mat holds them beside 'w' (noise_mat_key).
 
+    lpips_map: with a spatial perceptual term (lpips.PerceptualLoss(spatial=True); the engines score with it exactly as with a non-spatial one)
+    the result gains `lpips_map` [H,W]: where the best latent's image -- G(best latent, noise_mode="const"), or with optimize_noise the best
+    step's maps, as the saved PNG is rendered -- departs from the target; with `path_to_gen` it is also written there as
+    best_lpips_map.npy / .png (save_lpips_map).
+
     engine: a ProjectionEngine from an earlier call with the same generator, objective, step count and batch (return_engine=True
     hands it out) -- it is re-targeted in place (`ProjectionEngine.retarget`), which keeps its captured hipGraph and workspaces; this is
     how `project_many` walks a list of targets."""
@@ -347,6 +388,11 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
         raise ValueError("latent_space must be 'z', or 'w+' together with mode='gradient'")
     if optimize_noise and mode != "gradient":
         raise ValueError("optimize_noise needs mode='gradient' (the literal loop never back-propagates)")
+    if lpips_map and (percept is None or not getattr(percept, "spatial", False)):
+        raise ValueError("lpips_map=True needs a perceptual term that returns maps: percept=lpips.PerceptualLoss(spatial=True)")
+    if lpips_map and tuple(target.shape[2:]) != (G.img_resolution, G.img_resolution):
+        raise ValueError(f"lpips_map=True: the target is {tuple(target.shape[2:])}, the generated image {G.img_resolution}x{G.img_resolution} "
+                         "(args.pool_above): the map is defined at the image's own size")
     if latent_mean is None or latent_std is None:
         gen = None
         if seed is not None:
@@ -398,6 +444,10 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
         else:
             from .projection import save_best_png
             out["images"] = [save_best_png(G, w, os.path.join(path_to_gen, "{:06d}_{:04f}.png".format(step, loss)), args.ratio, noises=best_noises)]
+    if lpips_map:
+        out["lpips_map"] = _best_lpips_map(G, percept, w, target, best_noises)
+        if path_to_gen is not None:
+            out["lpips_map_files"] = save_lpips_map(out["lpips_map"], os.path.join(path_to_gen, "best_lpips_map"))
     if return_engine:
         out["engine"] = eng
     return out

@@ -495,8 +495,15 @@ class SqueezeFeatures:
         return taps
 
 
+def spatial_tap_output_side(h, H):
+    """Side of a tap map of side h after the reference's `upsample(..., out_H=H)` (networks_basic.py:20-24): it hands torch the scale factor
+    1. * H / h, and torch sizes the output floor(h * scale) in double -- which is not always H (47 * (96 / 47) floors to 95)."""
+    return int(math.floor(float(h) * (1.0 * H / h)))
+
+
 class PerceptualLoss(torch.nn.Module):
-    """lpips.PerceptualLoss(model='net-lin', net='squeeze', use_gpu=True)(pred, target, normalize=False) -> [N,1,1,1]."""
+    """lpips.PerceptualLoss(model='net-lin', net='squeeze', use_gpu=True)(pred, target, normalize=False) -> [N,1,1,1];
+    with spatial=True -> the [N,1,H,W] map of PNetLin(spatial=True) (networks_basic.py:75-76,85-92; `distance_map_into`)."""
 
     def __init__(self, model="net-lin", net="squeeze", colorspace="rgb", spatial=False, use_gpu=True, gpu_ids=(0,),
                  backbone_state=None, backbone_seed=None, allow_random_backbone=False, device="cuda"):
@@ -506,8 +513,9 @@ class PerceptualLoss(torch.nn.Module):
         backbone (allow_random_backbone=True or an explicit backbone_seed: benchmarks and parity tests, where only the arithmetic
         matters)."""
         super().__init__()
-        if model != "net-lin" or spatial or colorspace != "rgb":
-            raise NotImplementedError("the MI355X path implements model='net-lin', spatial=False, colorspace='rgb'")
+        if model != "net-lin" or colorspace != "rgb":
+            raise NotImplementedError("the MI355X path implements model='net-lin', colorspace='rgb'")
+        self.spatial = bool(spatial)
         if net not in NET_CHNS:
             raise NotImplementedError(f"unknown LPIPS backbone {net!r} (squeeze, vgg, alex)")
         if not use_gpu:
@@ -530,6 +538,8 @@ class PerceptualLoss(torch.nn.Module):
         self.lins = [torch.as_tensor(lin[f"lin{i}"], dtype=torch.float32, device=self.device_) for i in range(len(self.chns))]
         self._feats = {}
         self._stats = {}
+        self._map_ws = {}                 # (n, H) -> per-tap maps of distance_map_into (spatial=True)
+        self._map_taps = None             # spatial=True beside the fused stem: the target's unit taps through the un-fused path
         self._target_taps = None
         self._target_n = 1
         self.pair_offset = None           # [B] float32 = alpha (1 - alpha) LPIPS(Ta, Tb) while a target pair is set (set_target_pair)
@@ -578,6 +588,17 @@ class PerceptualLoss(torch.nn.Module):
             if i == 0 and self.fused_stem and n == 1:
                 continue                            # the stem already wrote tap 0 normalised
             _lib.check(L.mgf_lpips_unit_f32(t.data_ptr(), t.data_ptr(), n, t.shape[1], t.shape[2] * t.shape[3], st), "lpips_unit")
+        if self.spatial and self.fused_stem and n == 1:
+            # the map takes the un-fused path (the stem never writes tap 0), so its target taps come from the un-fused path too: the SAME
+            # kernels run on both images and identical images give an all-zero map exactly (outs, behind the stem, stay what distance_into reads)
+            mt = self._map_taps
+            if mt is None or [t.shape for t in mt] != [t.shape for t in outs]:
+                mt = self._map_taps = [torch.empty_like(t) for t in outs]
+            f(target.float(), out=mt)
+            for t in mt:
+                _lib.check(L.mgf_lpips_unit_f32(t.data_ptr(), t.data_ptr(), n, t.shape[1], t.shape[2] * t.shape[3], st), "lpips_unit")
+        else:
+            self._map_taps = None
         self._target_taps = outs
         self.pair_offset = None                     # a single target again: no constant to add (set_target_pair sets it afterwards)
 
@@ -703,11 +724,91 @@ class PerceptualLoss(torch.nn.Module):
                                                    c * hh * ww if per_sample else 0, 0, self._scratch.data_ptr(), st), "lpips_layer")
         return out
 
-    def forward(self, pred, target, normalize=False):
+    @staticmethod
+    def _require_square(H, W):
+        if H != W:
+            raise _lib.MgfError(f"PerceptualLoss(spatial=True): the image must be square (got {H}x{W}): the reference derives ONE scale factor from "
+                                "the height and its tap maps then disagree in width")
+
+    def _map_workspace(self, n, H, f):
+        """Per-tap maps [n, h_l, h_l] for n images of side H (cached like `_stats`), after the size checks of spatial mode."""
+        ws = self._map_ws.get((n, H))
+        if ws is None:
+            keys = TAPS_AFTER if self.net == "squeeze" else range(len(self.chns))
+            sides = []
+            for l, idx in enumerate(keys):
+                _, hh, ww = f.shapes[idx]
+                got = spatial_tap_output_side(hh, H)
+                if hh != ww or got != H:
+                    raise _lib.MgfError(f"PerceptualLoss(spatial=True, net={self.net!r}): tap {l} ({hh}x{ww}) up-samples to side {got}, not to the "
+                                        f"image's {H} (the reference's own sum of the tap maps fails at this size)")
+                sides.append(hh)
+            ws = self._map_ws[(n, H)] = [torch.empty(n, s, s, dtype=torch.float32, device=self.device_) for s in sides]
+        return ws
+
+    def _upsample_sum(self, out, maps, accumulate=False):
+        import ctypes as C
+        n, H = out.shape[0], out.shape[-1]
+        ptrs = (C.c_void_p * 8)(*[m.data_ptr() for m in maps])
+        sides = (C.c_int32 * 8)(*[m.shape[-1] for m in maps])
+        _lib.check(_lib.lib().mgf_lpips_upsample_sum_f32(out.data_ptr(), ptrs, sides, len(maps), n, H, int(accumulate), _lib.stream_ptr()),
+                   "lpips_upsample_sum")
+        return out
+
+    def distance_map_into(self, out, pred, per_tap=None):
+        """out[i,0,y,x] = sum over taps of the tap's per-pixel weighted distance between pred[i] and the cached target (`set_target`: one
+        target for every candidate, or n targets for n candidates, as in `distance_into`), up-sampled bilinearly to the image size -- what
+        PNetLin.forward returns with spatial=True (networks_basic.py:20-24,75-76,85-87).  pred: [n,3,H,H]; out: float32 [n,1,H,H].
+        per_tap: a list of [n,1,H,H] tensors, one per tap, that receive every tap's own up-sampled map.  The un-fused path: every tap is in the
+        workspace, as with keep_taps=True; the per-tap maps are cached per (n, H), nothing is allocated per call."""
+        if not self.spatial:
+            raise _lib.MgfError("distance_map_into: this PerceptualLoss was built with spatial=False")
+        _lib.require_gpu(out, pred)
+        n, _, H, W = pred.shape
+        self._require_square(H, W)
+        assert self._target_taps is not None, "call set_target first"
+        if self.pair_offset is not None:
+            raise _lib.MgfError("distance_map_into: a target pair is set (set_target_pair); the map is defined against one target")
+        per_sample = self._target_n > 1
+        assert not per_sample or self._target_n == n, f"{self._target_n} targets cannot pair with {n} candidates"
+        assert tuple(out.shape) == (n, 1, H, H) and out.dtype == torch.float32 and out.is_contiguous(), "out: contiguous float32 [n,1,H,H]"
+        f = self._features(n, H, W)
+        maps = self._map_workspace(n, H, f)
+        self._last, self._last_hw = None, None
+        f.tap_stats = {}
+        taps = f(pred.float())
+        L, st = _lib.lib(), _lib.stream_ptr()
+        targets = self._target_taps if self._map_taps is None else self._map_taps
+        for a, b, lin, m in zip(taps, targets, self.lins, maps):
+            _, c, hh, ww = a.shape
+            _lib.check(L.mgf_lpips_layer_map_f32(m.data_ptr(), a.data_ptr(), b.data_ptr(), lin.data_ptr(), n, c, hh * ww,
+                                                 c * hh * ww if per_sample else 0, st), "lpips_layer_map")
+        self._upsample_sum(out, maps)
+        if per_tap is not None:
+            assert len(per_tap) == len(maps)
+            for o, m in zip(per_tap, maps):
+                assert tuple(o.shape) == (n, 1, H, H) and o.dtype == torch.float32 and o.is_contiguous()
+                self._upsample_sum(o, [m])
+        return out
+
+    def forward(self, pred, target, normalize=False, retPerLayer=False):
+        """spatial=False: [N,1,1,1].  spatial=True: the float32 [N,1,H,W] map, and with retPerLayer=True (val, [per-tap up-sampled maps]).
+        The list is un-aliased: every entry is a tap's own map.  In the reference, `val = res[0]` followed by the in-place `val += res[l]`
+        (networks_basic.py:85-87) makes res[0] the running total, not tap 0's map."""
         _lib.require_gpu(pred, target)
         if normalize:
             target, pred = 2 * target - 1, 2 * pred - 1
         n = pred.shape[0]
+        if self.spatial:
+            H, W = pred.shape[2:]
+            self._require_square(H, W)
+            self.set_target(target.float().contiguous())          # n targets for n images, or one for all of them
+            val = torch.empty(n, 1, H, W, dtype=torch.float32, device=self.device_)
+            res = [torch.empty_like(val) for _ in self.lins] if retPerLayer else None
+            self.distance_map_into(val, pred.float().contiguous(), per_tap=res)
+            return (val, res) if retPerLayer else val
+        if retPerLayer:
+            raise NotImplementedError("retPerLayer=True is implemented for spatial=True; `distance_per_tap` returns the per-tap values otherwise")
         vals = []
         for i in range(n):      # per-sample values like the reference's [N,1,1,1]; the loop only ever uses N == 1
             # like the reference, the module-call form recomputes the target features on every call; the projection
