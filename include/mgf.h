@@ -727,6 +727,33 @@ int mgf_maxpool_s2_floor_bwd_f32(float* dx, const float* dy, const float* x, int
 int mgf_mse_grad_f32(float* d, const float* a, const float* b, int32_t n, int64_t numel, int64_t b_batch_stride, float scale,
                      int32_t accumulate, mgf_stream_t stream);
 
+/* Region-weighted image-space terms.  wmap holds NORMALISED per-pixel weights omega >= 0 ([hw] floats per map, w_batch_stride elements
+ * between the samples' maps, 0 = one map shared by all samples): the caller forms them once per (weight, geometry) -- for a tap
+ * omega = W_l / sum(W_l) with W_l the region weight pooled to the tap's grid, for pixels omega = W / (C * sum(W)) -- and the kernels
+ * only multiply.  omega = 1 / hw (taps) resp. 1 / (c * hw) (pixels) gives the un-weighted terms.
+ *   lpips_layer_defer_weighted: mgf_lpips_layer_defer_f32 whose partial sums are of omega[p] * d[p] (each lane loads its pixel's weight
+ *                      once; same two-stage order, no float atomics); `stats` does not depend on the weight and is written as by the
+ *                      un-weighted entry; finished by mgf_lpips_finish_taps_f32 with scale 1
+ *   lpips_layer_bwd_weighted / lpips_layer_bwd_relu_stats_weighted: the gradient of scale * sum_p omega[p] * d[p]: the un-weighted entries
+ *                      with the factor 2 scale / hw replaced by 2 scale omega[p]; a pixel with omega = 0 gets a gradient of exactly 0
+ *                      (with dy: dy through the ReLU mask, unchanged).  dy NULL / stats NULL / dz_b NULL as in the un-weighted entries.
+ *   mse_weighted:      out[i] (+)= scale * sum_c sum_p omega[p] (a[i,c,p] - b[i,c,p])^2, a [n,c,hw], b samples b_batch_stride apart
+ *                      (0 = shared), deterministic two-stage reduction through `scratch` (>= n * mgf_reduce_scratch_floats() floats)
+ *   mse_weighted_grad: d (+)= scale * 2 omega[p] (a - b) */
+int mgf_lpips_layer_defer_weighted_f32(float* scratch, float* stats, const float* f0, const float* f1_unit, const float* lin, const float* wmap,
+                                       int32_t n, int32_t c, int64_t hw, int64_t f1_batch_stride, int64_t w_batch_stride, int32_t* nparts_out,
+                                       mgf_stream_t stream);
+int mgf_lpips_layer_bwd_weighted_f32(float* df0, const float* f0, const float* f1_unit, const float* lin, const float* wmap, int32_t n, int32_t c,
+                                     int64_t hw, int64_t f1_batch_stride, int64_t w_batch_stride, float scale, int32_t accumulate,
+                                     mgf_stream_t stream);
+int mgf_lpips_layer_bwd_relu_stats_weighted_f32(float* dz_a, float* dz_b, const float* dy, const float* f0, const float* f1_unit, const float* lin,
+                                                const float* stats, const float* wmap, int32_t n, int32_t c, int32_t c_split, int64_t hw,
+                                                int64_t f1_batch_stride, int64_t w_batch_stride, float scale, mgf_stream_t stream);
+int mgf_mse_weighted_f32(float* out, const float* a, const float* b, const float* wmap, int32_t n, int32_t c, int64_t hw, int64_t b_batch_stride,
+                         int64_t w_batch_stride, float scale, int32_t accumulate, float* scratch, mgf_stream_t stream);
+int mgf_mse_weighted_grad_f32(float* d, const float* a, const float* b, const float* wmap, int32_t n, int32_t c, int64_t hw,
+                              int64_t b_batch_stride, int64_t w_batch_stride, float scale, int32_t accumulate, mgf_stream_t stream);
+
 /* Gradient mode of the biometric branch (autograd through backbones/iresnet.py:46-58,145-160 and F.interpolate); its convolution
  * gradients are mgf_conv_taps_f32 launches on transposed taps, BatchNorm gradients are mgf_channel_affine_prelu_f32 with the scale only.
  *   prelu_bwd:           dx = dy * (y > 0 ? 1 : slope[c]) from the PReLU OUTPUT y -- needs positive slopes (sign(y) = sign(input))

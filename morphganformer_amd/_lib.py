@@ -174,6 +174,11 @@ _SIGS = {
     "mgf_maxpool3x3s2_ceil_bwd_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "mgf_maxpool_s2_floor_bwd_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "mgf_mse_grad_f32": (C.c_int, [vp, vp, vp, i32, i64, i64, f32, i32, vp]),
+    "mgf_lpips_layer_defer_weighted_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i64, i64, i64, C.POINTER(i32), vp]),
+    "mgf_lpips_layer_bwd_weighted_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, i64, i64, f32, i32, vp]),
+    "mgf_lpips_layer_bwd_relu_stats_weighted_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, f32, vp]),
+    "mgf_mse_weighted_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, i64, i64, f32, i32, vp, vp]),
+    "mgf_mse_weighted_grad_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, i64, i64, f32, i32, vp]),
     "mgf_prelu_bwd_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, vp]),
     "mgf_linear_bwd_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
     "mgf_resize_bilinear_bwd_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -138,6 +138,8 @@ def _refine_arguments(m):
     m.add_argument("--biometric-weights", type=str, default=None, metavar="STATE_DICT")
     m.add_argument("--biometric-random", action="store_true")
     m.add_argument("--seed", type=int, default=None)
+    m.add_argument("--region-weight", type=str, default=None, metavar="FILE",
+                   help="--refine: weight the LPIPS and pixel terms by region (a .npy float [S,S] map >= 0, or a gray image scaled to [0,1])")
 
 
 def _refine(a, G, alphas):
@@ -185,7 +187,8 @@ def _refine(a, G, alphas):
     tb = drivers.image_transform(a.image_b, size=a.size, device=G.device)
     res = drivers.refine_morph(G, w1, w2, ta, tb, alphas, lockstep=not a.no_lockstep, args=args, percept=percept, biometric=biometric,
                                gamma=a.gamma, id_balance=a.id_balance, id_metric=a.id_metric, seed=a.seed, use_mse=not a.no_mse,
-                               out_prefix=a.out, ratio=a.ratio)
+                               out_prefix=a.out, ratio=a.ratio,
+                               region_weight=None if a.region_weight is None else drivers.load_region_weight(a.region_weight))
     for r in res:
         ids = "" if r["id_distances"] is None else "  d_a {:.6f}  d_b {:.6f}".format(*r["id_distances"])
         print(f"alpha {r['alpha']:.2f}: best step {r['best_step']}  loss {r['best_loss']:.6f} (start {r['losses'][0]:.6f}){ids}")
@@ -211,6 +214,12 @@ def build_parser():
     p.add_argument("--path_to_gen", type=str, default="images/projection/")
     p.add_argument("--lpips-map", action="store_true",
                    help="also write <path_to_gen>/best_lpips_map.npy / .png: the spatial LPIPS map of the best latent's image against the target")
+    p.add_argument("--region-weight", type=str, default=None, metavar="FILE",
+                   help="weight the LPIPS and pixel terms by region: a .npy float [H,W] map >= 0, or a gray image scaled to [0,1], at the size the "
+                        "image-space losses see")
+    p.add_argument("--region-from-landmarks", type=str, default=None, metavar="INSIDE,OUTSIDE[,FEATHER]",
+                   help="the region weight from the target row of --landmarks: INSIDE on the landmarks' convex hull, OUTSIDE elsewhere, the edge "
+                        "blurred with a Gaussian of FEATHER pixels (drivers.face_region_weight)")
     _loop_arguments(p)
 
     q = sub.add_parser("morph-pairs", help="Project both images of every CSV pair and render their latent morph "
@@ -325,8 +334,28 @@ def mdf_options(a):
     return dict(num_scales=a.mdf_scales, is_ascending=0 if a.mdf_descending else 1, differentiable=a.mode == "gradient")
 
 
+def region_arguments(a):
+    """Checks of `project`'s two region options (before anything is loaded) -> None, ("file", path) or ("landmarks", inside, outside, feather)."""
+    if a.cmd != "project" or (a.region_weight is None and a.region_from_landmarks is None):
+        return None
+    if a.region_weight is not None and a.region_from_landmarks is not None:
+        raise SystemExit("project: --region-weight and --region-from-landmarks both define the region weight: pass one of them")
+    if a.region_weight is not None:
+        return ("file", a.region_weight)
+    if not a.landmarks:
+        raise SystemExit("project: --region-from-landmarks takes the hull of the target's landmarks: it needs --landmarks")
+    try:
+        vals = [float(v) for v in a.region_from_landmarks.split(",")]
+    except ValueError:
+        vals = []
+    if len(vals) not in (2, 3) or min(vals) < 0 or max(vals[:2]) <= 0:
+        raise SystemExit(f"project: --region-from-landmarks takes INSIDE,OUTSIDE[,FEATHER], all >= 0 and not both weights zero (got {a.region_from_landmarks!r})")
+    return ("landmarks", vals[0], vals[1], vals[2] if len(vals) == 3 else 0.0)
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    region = region_arguments(a)
     if a.cmd == "merge-files":                              # file bookkeeping only (1024_merge_files.py): no generator, no GPU
         from . import drivers
         files = drivers.merge_files(a.src, a.dst)
@@ -448,6 +477,11 @@ def main(argv=None):
         lm_t, lm_s = lm["target"], lm["steps"]
         if lm_s.shape[0] < a.step:
             raise SystemExit(f"--landmarks holds {lm_s.shape[0]} steps, --step is {a.step}")
+    region_weight = None
+    if region is not None and region[0] == "file":
+        region_weight = drivers.load_region_weight(region[1])
+    elif region is not None:             # the landmarks are in the pixels of the --size image; the weight is at the size the losses see
+        region_weight = drivers.face_region_weight(np.asarray(lm_t, dtype=np.float64) * (tsize / a.size), tsize, *region[1:])
     stem = os.path.splitext(os.path.basename(a.image))[0]
     lbp_target = None
     if a.pixel_term == "lbp":          # LBP_feature(path): the file's own pixels (1024_example_LBP_percept.py:40-45,140); min_distance starts at 1 (:151)
@@ -458,7 +492,8 @@ def main(argv=None):
     res = drivers.project_image(G, target, lm_t, lm_s, args=args, percept=percept, batch=a.batch, seed=a.seed,
                                 out_prefix=os.path.join(a.path_to_gen, stem), mode=a.mode, path_to_gen=a.path_to_gen,
                                 keep_images=a.keep_images, latent_space=space, biometric=biometric, gamma=a.gamma, use_mse=not a.no_mse, pipeline=None if a.pipeline < 0 else (bool(a.pipeline) and a.mode == "literal"),
-                                lbp_target=lbp_target, mdf=mdf, optimize_noise=a.optimize_noise, noise_init=a.noise_init, lpips_map=a.lpips_map)
+                                lbp_target=lbp_target, mdf=mdf, optimize_noise=a.optimize_noise, noise_init=a.noise_init, lpips_map=a.lpips_map,
+                                region_weight=region_weight)
     print(f"best step {res['step']}  loss {res['loss']:.6f}")
     return 0
 

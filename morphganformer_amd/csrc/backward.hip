@@ -827,10 +827,12 @@ __global__ __launch_bounds__(256) void latent_grad_gather_kernel(float* dw, cons
 // CPT > 0: c <= CPT * (256 / PXB), and the lane keeps its CPT channels of f0 and f1 in registers between the two sweeps: 629 -> 588 us
 // at 8 x 64 x 511^2 with 16 channels per lane; with 32 (128 channels) the registers cost more residency than the second sweep's
 // mostly cache-resident reads (321 -> 435 us), so only CPT = 16 is built.  Wider pixel blocks (128, 256) measured no faster than 64.
-template <int PXB, bool RELU, int CPT>
+// WEIGHTED (region weights): l = scale * sum_p omega[p] sum_c ..., so k = 2 scale omega[p] per pixel -- the host passes 2 scale and every lane
+// multiplies by its pixel's weight (one more buffer load); omega = 0 gives g = 0 exactly, i.e. din through the ReLU mask.
+template <int PXB, bool RELU, int CPT, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void lpips_layer_bwd_kernel(float* oa, float* ob, const float* din, const float* f0, const float* f1u,
                                                               const float* lin, int c, int c_split, int64_t hw, int64_t f1_bs, float k,
-                                                              int accumulate, const float* stats) {
+                                                              int accumulate, const float* stats, const float* wmap, int64_t w_bs) {
     // a workgroup owns PXB consecutive pixels; its G = 256 / PXB lane groups split the channels and meet in LDS
     constexpr int G = 256 / PXB;
     constexpr int NV = CPT > 0 ? CPT : 1;
@@ -853,6 +855,10 @@ __global__ __launch_bounds__(256) void lpips_layer_bwd_kernel(float* oa, float* 
     };
     auto ldlin = [&](int j) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, 4u * (unsigned)grp, 4 * j * G, 0)); };
     const int nj = (c + G - 1) / G;                   // channel steps (a lane whose channel of the last step is past c reads zeros)
+    if (WEIGHTED) {
+        const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(wmap + (int64_t)n * w_bs), 0, (int)plane_b, 0x00020000);
+        k *= __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, 4u * (unsigned)pc, 0, 0));
+    }
     float va[NV], vb[NV];
     float A = 0.f, B = 0.f, Cc = 0.f;
     // stats: the per-pixel sums A, B, C of the forward (mgf_lpips_layer_stats_f32, [n][3][hw]) -- no first sweep, no meeting in LDS
@@ -1519,13 +1525,22 @@ extern "C" int mgf_latent_grad_gather(float* dw, const float* dwg, int32_t n_sty
 // MGF_LPIPS_BWD_CACHE=0 turns the register-resident second sweep off (tuning).
 template <bool RELU>
 static void lpips_bwd_launch(float* oa, float* ob, const float* din, const float* f0, const float* f1u, const float* lin, int n, int c,
-                             int c_split, int64_t hw, int64_t f1_bs, float k, int accumulate, hipStream_t st, const float* stats = nullptr) {
+                             int c_split, int64_t hw, int64_t f1_bs, float k, int accumulate, hipStream_t st, const float* stats = nullptr,
+                             const float* wmap = nullptr, int64_t w_bs = 0) {
     static const int env_pxb = [] { const char* e = mgf_knob("MGF_LPIPS_BWD_PXB"); return e ? atoi(e) : 0; }();
     int pxb = mgf_cdiv(hw, 64) * n >= 512 ? 64 : mgf_cdiv(hw, 32) * n >= 256 ? 32 : 16;
     if (env_pxb == 16 || env_pxb == 32 || env_pxb == 64) pxb = env_pxb;
     static const bool no_cache = [] { const char* e = mgf_knob("MGF_LPIPS_BWD_CACHE"); return e && e[0] == '0'; }();
     const dim3 grid((unsigned)mgf_cdiv(hw, pxb), n);
-#define MGF_LPB_LAUNCH(PX, CP) hipLaunchKernelGGL((lpips_layer_bwd_kernel<PX, RELU, CP>), grid, dim3(256), 0, st, oa, ob, din, f0, f1u, lin, c, c_split, hw, f1_bs, k, accumulate, stats)
+#define MGF_LPB_LAUNCH(PX, CP)                                                                                                                     \
+    do {                                                                                                                                           \
+        if (wmap)                                                                                                                                  \
+            hipLaunchKernelGGL((lpips_layer_bwd_kernel<PX, RELU, CP, true>), grid, dim3(256), 0, st, oa, ob, din, f0, f1u, lin, c, c_split, hw,    \
+                               f1_bs, k, accumulate, stats, wmap, w_bs);                                                                           \
+        else                                                                                                                                       \
+            hipLaunchKernelGGL((lpips_layer_bwd_kernel<PX, RELU, CP>), grid, dim3(256), 0, st, oa, ob, din, f0, f1u, lin, c, c_split, hw, f1_bs,   \
+                               k, accumulate, stats, nullptr, 0);                                                                                  \
+    } while (0)
     if (pxb == 64) {
         if (c <= 64 && !no_cache && !stats) MGF_LPB_LAUNCH(64, 16);
         else MGF_LPB_LAUNCH(64, 0);
@@ -1563,6 +1578,33 @@ extern "C" int mgf_lpips_layer_bwd_relu_stats_f32(float* dz_a, float* dz_b, cons
     const float kk = 2.f * scale / (float)hw;
     lpips_bwd_launch<true>(dz_a, dz_b, dy, f0, f1_unit, lin, n, c, c_split, hw, f1_batch_stride, kk, 0, (hipStream_t)stream, stats);
     MGF_CHECK_LAUNCH("lpips_layer_bwd_relu");
+    return MGF_OK;
+}
+
+/* The region-weighted forms: the factor 2 scale / hw becomes 2 scale omega[p] (wmap: normalised weights, w_batch_stride 0 = shared) */
+extern "C" int mgf_lpips_layer_bwd_weighted_f32(float* df0, const float* f0, const float* f1_unit, const float* lin, const float* wmap, int32_t n,
+                                                int32_t c, int64_t hw, int64_t f1_batch_stride, int64_t w_batch_stride, float scale,
+                                                int32_t accumulate, mgf_stream_t stream) {
+    MGF_REQUIRE(df0 && f0 && f1_unit && lin && wmap && n >= 1 && c >= 1 && hw >= 1 && w_batch_stride >= 0, MGF_EINVAL, "lpips_layer_bwd_weighted: bad arguments");
+    MGF_REQUIRE((int64_t)c * hw < (1LL << 30), MGF_ETOOBIG, "lpips_layer_bwd_weighted: one sample's tap must stay below 4 GiB (32-bit buffer offsets)");
+    MGF_REQUIRE(n <= 65535, MGF_ETOOBIG, "lpips_layer_bwd_weighted: n must be <= 65535");
+    lpips_bwd_launch<false>(df0, nullptr, nullptr, f0, f1_unit, lin, n, c, c, hw, f1_batch_stride, 2.f * scale, accumulate, (hipStream_t)stream, nullptr,
+                            wmap, w_batch_stride);
+    MGF_CHECK_LAUNCH("lpips_layer_bwd_weighted");
+    return MGF_OK;
+}
+
+extern "C" int mgf_lpips_layer_bwd_relu_stats_weighted_f32(float* dz_a, float* dz_b, const float* dy, const float* f0, const float* f1_unit,
+                                                           const float* lin, const float* stats, const float* wmap, int32_t n, int32_t c,
+                                                           int32_t c_split, int64_t hw, int64_t f1_batch_stride, int64_t w_batch_stride,
+                                                           float scale, mgf_stream_t stream) {
+    MGF_REQUIRE(dz_a && f0 && f1_unit && lin && wmap && n >= 1 && c >= 1 && hw >= 1 && w_batch_stride >= 0, MGF_EINVAL, "lpips_layer_bwd_relu_weighted: bad arguments");
+    MGF_REQUIRE(c_split >= 1 && c_split <= c && (dz_b || c_split == c), MGF_EINVAL, "lpips_layer_bwd_relu_weighted: bad split %d of %d channels", c_split, c);
+    MGF_REQUIRE(n <= 65535, MGF_ETOOBIG, "lpips_layer_bwd_relu_weighted: n must be <= 65535");
+    MGF_REQUIRE((int64_t)c * hw < (1LL << 30), MGF_ETOOBIG, "lpips_layer_bwd_relu_weighted: one sample's tap must stay below 4 GiB (32-bit buffer offsets)");
+    lpips_bwd_launch<true>(dz_a, dz_b, dy, f0, f1_unit, lin, n, c, c_split, hw, f1_batch_stride, 2.f * scale, 0, (hipStream_t)stream, stats, wmap,
+                           w_batch_stride);
+    MGF_CHECK_LAUNCH("lpips_layer_bwd_relu_weighted");
     return MGF_OK;
 }
 

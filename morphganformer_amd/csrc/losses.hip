@@ -66,6 +66,78 @@ __global__ __launch_bounds__(256) void mse_partial_kernel(float* scratch, const 
     if (threadIdx.x == 0) scratch[(int64_t)blockIdx.y * RED_BLOCKS + blockIdx.x] = acc;
 }
 
+// Region-weighted pixel term on [n][c][hw] images: a thread takes quads of 4 consecutive elements of a sample (flat over c * hw) with the
+// weight of each element's pixel.  VEC (hw % 4 == 0, all pointers 16-byte aligned per sample): a quad lies in one channel plane and is three
+// 16-byte loads; otherwise the same quad through scalar loads -- the same operands in the same expressions, so both paths give the same bits.
+template <bool VEC>
+__device__ __forceinline__ void wquad_load(float (&u)[4], float (&v)[4], float (&w)[4], const float* as, const float* bs, const float* ws,
+                                           int64_t q, int64_t numel, int64_t hw) {
+    if (VEC) {
+        const float4 a4 = reinterpret_cast<const float4*>(as)[q], b4 = reinterpret_cast<const float4*>(bs)[q];
+        const float4 w4 = reinterpret_cast<const float4*>(ws)[q % (hw >> 2)];
+        u[0] = a4.x; u[1] = a4.y; u[2] = a4.z; u[3] = a4.w;
+        v[0] = b4.x; v[1] = b4.y; v[2] = b4.z; v[3] = b4.w;
+        w[0] = w4.x; w[1] = w4.y; w[2] = w4.z; w[3] = w4.w;
+    } else {
+        int64_t p = (q * 4) % hw;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t i = q * 4 + e;
+            const bool in = i < numel;                      // the last quad of a sample may be ragged: a = b = w = 0 adds +0
+            u[e] = in ? as[i] : 0.f; v[e] = in ? bs[i] : 0.f; w[e] = in ? ws[p] : 0.f;
+            if (++p == hw) p = 0;
+        }
+    }
+}
+
+// grid = (blocks, n): scratch[s][block] = sum over the block's quads of omega[p] (a - b)^2
+template <bool VEC>
+__global__ __launch_bounds__(256) void mse_weighted_partial_kernel(float* scratch, const float* a, const float* b, const float* wmap, int64_t numel,
+                                                                   int64_t hw, int64_t b_stride, int64_t w_stride) {
+    __shared__ float sm[4];
+    const float* as = a + (int64_t)blockIdx.y * numel;
+    const float* bs = b + (int64_t)blockIdx.y * b_stride;
+    const float* ws = wmap + (int64_t)blockIdx.y * w_stride;
+    const int64_t nquad = (numel + 3) >> 2;
+    float acc = 0.f;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
+        float u[4], v[4], w[4];
+        wquad_load<VEC>(u, v, w, as, bs, ws, q, numel, hw);
+        const float d0 = u[0] - v[0], d1 = u[1] - v[1], d2 = u[2] - v[2], d3 = u[3] - v[3];
+        acc += w[0] * (d0 * d0) + w[1] * (d1 * d1) + w[2] * (d2 * d2) + w[3] * (d3 * d3);
+    }
+    acc = block_sum_256(acc, sm);
+    if (threadIdx.x == 0) scratch[(int64_t)blockIdx.y * RED_BLOCKS + blockIdx.x] = acc;
+}
+
+// grid = (blocks, n): d (+)= k omega[p] (a - b)        (k = 2 scale)
+template <bool VEC>
+__global__ __launch_bounds__(256) void mse_weighted_grad_kernel(float* d, const float* a, const float* b, const float* wmap, int64_t numel, int64_t hw,
+                                                                int64_t b_stride, int64_t w_stride, float k, int accumulate) {
+    const float* as = a + (int64_t)blockIdx.y * numel;
+    const float* bs = b + (int64_t)blockIdx.y * b_stride;
+    const float* ws = wmap + (int64_t)blockIdx.y * w_stride;
+    float* ds = d + (int64_t)blockIdx.y * numel;
+    const int64_t nquad = (numel + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
+        float u[4], v[4], w[4], g[4];
+        wquad_load<VEC>(u, v, w, as, bs, ws, q, numel, hw);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) g[e] = (k * w[e]) * (u[e] - v[e]);
+        if (VEC) {
+            float4* dp = reinterpret_cast<float4*>(ds) + q;
+            if (accumulate) { const float4 o = *dp; g[0] = o.x + g[0]; g[1] = o.y + g[1]; g[2] = o.z + g[2]; g[3] = o.w + g[3]; }
+            *dp = make_float4(g[0], g[1], g[2], g[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t i = q * 4 + e;
+                if (i < numel) ds[i] = accumulate ? ds[i] + g[e] : g[e];
+            }
+        }
+    }
+}
+
 // grid = (pixel blocks, n).  A workgroup owns PXB consecutive pixels of one sample (lanes = consecutive pixels, so a wave reads
 // whole 64/256-byte segments of a channel plane); its G = 256 / PXB lane groups take the channels grp, grp + G, grp + 2G ...
 // ONE sweep over HBM: each thread keeps its <= CPT channel values in registers, the squared norms meet in LDS in a fixed order
@@ -73,10 +145,12 @@ __global__ __launch_bounds__(256) void mse_partial_kernel(float* scratch, const 
 // per target) or compared with the stored unit-normalised reference taps and reduced to one partial per workgroup.
 // MAP (spatial LPIPS, networks_basic.py:75-76): the per-pixel distance itself is the result -- the G lane groups' d meet in LDS, are added in
 // group order and lane group 0 stores one float per pixel to `stats` (here the [n][hw] map); no partial sums, no finish launch.
-template <int PXB, int CPT, bool UNIT_OUT, bool STATS = false, bool MAP = false>
+// WEIGHTED (region weights): the partial sums are of omega[p] * d[p] -- every lane loads its pixel's normalised weight (one more buffer
+// load; the G lane groups of a pixel hit the same line) and scales its own share of d; STATS are formed as without a weight.
+template <int PXB, int CPT, bool UNIT_OUT, bool STATS = false, bool MAP = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void lpips_layer_kernel(float* scratch, float* unit_out, const float* f0, const float* f1u,
                                                            const float* lin, int c, int64_t hw, int64_t f1_stride, int nsamp, int nblk,
-                                                           int xcd_per, float* stats) {
+                                                           int xcd_per, float* stats, const float* wmap, int64_t w_stride) {
     constexpr int G = 256 / PXB;
     __shared__ float red[G][PXB];
     __shared__ float redb[(STATS || MAP) ? G : 1][PXB], redc[STATS ? G : 1][PXB];      // STATS: the two other per-pixel sums the gradient needs
@@ -164,13 +238,24 @@ __global__ __launch_bounds__(256) void lpips_layer_kernel(float* scratch, float*
         }
         return;
     }
+    if (WEIGHTED) {
+        // loaded HERE, behind the barriers and the channel sweep, not in the tap burst: one more live register through the sweep takes the
+        // 64-values-per-thread forms from 168 to 169 VGPRs, i.e. from three waves per SIMD to two (+18 % at 32 x 512 @ 63^2)
+        // (the pixel offset is formed again from the thread index -- the empty asm keeps the compiler from carrying `pp` through instead)
+        unsigned t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        const int64_t iw = (int64_t)blk * PXB + (int)(t % PXB);
+        const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(wmap + (int64_t)nn * w_stride), 0, (int)plane_bytes, 0x00020000);
+        d *= __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, 4u * (unsigned)(iw < hw ? iw : hw - 1), 0, 0));
+    }
     const float acc = block_sum_256(valid ? d : 0.f, sm);
     if (threadIdx.x == 0) scratch[(int64_t)nn * RED_BLOCKS + blk] = acc;
 }
 
 template <bool UNIT_OUT>
 int launch_lpips_layer(float* scratch, float* unit_out, const float* f0, const float* f1u, const float* lin, int n, int c, int64_t hw,
-                       int64_t f1_stride, hipStream_t st, int* grid_out, float* stats = nullptr, float* map = nullptr) {
+                       int64_t f1_stride, hipStream_t st, int* grid_out, float* stats = nullptr, float* map = nullptr,
+                       const float* wmap = nullptr, int64_t w_stride = 0) {
     // 64 pixels per workgroup (256-byte segments) whenever that still yields >= 4 workgroups per CU, 16 for the small deep taps
     static const int pxb_env = [] { const char* e = mgf_knob("MGF_LPIPS_PXB"); return e ? atoi(e) : 0; }();      // tuning hook: 16 | 32 | 64
     // (re-tuned on buffer addressing, 32 x {128 @ 255^2, 256 @ 127^2, 384 @ 63^2, 512 @ 63^2}, us for 64 / 32 / 16-pixel blocks:
@@ -190,15 +275,21 @@ int launch_lpips_layer(float* scratch, float* unit_out, const float* f0, const f
     *grid_out = (int)grid64;
 #define MGF_LPIPS_LAUNCH(PXB, CPT)                                                                                                            \
     do {                                                                                                                                      \
-        if (!UNIT_OUT && map)                                                                                                                 \
-            hipLaunchKernelGGL((lpips_layer_kernel<PXB, CPT, false, false, true>), grid, dim3(256), 0, st, scratch, unit_out, f0, f1u, lin, c, \
-                               hw, f1_stride, n, (int)grid64, xcd_per, map);                                                                  \
+        if (!UNIT_OUT && wmap && stats)                                                                                                       \
+            hipLaunchKernelGGL((lpips_layer_kernel<PXB, CPT, false, true, false, true>), grid, dim3(256), 0, st, scratch, unit_out, f0, f1u,  \
+                               lin, c, hw, f1_stride, n, (int)grid64, xcd_per, stats, wmap, w_stride);                                        \
+        else if (!UNIT_OUT && wmap)                                                                                                           \
+            hipLaunchKernelGGL((lpips_layer_kernel<PXB, CPT, false, false, false, true>), grid, dim3(256), 0, st, scratch, unit_out, f0, f1u, \
+                               lin, c, hw, f1_stride, n, (int)grid64, xcd_per, nullptr, wmap, w_stride);                                      \
+        else if (!UNIT_OUT && map)                                                                                                            \
+            hipLaunchKernelGGL((lpips_layer_kernel<PXB, CPT, false, false, true>), grid, dim3(256), 0, st, scratch, unit_out, f0, f1u, lin, c,\
+                               hw, f1_stride, n, (int)grid64, xcd_per, map, nullptr, 0);                                                      \
         else if (!UNIT_OUT && stats)                                                                                                          \
-            hipLaunchKernelGGL((lpips_layer_kernel<PXB, CPT, false, true>), grid, dim3(256), 0, st, scratch, unit_out, f0, f1u, lin, c, hw,    \
-                               f1_stride, n, (int)grid64, xcd_per, stats);                                                                    \
+            hipLaunchKernelGGL((lpips_layer_kernel<PXB, CPT, false, true>), grid, dim3(256), 0, st, scratch, unit_out, f0, f1u, lin, c, hw,   \
+                               f1_stride, n, (int)grid64, xcd_per, stats, nullptr, 0);                                                        \
         else                                                                                                                                  \
             hipLaunchKernelGGL((lpips_layer_kernel<PXB, CPT, UNIT_OUT>), grid, dim3(256), 0, st, scratch, unit_out, f0, f1u, lin, c, hw,      \
-                               f1_stride, n, (int)grid64, xcd_per, nullptr);                                                                  \
+                               f1_stride, n, (int)grid64, xcd_per, nullptr, nullptr, 0);                                                      \
     } while (0)
     if (pxb == 64) {
         if (c <= 128) MGF_LPIPS_LAUNCH(64, 32); else if (c <= 256) MGF_LPIPS_LAUNCH(64, 64); else MGF_LPIPS_LAUNCH(64, 128);
@@ -521,6 +612,48 @@ extern "C" int mgf_mse_f32(float* out, const float* a, const float* b, int32_t n
     return MGF_OK;
 }
 
+namespace {
+// the 16-byte path of the weighted pixel term: whole quads per plane and every sample's rows aligned
+bool wquad_vec(const void* a, const void* b, const void* w, const void* d, int32_t n, int64_t numel, int64_t hw, int64_t b_bs, int64_t w_bs) {
+    const auto al = [](const void* p) { return (uintptr_t)p % 16 == 0; };
+    return hw % 4 == 0 && al(a) && al(b) && al(w) && al(d) && b_bs % 4 == 0 && w_bs % 4 == 0 && (numel % 4 == 0 || n == 1);
+}
+}  // namespace
+
+extern "C" int mgf_mse_weighted_f32(float* out, const float* a, const float* b, const float* wmap, int32_t n, int32_t c, int64_t hw,
+                                    int64_t b_batch_stride, int64_t w_batch_stride, float scale, int32_t accumulate, float* scratch,
+                                    mgf_stream_t stream) {
+    MGF_REQUIRE(out && a && b && wmap && scratch && c >= 1 && hw >= 1 && n >= 1 && n <= 65535 && b_batch_stride >= 0 && w_batch_stride >= 0,
+                MGF_EINVAL, "mse_weighted: bad arguments");
+    const int64_t numel = (int64_t)c * hw;
+    const int grid = (int)(mgf_cdiv(numel, 256 * 8) < 1024 ? mgf_cdiv(numel, 256 * 8) : 1024);
+    hipStream_t st = (hipStream_t)stream;
+    if (wquad_vec(a, b, wmap, nullptr, n, numel, hw, b_batch_stride, w_batch_stride))
+        hipLaunchKernelGGL(mse_weighted_partial_kernel<true>, dim3(grid, n), dim3(256), 0, st, scratch, a, b, wmap, numel, hw, b_batch_stride, w_batch_stride);
+    else
+        hipLaunchKernelGGL(mse_weighted_partial_kernel<false>, dim3(grid, n), dim3(256), 0, st, scratch, a, b, wmap, numel, hw, b_batch_stride, w_batch_stride);
+    hipLaunchKernelGGL(finish_kernel, dim3(n), dim3(256), 0, st, out, scratch, grid, scale, accumulate);
+    MGF_CHECK_LAUNCH("mse_weighted");
+    return MGF_OK;
+}
+
+extern "C" int mgf_mse_weighted_grad_f32(float* d, const float* a, const float* b, const float* wmap, int32_t n, int32_t c, int64_t hw,
+                                         int64_t b_batch_stride, int64_t w_batch_stride, float scale, int32_t accumulate, mgf_stream_t stream) {
+    MGF_REQUIRE(d && a && b && wmap && c >= 1 && hw >= 1 && n >= 1 && n <= 65535 && b_batch_stride >= 0 && w_batch_stride >= 0, MGF_EINVAL,
+                "mse_weighted_grad: bad arguments");
+    const int64_t numel = (int64_t)c * hw;
+    const int grid = (int)(mgf_cdiv(numel, 256 * 8) < 1024 ? mgf_cdiv(numel, 256 * 8) : 1024);
+    hipStream_t st = (hipStream_t)stream;
+    if (wquad_vec(a, b, wmap, d, n, numel, hw, b_batch_stride, w_batch_stride))
+        hipLaunchKernelGGL(mse_weighted_grad_kernel<true>, dim3(grid, n), dim3(256), 0, st, d, a, b, wmap, numel, hw, b_batch_stride, w_batch_stride,
+                           2.f * scale, accumulate);
+    else
+        hipLaunchKernelGGL(mse_weighted_grad_kernel<false>, dim3(grid, n), dim3(256), 0, st, d, a, b, wmap, numel, hw, b_batch_stride, w_batch_stride,
+                           2.f * scale, accumulate);
+    MGF_CHECK_LAUNCH("mse_weighted_grad");
+    return MGF_OK;
+}
+
 extern "C" int mgf_lpips_unit_f32(float* out, const float* f, int32_t n, int32_t c, int64_t hw, mgf_stream_t stream) {
     MGF_REQUIRE(out && f && n >= 1 && n <= 65535 && c >= 1 && hw >= 1, MGF_EINVAL, "lpips_unit: bad arguments");
     int grid = 0;
@@ -559,6 +692,21 @@ extern "C" int mgf_lpips_layer_defer_f32(float* scratch, float* stats, const flo
     if (rc != MGF_OK) return rc;
     *nparts_out = grid;
     MGF_CHECK_LAUNCH("lpips_layer_defer");
+    return MGF_OK;
+}
+
+/* mgf_lpips_layer_defer_f32 with a normalised per-pixel weight: the partials are of omega[p] * d[p] (finish with scale 1) */
+extern "C" int mgf_lpips_layer_defer_weighted_f32(float* scratch, float* stats, const float* f0, const float* f1_unit, const float* lin,
+                                                  const float* wmap, int32_t n, int32_t c, int64_t hw, int64_t f1_batch_stride,
+                                                  int64_t w_batch_stride, int32_t* nparts_out, mgf_stream_t stream) {
+    MGF_REQUIRE(scratch && f0 && f1_unit && lin && wmap && nparts_out && n >= 1 && n <= 65535 && c >= 1 && hw >= 1 && w_batch_stride >= 0, MGF_EINVAL,
+                "lpips_layer_defer_weighted: bad arguments");
+    int grid = 0;
+    const int rc = launch_lpips_layer<false>(scratch, nullptr, f0, f1_unit, lin, n, c, hw, f1_batch_stride, (hipStream_t)stream, &grid, stats, nullptr,
+                                             wmap, w_batch_stride);
+    if (rc != MGF_OK) return rc;
+    *nparts_out = grid;
+    MGF_CHECK_LAUNCH("lpips_layer_defer_weighted");
     return MGF_OK;
 }
 

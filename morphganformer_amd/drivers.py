@@ -167,7 +167,8 @@ def _blend_latents(a1, a2, a):
 
 def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, args: ProjectionArgs = None, percept=None, biometric=None,
                  gamma=1.0, id_balance=0.0, id_metric="mse", latent_std=None, eps=None, seed=None, use_graph=True, noise_mode="random",
-                 use_mse=True, lm_target=None, lm_target_b=None, lm_steps=None, weight_decay=0.0, mode="gradient", out_prefix=None, ratio=None):
+                 use_mse=True, lm_target=None, lm_target_b=None, lm_steps=None, weight_decay=0.0, mode="gradient", out_prefix=None, ratio=None,
+                 region_weight=None):
     """Morph refinement: for every alpha start at merge_morph's blend (1 - a) w1 + a w2 (the same float32 arithmetic) and descend it so that
     the image matches BOTH contributing subjects -- target_a weighted 1 - a, target_b weighted a: perceptually, in pixels and in identity
     space, the two identity distances kept in balance by id_balance |d_a - d_b| (GradientProjectionEngine(target_b=...) has the objective).
@@ -177,7 +178,8 @@ def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, ar
     latent statistics' scale, as for a projection).  lm_target / lm_target_b [68,2] and lm_steps [steps,68,2] add the Wing term against the
     blended landmarks.  Returns one dict per alpha: alpha, w_start (numpy), w (best latent, [1,k,D] or W+), losses, best_step, best_loss,
     id_distances ((d_a, d_b) at the best step; None without a biometric term).  out_prefix: `<prefix>_a{alpha:.2f}_refined.mat / .png`, the
-    image rendered like a projection result (no truncation)."""
+    image rendered like a projection result (no truncation).  region_weight: one map [S,S] >= 0 that weights the LPIPS and pixel terms of
+    every alpha (GradientProjectionEngine(region_weight=...); `face_region_weight` builds one from landmarks)."""
     if mode != "gradient":
         raise ValueError(f"refine_morph descends the objective: mode must be 'gradient' (got {mode!r}; the literal loop never moves the latent)")
     a1 = np.asarray(w1.detach().cpu() if isinstance(w1, torch.Tensor) else w1, dtype=np.float32)
@@ -221,7 +223,7 @@ def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, ar
                                        weight_decay=weight_decay, percept=percept, eps=eps[:, js].contiguous(), noise_mode=noise_mode,
                                        use_graph=use_graph, use_mse=use_mse, latent_space=space, biometric=biometric, gamma=gamma,
                                        target_b=rep(target_b), morph_alpha=[alphas[j] for j in js], id_balance=id_balance, id_metric=id_metric,
-                                       **lm_kw)
+                                       region_weight=region_weight, **lm_kw)
         w, step, loss, losses = eng.run().result()
         trace = None if eng.id_trace is None else eng.id_trace.cpu().numpy()
         if n == 1:
@@ -296,6 +298,40 @@ def merge_files(src_path, dst_path):
     return out
 
 
+def face_region_weight(landmarks, size, inside=1.0, outside=0.0, feather=0.0):
+    """A region weight from face landmarks: `inside` on the convex hull of the [68,2] (x, y) points, `outside` elsewhere -- the landmark hull is
+    the region the reference's warp script treats as the face (1024_warp_morphs.py:160-210 triangulates exactly these points).  Host only: the
+    hull is scipy.spatial.ConvexHull, filled as a polygon (Pillow ImageDraw, boundary included); feather > 0 blurs the edge with a Gaussian of
+    that sigma in pixels (scipy.ndimage.gaussian_filter).  -> float32 [size, size] for the engines' region_weight."""
+    from PIL import Image, ImageDraw
+    from scipy.spatial import ConvexHull
+    pts = np.asarray(landmarks, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.shape[0] < 3 or not np.isfinite(pts).all():
+        raise ValueError(f"face_region_weight: landmarks must be finite [P,2] points, P >= 3 (got {pts.shape})")
+    if inside < 0 or outside < 0 or feather < 0 or max(inside, outside) <= 0:
+        raise ValueError("face_region_weight: inside, outside >= 0 (not both zero) and feather >= 0")
+    hull = pts[ConvexHull(pts).vertices]                         # counter-clockwise
+    mask = Image.new("L", (int(size), int(size)), 0)
+    ImageDraw.Draw(mask).polygon([(float(x), float(y)) for x, y in hull], fill=1, outline=1)
+    w = np.where(np.asarray(mask) > 0, float(inside), float(outside))
+    if feather > 0:
+        from scipy.ndimage import gaussian_filter
+        w = gaussian_filter(w, sigma=float(feather), mode="nearest")
+    return np.ascontiguousarray(w, dtype=np.float32)
+
+
+def load_region_weight(path):
+    """A region weight file -> float32 [H,W]: a .npy float map as it is, any image file as its gray values scaled to [0, 1]."""
+    if str(path).endswith(".npy"):
+        w = np.load(path)
+    else:
+        from PIL import Image
+        w = np.asarray(Image.open(path).convert("L"), dtype=np.float32) / 255.0
+    if w.ndim != 2:
+        raise ValueError(f"{path}: a region weight is one [H,W] map (got {w.shape})")
+    return np.ascontiguousarray(w, dtype=np.float32)
+
+
 def lpips_map(percept, img, target):
     """Where `img` departs from `target`: the [N,1,H,W] map of a lpips.PerceptualLoss(spatial=True) (PNetLin.forward with spatial=True,
     lpips/networks_basic.py:75-76,85-87).  img: [N,3,H,H] in [-1,1]; target: [1,3,H,H] (shared) or [N,3,H,H]."""
@@ -338,7 +374,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                   eps=None, out_prefix=None, batch=DEFAULT_BATCH, use_graph=True, noise_mode="random", use_mse=True, seed=None,
                   landmark_fn=None, mode="literal", weight_decay=0.0, path_to_gen=None, keep_images=64, engine=None,
                   return_engine=False, latent_space="z", landmark_input="float", biometric=None, gamma=1.0, lbp_target=None, pipeline=None,
-                  mdf=None, optimize_noise=False, noise_init="randn", lpips_map=False):
+                  mdf=None, optimize_noise=False, noise_init="randn", lpips_map=False, region_weight=None):
     """One full `projection(...)` call (:135-208).  `target`: [1,3,S,S] from image_transform; `lm_target` [68,2] and either
     `lm_steps` [steps,68,2] (injected landmark detections) or `landmark_fn` (host detector called on every generated image,
     see ProjectionEngine; landmark_input="gray_u8" hands it the drivers' gray uint8 image, built on the device).  mode="literal" is the loop as the reference executes it (best-of-N noisy sampling, `batch` steps per
@@ -376,6 +412,9 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     step's maps, as the saved PNG is rendered -- departs from the target; with `path_to_gen` it is also written there as
     best_lpips_map.npy / .png (save_lpips_map).
 
+    region_weight: a map [H,W] >= 0 at the size the image-space losses see that weights the LPIPS and pixel terms by region (both engines'
+    region_weight; `face_region_weight` builds one from landmarks).  A re-targeted engine takes the new target's weight in place.
+
     engine: a ProjectionEngine from an earlier call with the same generator, objective, step count and batch (return_engine=True
     hands it out) -- it is re-targeted in place (`ProjectionEngine.retarget`), which keeps its captured hipGraph and workspaces; this is
     how `project_many` walks a list of targets."""
@@ -412,21 +451,23 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                                       ("percept", engine.percept is percept), ("use_mse", engine.use_mse == bool(use_mse)),
                                       ("noise_mode", engine.noise_mode == noise_mode), ("args", engine.args == args),
                                       ("landmark_fn", engine.landmark_fn is landmark_fn), ("biometric", engine.biometric is biometric),
-                                      ("gamma", biometric is None or engine.gamma == float(gamma)), ("mdf", engine.mdf is mdf)) if not ok]
+                                      ("gamma", biometric is None or engine.gamma == float(gamma)), ("mdf", engine.mdf is mdf),
+                                      ("region_weight", (engine.pix_w is not None) == (region_weight is not None))) if not ok]
         if diff:
             raise ValueError("engine= was built for another objective: " + ", ".join(diff) + " differ(s); build a fresh engine")
         eng = engine.retarget(target, lm_target=lm_target, lm_steps=lm_steps, eps=eps, seed=seed if eps is None else None,
-                              latent_mean=latent_mean, latent_std=float(latent_std), lbp_target=lbp_target)
+                              latent_mean=latent_mean, latent_std=float(latent_std), lbp_target=lbp_target, region_weight=region_weight)
     elif mode == "gradient":
         eng = GradientProjectionEngine(G, target, latent_mean, float(latent_std), args, weight_decay=weight_decay, percept=percept,
                                        lm_target=lm_target, lm_steps=lm_steps, eps=eps, noise_mode=noise_mode, use_graph=use_graph,
                                        use_mse=use_mse, landmark_fn=landmark_fn, seed=0 if seed is None else seed, latent_space=latent_space,
-                                       biometric=biometric, gamma=gamma, mdf=mdf, optimize_noise=optimize_noise, noise_init=noise_init)
+                                       biometric=biometric, gamma=gamma, mdf=mdf, optimize_noise=optimize_noise, noise_init=noise_init,
+                                       region_weight=region_weight)
     else:
         eng = ProjectionEngine(G, target, latent_mean, float(latent_std), args, percept=percept, lm_target=lm_target,
                                lm_steps=lm_steps, eps=eps, noise_mode=noise_mode, use_graph=use_graph, batch=batch, use_mse=use_mse,
                                landmark_fn=landmark_fn, keep_images=keep, seed=0 if seed is None else seed, landmark_input=landmark_input,
-                               biometric=biometric, gamma=gamma, lbp_target=lbp_target, pipeline=pipeline, mdf=mdf)
+                               biometric=biometric, gamma=gamma, lbp_target=lbp_target, pipeline=pipeline, mdf=mdf, region_weight=region_weight)
     w, step, loss, losses = eng.run().result()
     out = {"w": w, "step": step, "loss": loss, "losses": losses}
     best_noises = None
@@ -453,7 +494,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     return out
 
 
-def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, **kw):
+def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_weights=None, **kw):
     """Pair-level sharding of BASELINE configs 3/5: rank r projects `targets[r::world]` (or, with dynamic=True, whatever the
     shared `distributed.WorkQueue` hands it), then ONE all_gather returns every item's {latent, loss, step} to every rank.
     targets: list of [1,3,S,S] device tensors (or image paths); landmarks: optional list of (lm_target, lm_steps) per item.
@@ -462,7 +503,11 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, **kw):
     In literal mode the rank builds ONE engine (latent statistics, LPIPS workspaces, hipGraph capture) for its first item and
     re-targets it for the others, as the reference keeps G / percept / latent statistics outside its per-image loop
     (projection_example_v2_percept_morph.py:311-355).
+    region_weights: one region weight [H,W] for every item, or a list with one per item (project_image's region_weight).
     Returns dict(latents [N,k,D], losses [N], steps [N], items [N]) ordered by item id, plus `mine`: the items this rank worked on."""
+    if isinstance(region_weights, (list, tuple)) and len(region_weights) != len(targets):
+        raise ValueError(f"project_many: {len(region_weights)} region weights for {len(targets)} targets")
+    rw = lambda i: region_weights[i] if isinstance(region_weights, (list, tuple)) else region_weights
     import torch.distributed as dist
     from .distributed import gather_many, pack_result, run_sharded, shard_items, unpack_results
     on = dist.is_available() and dist.is_initialized()
@@ -483,7 +528,8 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, **kw):
         mine = shard_items(len(targets), rank, world)
         for g0 in range(0, len(mine), lockstep):
             ids = mine[g0:g0 + lockstep]
-            res = _project_group(G, [load(targets[i]) for i in ids], [landmarks[i] for i in ids] if landmarks is not None else None, **kw)
+            res = _project_group(G, [load(targets[i]) for i in ids], [landmarks[i] for i in ids] if landmarks is not None else None,
+                                 region_weight=None if region_weights is None else [rw(i) for i in ids], **kw)
             recs += [pack_result(res["w"][j:j + 1].to(G.device), float(res["loss"][j]), int(res["step"][j]), item=i) for j, i in enumerate(ids)]
         rows = torch.stack(recs) if recs else torch.empty([0, width], dtype=torch.float64, device=G.device)
         out = unpack_results(gather_many(rows, -(-len(targets) // world)), lshape)
@@ -504,7 +550,7 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, **kw):
         eng = state["eng"]
         if eng is not None and eng.use_wing != (lm_t is not None):
             eng = None                     # an item with / without landmarks after one without / with: another objective, a fresh engine
-        r = project_image(G, load(targets[i]), lm_t, lm_s, engine=eng, return_engine=reuse, **kw)
+        r = project_image(G, load(targets[i]), lm_t, lm_s, engine=eng, return_engine=reuse, region_weight=rw(i), **kw)
         state["eng"] = r.get("engine")
         return pack_result(r["w"].to(G.device), r["loss"], r["step"], item=i)
 
@@ -570,7 +616,7 @@ def morph_pairs(G, pairs, src_dir, dst_raw, dst_morph, landmarks=None, truncatio
 
 def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=None, latent_mean=None, latent_std=None, eps=None,
                    use_graph=True, noise_mode="random", use_mse=True, seed=None, weight_decay=0.0, mode="gradient", latent_space="z",
-                   biometric=None, gamma=1.0, batch=None, pipeline=None, mdf=None, **unused):
+                   biometric=None, gamma=1.0, batch=None, pipeline=None, mdf=None, region_weight=None, **unused):
     """B targets through one lockstep GradientProjectionEngine; returns dict(w [B,k,D] (W+: [B,k,num_ws,D]), step [B], loss [B],
     losses [B,steps])."""
     args = args or ProjectionArgs()
@@ -586,6 +632,9 @@ def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=N
             gen.manual_seed(seed)
         latent_mean, latent_std = (latent_stats_w if latent_space == "w+" else latent_stats)(G, args.n_mean_latent, G.device, generator=gen)
     tg = torch.cat([t.reshape(1, *t.shape[-3:]) for t in targets]).contiguous()
+    if region_weight is not None:                   # one map per target of the group
+        region_weight = torch.stack([torch.as_tensor(np.asarray(w.detach().cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float64)).reshape(
+            tg.shape[-2], tg.shape[-1]) for w in region_weight])[:, None]
     lm_t = lm_s = None
     if landmarks is not None:
         lm_t, lm_s = np.stack([np.asarray(l[0]) for l in landmarks]), np.stack([np.asarray(l[1]) for l in landmarks])
@@ -593,7 +642,8 @@ def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=N
         lm_t, lm_s = lm_t[0], lm_s[0]
     eng = GradientProjectionEngine(G, tg, latent_mean, float(latent_std), args, weight_decay=weight_decay, percept=percept,
                                    lm_target=lm_t, lm_steps=lm_s, eps=eps, noise_mode=noise_mode, use_graph=use_graph, use_mse=use_mse,
-                                   seed=0 if seed is None else seed, latent_space=latent_space, biometric=biometric, gamma=gamma)
+                                   seed=0 if seed is None else seed, latent_space=latent_space, biometric=biometric, gamma=gamma,
+                                   region_weight=region_weight)
     w, step, loss, losses = eng.run().result()
     if len(targets) == 1:
         return {"w": w, "step": np.array([step]), "loss": np.array([loss]), "losses": losses[None]}

@@ -194,11 +194,12 @@ class SequentialFeatures:
         return taps
 
 
-    def backward(self, target_taps, lins, scale, per_sample=False):
+    def backward(self, target_taps, lins, scale, per_sample=False, region=None):
         """Gradient of  scale * sum_taps lpips_layer(tap, target_tap)  with respect to the input image of the latest __call__
         (taps in the internal workspace); per_sample: target_taps hold one target per sample instead of one shared target.
         3x3 / stride-1 layers take the tap-list kernel on transposed, flipped taps; AlexNet's 5x5 runs as chained <= 9-tap launches
-        (conv.conv_large_dgrad) and its 11x11 / stride-4 stem as 16 phase launches (conv.conv_strided_dgrad)."""
+        (conv.conv_large_dgrad) and its 11x11 / stride-4 stem as 16 phase launches (conv.conv_strided_dgrad).
+        region: (per-tap normalised weights [nw, h_l * w_l], nw) -- the gradient of the region-weighted distance (the weighted tap kernels)."""
         L, st = _lib.lib(), _lib.stream_ptr()
         rows = [(row, buf) for row, buf in zip(self.spec, self.bufs)]
         if not self.gp:
@@ -222,7 +223,11 @@ class SequentialFeatures:
             c, hh, ww = h.shape[1:]
             behind = pos != len(nodes) - 1                     # a gradient from the rows behind this one is already in gh
             fused = FUSE_TAP_RELU and i in tap_of and row[0] == "conv"
-            if fused:
+            if i in tap_of and region is not None:
+                kk = tap_of[i]
+                _tap_bwd_weighted(L, st, fused, gh, None, gh if behind else None, h, target_taps[kk], lins[kk],
+                                  getattr(self, "tap_stats", {}).get(kk), region, kk, n, c, c, hh * ww, per_sample, scale, behind)
+            elif fused:
                 kk = tap_of[i]
                 _lib.check(L.mgf_lpips_layer_bwd_relu_stats_f32(gh.data_ptr(), None, gh.data_ptr() if behind else None, h.data_ptr(),
                                                                 target_taps[kk].data_ptr(), lins[kk].data_ptr(),
@@ -249,6 +254,55 @@ class SequentialFeatures:
                 _lib.check(L.mgf_maxpool_s2_floor_bwd_f32(gprev.data_ptr(), gh.data_ptr(), prev.data_ptr(), n * c, prev.shape[2],
                                                           prev.shape[3], row[1], st), "maxpool_bwd")
         return self.gxs.div_(self.scale)                   # through the ScalingLayer (x - shift) / scale
+
+
+def _tap_bwd_weighted(L, st, fused, da, db, din, h, target, lin, stats, region, k, n, c, c_split, hw, per_sample, scale, accumulate):
+    """One tap's region-weighted distance gradient: the weighted form of the launch `backward` would issue without a weight (fused with
+    the ReLU behind the tap, or the plain form that adds to the gradient already in da)."""
+    omegas, nw = region
+    wm, ws = omegas[k], (hw if nw > 1 else 0)
+    if fused:
+        _lib.check(L.mgf_lpips_layer_bwd_relu_stats_weighted_f32(da.data_ptr(), _lib.ptr(db), _lib.ptr(din), h.data_ptr(), target.data_ptr(),
+                                                                 lin.data_ptr(), _lib.ptr(stats), wm.data_ptr(), n, c, c_split, hw,
+                                                                 c * hw if per_sample else 0, ws, float(scale), st), "lpips_layer_bwd_relu_weighted")
+    else:
+        _lib.check(L.mgf_lpips_layer_bwd_weighted_f32(da.data_ptr(), h.data_ptr(), target.data_ptr(), lin.data_ptr(), wm.data_ptr(), n, c, hw,
+                                                      c * hw if per_sample else 0, ws, float(scale), int(accumulate), st), "lpips_layer_bwd_weighted")
+
+
+def region_tap_weights(weight, sides):
+    """Normalised per-tap region weights.  weight: [..., H, W] >= 0 (any float dtype, CPU or device); sides: the taps' (h_l, w_l).  For every
+    tap W_l = adaptive_avg_pool2d(W, (h_l, w_l)) and omega_l = W_l / sum(W_l), both in float64, cast to float32 once -> list of [..., h_l, w_l].
+    (Every tap's grid is taken to span the image uniformly: the geometric assumption of the reference's spatial=True up-sampling,
+    networks_basic.py:20-24.)  A constant W gives omega_l = 1 / (h_l w_l): the un-weighted spatial mean."""
+    w = torch.as_tensor(weight).to(torch.float64)
+    lead = w.shape[:-2]
+    w4 = w.reshape(-1, 1, *w.shape[-2:])
+    out = []
+    for hh, ww in sides:
+        wl = torch.nn.functional.adaptive_avg_pool2d(w4, (int(hh), int(ww)))
+        wl = wl / wl.sum(dim=(2, 3), keepdim=True)
+        out.append(wl.to(torch.float32).reshape(*lead, int(hh), int(ww)))
+    return out
+
+
+def check_region_weight(weight, what="region weight"):
+    """A region weight as float64 [n, H, W] on the CPU from [H,W], [1,1,H,W] or [n,1,H,W]; ValueError for a negative or non-finite value, an
+    all-zero map or another shape."""
+    w = torch.as_tensor(weight).detach().to("cpu", torch.float64)
+    if w.dim() == 2:
+        w = w[None]
+    elif w.dim() == 4 and w.shape[1] == 1:
+        w = w[:, 0]
+    else:
+        raise ValueError(f"{what}: expected [H,W], [1,1,H,W] or [n,1,H,W] (got {tuple(w.shape)})")
+    if w.numel() == 0 or not bool(torch.isfinite(w).all()):
+        raise ValueError(f"{what}: values must be finite")
+    if bool((w < 0).any()):
+        raise ValueError(f"{what}: values must be >= 0")
+    if not bool((w.sum(dim=(1, 2)) > 0).all()):
+        raise ValueError(f"{what}: every map needs a positive sum (got an all-zero map)")
+    return w.contiguous()
 
 
 def _pool_out(n):
@@ -355,10 +409,10 @@ class SqueezeFeatures:
             n, _, h1, w1 = self.buf[1].shape
             self.gimg = torch.empty([n, 3, 2 * h1 + 1, cv.tconv_pitch(w1)], dtype=torch.float32, device=self.device)
 
-    def backward(self, target_taps, lins, scale, per_sample=False):
+    def backward(self, target_taps, lins, scale, per_sample=False, region=None):
         """Gradient of  scale * sum_taps lpips_layer(tap, target_tap)  with respect to the input image of the latest __call__
         (un-fused path: all 7 taps are in the workspace; per_sample: one target per sample instead of one shared target).  Returns a [n,3,2*h1+1,2*w1+1] view (rows/columns beyond it get no
-        gradient: the stride-2 stem never reads them)."""
+        gradient: the stride-2 stem never reads them).  region: as SequentialFeatures.backward."""
         self._grad_ws()
         L, st = _lib.lib(), _lib.stream_ptr()
         n = self.n
@@ -368,7 +422,12 @@ class SqueezeFeatures:
             # every tap is a ReLU output (the stem's, or a Fire's concat): its distance gradient and that ReLU's backward (with the
             # Fire's split into the two expand branches) are one pass
             fused = FUSE_TAP_RELU and idx in TAPS_AFTER and idx not in POOLS
-            if fused:
+            if idx in TAPS_AFTER and region is not None:
+                k = TAPS_AFTER.index(idx)
+                da, db, ex = (gh, None, c) if (idx == 1 or not fused) else (*self.gex[idx], FIRES[idx][2])
+                _tap_bwd_weighted(L, st, fused, da, db, gh if idx != 12 else None, h, target_taps[k], lins[k],
+                                  getattr(self, "tap_stats", {}).get(k), region, k, n, c, ex, hh * ww, per_sample, scale, idx != 12)
+            elif fused:
                 k = TAPS_AFTER.index(idx)
                 da, db, ex = (gh, None, c) if idx == 1 else (*self.gex[idx], FIRES[idx][2])
                 _lib.check(L.mgf_lpips_layer_bwd_relu_stats_f32(da.data_ptr(), _lib.ptr(db), gh.data_ptr() if idx != 12 else None, h.data_ptr(),
@@ -544,6 +603,8 @@ class PerceptualLoss(torch.nn.Module):
         self._target_n = 1
         self.pair_offset = None           # [B] float32 = alpha (1 - alpha) LPIPS(Ta, Tb) while a target pair is set (set_target_pair)
         self._last, self._last_hw = None, None
+        self._region = None               # float64 [nw, H, W] on the CPU while a region weight is set (set_region_weight)
+        self._region_taps = {}            # (nw, H, W) -> per-tap normalised weights [nw, h_l * w_l], rewritten in place per weight
         # the one-pass stem exists for SqueezeNet's first three layers; MGF_LPIPS_STEM=0 (tuning hook) keeps them separate
         self.fused_stem = net == "squeeze" and os.environ.get("MGF_LPIPS_STEM", "1") != "0"
         self._scratch = torch.empty(int(_lib.lib().mgf_reduce_scratch_floats()), dtype=torch.float32, device=self.device_)
@@ -561,6 +622,40 @@ class PerceptualLoss(torch.nn.Module):
                 f = SequentialFeatures(self.net, self.backbone_state, n, h, w, self.device_, share=share)
             self._feats[key] = f
         return f
+
+    def set_region_weight(self, weight):
+        """Weight the distance by region: weight [H,W], [1,1,H,W] (one map for every candidate) or [n,1,H,W] (one per candidate) >= 0 at the
+        image size; None: the uniform spatial mean again, with today's dispatch (fused stem included).  Per tap the weight is pooled to the
+        tap's grid and normalised (`region_tap_weights`), and `distance_into`, `grad_into`, `distance_per_tap` and the scalar module call
+        compute sum_l sum_p omega_l[p] m_l[p] on the un-fused path (the fused stem consumes tap 0 with a uniform mean).  `distance_map_into`
+        is unaffected.  The per-tap weights live in buffers that are rewritten in place while the geometry stays (captured graphs read
+        them).  With a target pair set, call `set_target_pair` again afterwards: its constant depends on the weight."""
+        if weight is None:
+            self._region = None
+            return
+        w = check_region_weight(weight, "set_region_weight")
+        nw, H, W = w.shape
+        f = self._features(nw, H, W)
+        keys = TAPS_AFTER if self.net == "squeeze" else range(len(self.chns))
+        om = region_tap_weights(w, [f.shapes[idx][1:] for idx in keys])
+        bufs = self._region_taps.get((nw, H, W))
+        if bufs is None:
+            bufs = self._region_taps[(nw, H, W)] = [torch.empty(nw, o.shape[1] * o.shape[2], dtype=torch.float32, device=self.device_) for o in om]
+        for b, o in zip(bufs, om):
+            b.copy_(o.reshape(nw, -1))
+        self._region = w
+        self.pair_offset = None
+
+    def _region_for(self, n, h, w):
+        """(per-tap weight buffers, nw) of the weight that is set, checked against n candidates of size h x w; None without a weight."""
+        if self._region is None:
+            return None
+        nw, H, W = self._region.shape
+        if (H, W) != (h, w):
+            raise ValueError(f"region weight is {H}x{W} but the images are {h}x{w}")
+        if nw not in (1, n):
+            raise ValueError(f"{nw} region weights cannot pair with {n} candidates")
+        return self._region_taps[(nw, H, W)], nw
 
     def set_target(self, target):
         """Cache the target's feature maps, unit-normalised over channels (they do not change across projection iterations; the
@@ -641,7 +736,11 @@ class PerceptualLoss(torch.nn.Module):
         (what autograd computes through networks_basic.py:64-92 and the backbone).  SqueezeNet and VGG16 backbones."""
         f = self._last
         assert f is not None and tuple(dimg.shape) == (f.n, 3, *self._last_hw), "call distance_into(..., keep_taps=True) first"
-        g = f.backward(self._target_taps, self.lins, scale, per_sample=self._target_n > 1)
+        region = self._region_for(f.n, *self._last_hw)
+        if region is None:
+            g = f.backward(self._target_taps, self.lins, scale, per_sample=self._target_n > 1)
+        else:
+            g = f.backward(self._target_taps, self.lins, scale, per_sample=self._target_n > 1, region=region)
         if not accumulate:
             dimg.zero_()
         dimg[:, :, :g.shape[2], :g.shape[3]].add_(g)
@@ -661,7 +760,8 @@ class PerceptualLoss(torch.nn.Module):
             self._scratch = torch.empty(need, dtype=torch.float32, device=self.device_)
         self._last, self._last_hw = (f, tuple(pred.shape[2:])) if keep_taps else (None, None)
         f.tap_stats = {}                            # tap index -> per-pixel sums of this forward (keep_taps only)
-        if self.fused_stem and not keep_taps and not per_sample:
+        region = self._region_for(n, pred.shape[2], pred.shape[3])
+        if self.fused_stem and not keep_taps and not per_sample and region is None:
             f.stem(pred.contiguous(), feat_ref=self._target_taps[0], lin=self.lins[0], dist_out=out, scratch=self._scratch)
             taps = f(pred, from_pooled=True)
         else:
@@ -688,6 +788,14 @@ class PerceptualLoss(torch.nn.Module):
                     stats = self._stats[key] = torch.empty(n, 3, hh * ww, dtype=torch.float32, device=self.device_)
                 f.tap_stats[i] = stats
             got = C.c_int32(0)
+            if region is not None:                  # the partials are of omega[p] d[p] with omega normalised: no 1 / hw
+                _lib.check(L.mgf_lpips_layer_defer_weighted_f32(self._scratch[k * n * red:].data_ptr(), _lib.ptr(stats), a.data_ptr(), b.data_ptr(),
+                                                                lin.data_ptr(), region[0][i].data_ptr(), n, c, hh * ww,
+                                                                c * hh * ww if per_sample else 0, hh * ww if region[1] > 1 else 0, C.byref(got), st),
+                           "lpips_layer_weighted")
+                nparts[k], scales[k] = got.value, 1.0
+                k += 1
+                continue
             _lib.check(L.mgf_lpips_layer_defer_f32(self._scratch[k * n * red:].data_ptr(), _lib.ptr(stats), a.data_ptr(), b.data_ptr(), lin.data_ptr(),
                                                    n, c, hh * ww, c * hh * ww if per_sample else 0, C.byref(got), st), "lpips_layer")
             nparts[k], scales[k] = got.value, 1.0 / float(hh * ww)
@@ -710,7 +818,8 @@ class PerceptualLoss(torch.nn.Module):
             self._scratch = torch.empty(need, dtype=torch.float32, device=self.device_)
         out = torch.zeros(len(self.chns), n, dtype=torch.float32, device=self.device_)
         f.tap_stats = {}
-        if self.fused_stem and not per_sample:
+        region = self._region_for(n, pred.shape[2], pred.shape[3])
+        if self.fused_stem and not per_sample and region is None:
             f.stem(pred.contiguous(), feat_ref=self._target_taps[0], lin=self.lins[0], dist_out=out[0], scratch=self._scratch)
             taps = f(pred, from_pooled=True)
         else:
@@ -720,6 +829,15 @@ class PerceptualLoss(torch.nn.Module):
             if a is None:
                 continue
             _, c, hh, ww = a.shape
+            if region is not None:
+                import ctypes as C
+                got, one = C.c_int32(0), (C.c_float * 8)(1.0)
+                _lib.check(L.mgf_lpips_layer_defer_weighted_f32(self._scratch.data_ptr(), None, a.data_ptr(), b.data_ptr(), lin.data_ptr(),
+                                                                region[0][i].data_ptr(), n, c, hh * ww, c * hh * ww if per_sample else 0,
+                                                                hh * ww if region[1] > 1 else 0, C.byref(got), st), "lpips_layer_weighted")
+                _lib.check(L.mgf_lpips_finish_taps_f32(out[i].data_ptr(), self._scratch.data_ptr(), n * int(L.mgf_reduce_scratch_floats()), 1,
+                                                       (C.c_int32 * 8)(got.value), one, n, 0, st), "lpips_finish_taps")
+                continue
             _lib.check(L.mgf_lpips_layer_stats_f32(out[i].data_ptr(), None, a.data_ptr(), b.data_ptr(), lin.data_ptr(), n, c, hh * ww,
                                                    c * hh * ww if per_sample else 0, 0, self._scratch.data_ptr(), st), "lpips_layer")
         return out
@@ -809,6 +927,12 @@ class PerceptualLoss(torch.nn.Module):
             return (val, res) if retPerLayer else val
         if retPerLayer:
             raise NotImplementedError("retPerLayer=True is implemented for spatial=True; `distance_per_tap` returns the per-tap values otherwise")
+        if self._region is not None and self._region.shape[0] > 1:
+            # one region weight per image: n targets pair up with n images and n weights in one evaluation
+            self.set_target(target.float().contiguous())
+            vals = torch.empty(n, dtype=torch.float32, device=self.device_)
+            self.distance_into(vals, pred.float().contiguous())
+            return vals.reshape(n, 1, 1, 1)
         vals = []
         for i in range(n):      # per-sample values like the reference's [N,1,1,1]; the loop only ever uses N == 1
             # like the reference, the module-call form recomputes the target features on every call; the projection

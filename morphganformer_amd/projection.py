@@ -141,7 +141,7 @@ class ProjectionEngine:
     def __init__(self, G, target, latent_mean, latent_std, args: ProjectionArgs = None, percept=None, use_mse=True,
                  lm_target=None, lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, batch=1,
                  landmark_fn=None, biometric=None, gamma=1.0, wing_kind="wing", landmark_model=None, pipeline=False, keep_images=0,
-                 latent_shape=None, landmark_input="float", lbp_target=None, mdf=None):
+                 latent_shape=None, landmark_input="float", lbp_target=None, mdf=None, region_weight=None):
         """batch = number of consecutive loop steps evaluated per generator forward.  In literal mode the steps do not depend
         on each other (latent_in never changes), so evaluating `batch` candidates at once and examining them in step order
         gives exactly the sequential loop's result while the small 4x4..64x64 layers, the mapping network and the LPIPS tail
@@ -183,7 +183,12 @@ class ProjectionEngine:
         BGR2GRAY on RGB data), made ON THE DEVICE (mgf_reference_gray_u8, bit-identical to drivers.reference_gray_u8) and copied into
         pinned host memory -- 1 MB per candidate -- and the launch sequence stays two captured hipGraphs with the host detour between
         them: {perturb, generator, gray image, device->host copy} | callbacks, one host->device copy of the landmark rows | {losses,
-        selection}."""
+        selection}.
+
+        region_weight: a map W [H,W] (or [1,1,H,W]) >= 0 with a positive sum, at the size the image-space losses see (the pooled size with
+        pool_above): the LPIPS term becomes sum_l sum_p omega_l[p] m_l[p] (PerceptualLoss.set_region_weight) and the pixel term
+        sum_c sum_p W[p] (x - t)^2 / (C sum W) (mgf_mse_weighted_f32).  A constant W is today's objective.  Wing, biometric and MDF terms
+        ignore it; the DSSIM / PSNR / LBP pixel terms and latent_copies > 1 refuse it."""
         self.G, self.args = G, args or ProjectionArgs()
         self.batch = int(batch)
         assert self.batch >= 1
@@ -278,6 +283,7 @@ class ProjectionEngine:
             if nbytes <= 0:
                 raise _lib.MgfError(f"projection: pixel_term='dssim' needs images of at least 7x7 pixels, got {h}x{w}")
             self.dssim_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        self._init_region(region_weight)
         if self.percept is not None:
             self.percept.set_target(self.target)
         self.biometric, self.gamma = biometric, float(gamma)
@@ -329,6 +335,41 @@ class ProjectionEngine:
             self._parity = 0
             self._primed = False
             self._seq_launched = 0                                                # host count of launch sequences since the last rewind
+
+    def _init_region(self, region_weight):
+        """The region weight of the image-space terms (None: uniform means, today's kernels).  `pix_w` [nw, H W] holds W / (C sum W), what
+        the weighted pixel kernels multiply by; the LPIPS module keeps its per-tap weights itself.  Both are rewritten in place by
+        retarget(region_weight=): captured graphs read them."""
+        a = self.args
+        self.pix_w = None
+        if region_weight is None:
+            if self.percept is not None and hasattr(self.percept, "set_region_weight"):
+                self.percept.set_region_weight(None)
+            return
+        if a.pixel_term != "mse":
+            raise _lib.MgfError(f"projection: pixel_term={a.pixel_term!r} does not take a region_weight: the weighted window forms (DSSIM's 7x7 "
+                                "windows, the PSNR script's element order, the LBP histogram) are not built; use pixel_term='mse'")
+        if int(a.latent_copies) > 1:
+            raise _lib.MgfError("projection: latent_copies > 1 (the v2 driver's averaged latent) does not take a region_weight")
+        self._set_region(region_weight)
+
+    def _set_region(self, region_weight):
+        from .lpips import check_region_weight
+        w = check_region_weight(region_weight, "region_weight")
+        nt, C, H, W = self.target.shape
+        if tuple(w.shape[1:]) != (H, W):
+            raise ValueError(f"region_weight is {tuple(w.shape[1:])}, the image-space losses see {(H, W)}")
+        if w.shape[0] not in (1, nt):
+            raise ValueError(f"{w.shape[0]} region weights for {nt} target(s): pass one map, or one per target")
+        pix = (w / (C * w.sum(dim=(1, 2), keepdim=True))).to(torch.float32).reshape(w.shape[0], H * W)
+        if self.pix_w is None:
+            self.pix_w = pix.to(self.device).contiguous()
+        elif tuple(self.pix_w.shape) != tuple(pix.shape):
+            raise ValueError(f"retarget: {w.shape[0]} region weight map(s) where the engine was built with {self.pix_w.shape[0]}")
+        else:
+            self.pix_w.copy_(pix)
+        if self.percept is not None:
+            self.percept.set_region_weight(w[:, None])
 
     def _init_pool(self, B):
         """projection_example_v1.py:150-155: images above `pool_above` pixels are block-averaged by height // pool_above in front of the
@@ -385,6 +426,10 @@ class ProjectionEngine:
             c, h, w = img.shape[1:]
             _lib.check(L.mgf_dssim_u8_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, c, h, w, 0, 255.0, 1.0, 0,
                                           self.dssim_scratch.data_ptr(), st), "dssim")
+        elif self.use_mse and self.pix_w is not None:
+            c, hw = img.shape[1], img.shape[2] * img.shape[3]
+            _lib.check(L.mgf_mse_weighted_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.pix_target.data_ptr(), self.pix_w.data_ptr(), B, c, hw,
+                                              0, 0, 1.0, 0, self.scratch.data_ptr(), st), "mse_weighted")
         elif self.use_mse:
             per = img.numel() // B
             _lib.check(L.mgf_mse_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.pix_target.data_ptr(), B, per, 0, 1.0, 0,
@@ -693,7 +738,7 @@ class ProjectionEngine:
         return target.permute(0, 2, 3, 1).contiguous().view(target.shape)
 
     def retarget(self, target, lm_target=None, lm_steps=None, lm_valid=None, eps=None, seed=None, latent_mean=None, latent_std=None,
-                 lbp_target=None):
+                 lbp_target=None, region_weight=None):
         """Point this engine at ANOTHER target image and rewind the loop, keeping everything that was expensive to set up: the captured
         hipGraph(s), the generator workspace, the LPIPS / embedder workspaces, the loss scratch.  Only data changes, in place, in the
         buffers the graph already references: the target image and its cached LPIPS taps / embedding, the landmark tables, the noise
@@ -701,11 +746,17 @@ class ProjectionEngine:
         counter, best-so-far, loss history, improvement trail).  A run after retarget() equals the run of a freshly constructed engine
         on the same inputs bit for bit (tests/test_hip_drivers.py).  This is what the reference's serial per-image loop amortises by
         keeping G / percept / latent statistics outside `projection()` (projection_example_v2_percept_morph.py:311-355); BASELINE
-        configs 3 and 5 are batches of targets."""
+        configs 3 and 5 are batches of targets.  region_weight: the new target's region weight, written into the weight buffers in place (an
+        engine built with a weight; without the argument the weight stays)."""
         a, dev = self.args, self.device
         _lib.require_gpu(target)
         assert tuple(target.shape) == tuple(self.target.shape), (tuple(target.shape), tuple(self.target.shape))
         torch.cuda.synchronize(dev)
+        if region_weight is not None:
+            if self.pix_w is None:
+                raise _lib.MgfError("retarget: this engine was built without a region_weight (its launch sequence holds the un-weighted kernels); "
+                                    "build a fresh one")
+            self._set_region(region_weight)
         self.target.copy_(target)
         if self.pix_target is not self.target:
             self.pix_target.copy_(self._script_order(self.target))
@@ -806,7 +857,7 @@ class GradientProjectionEngine(ProjectionEngine):
                  lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, landmark_fn=None, biometric=None,
                  gamma=1.0, wing_kind="wing", landmark_model=None, betas=(0.9, 0.999), adam_eps=1e-8, weight_decay=0.0,
                  latent_space="z", mdf=None, optimize_noise=False, noise_init="randn", target_b=None, morph_alpha=0.5, id_balance=0.0,
-                 id_metric="mse", lm_target_b=None, **ignored):
+                 id_metric="mse", lm_target_b=None, region_weight=None, **ignored):
         """latent_space: "z" -- the drivers' parameter, the gradient runs on through the mapping network -- or "w+": the parameter is the
         per-layer intermediate latent ws [k, num_ws, D] itself (north_star: "backprops into the k-component latent W+"; layer `slot` reads
         ws[:, slot], networks.py:1252-1253), perturbed, descended by Adam and kept best-of exactly like z.  latent_mean is then a w-space
@@ -819,7 +870,10 @@ class GradientProjectionEngine(ProjectionEngine):
         engine-owned tensors (`noise_init`: "randn", seeded, or "const", a copy of every layer's noise_const) the generator runs with
         (`noise_mode` is then irrelevant), the total gains args.noise_regularize * sum over the maps of the regulariser, and every step the maps take
         an Adam step with the latent's learning rate and betas followed by noise_normalize_.  `noises` holds the current maps, `best_noises`
-        those of the best step's image ({layer name: [1, res, res]}), both filled inside the launch sequence.  One target per engine."""
+        those of the best step's image ({layer name: [1, res, res]}), both filled inside the launch sequence.  One target per engine.
+
+        region_weight: as ProjectionEngine's; with B lockstep targets one map for all of them or [B,1,H,W], one per target.  A target pair's
+        constants (alpha (1 - alpha) LPIPS_W(Ta, Tb) and the same of the pixel term) use the weighted values.  The noise regulariser ignores it."""
         from .grad import GeneratorGrad
         pair = self._pair_arguments(target, target_b, morph_alpha, id_balance, id_metric, biometric, mdf, optimize_noise, lm_target, lm_target_b)
         if pair is not None:
@@ -853,11 +907,11 @@ class GradientProjectionEngine(ProjectionEngine):
             super().__init__(G, target, latent_mean, latent_std, args, percept=percept, use_mse=use_mse, lm_target=lm_target,
                              lm_steps=lm_steps, lm_valid=lm_valid, eps=eps, noise_mode=noise_mode, seed=seed, use_graph=use_graph, batch=1,
                              landmark_fn=landmark_fn, biometric=biometric, gamma=gamma, wing_kind=wing_kind,
-                             landmark_model=landmark_model, pipeline=False, latent_shape=ls, mdf=mdf)
+                             landmark_model=landmark_model, pipeline=False, latent_shape=ls, mdf=mdf, region_weight=region_weight)
             self.lm_tables = [self.lm_steps] if self.use_wing else None
         else:
             self._init_multi(G, target, latent_mean, latent_std, args, percept, use_mse, lm_target, lm_steps, lm_valid, eps, noise_mode,
-                             seed, use_graph, biometric, gamma, wing_kind, ls)
+                             seed, use_graph, biometric, gamma, wing_kind, ls, region_weight)
             assert landmark_fn is None and landmark_model is None, "landmark detectors are wired for one target per engine"
         self.targets = B
         a, dev = self.args, self.device
@@ -942,8 +996,14 @@ class GradientProjectionEngine(ProjectionEngine):
         if self.use_mse and not self.use_dssim:
             per = P["ta"].numel() // B
             self.pair_mse_off = torch.zeros(B, dtype=torch.float32, device=dev)
-            _lib.check(L.mgf_mse_f32(self.pair_mse_off.data_ptr(), P["ta"].data_ptr(), P["tb"].data_ptr(), B, per, per, 1.0, 0,
-                                     self.scratch.data_ptr(), st), "mse(target pair)")
+            if self.pix_w is not None:
+                c, hw = P["ta"].shape[1], P["ta"].shape[2] * P["ta"].shape[3]
+                _lib.check(L.mgf_mse_weighted_f32(self.pair_mse_off.data_ptr(), P["ta"].data_ptr(), P["tb"].data_ptr(), self.pix_w.data_ptr(), B, c,
+                                                  hw, per, hw if self.pix_w.shape[0] > 1 else 0, 1.0, 0, self.scratch.data_ptr(), st),
+                           "mse_weighted(target pair)")
+            else:
+                _lib.check(L.mgf_mse_f32(self.pair_mse_off.data_ptr(), P["ta"].data_ptr(), P["tb"].data_ptr(), B, per, per, 1.0, 0,
+                                         self.scratch.data_ptr(), st), "mse(target pair)")
             self.pair_mse_off.mul_(torch.as_tensor(al * (1.0 - al), dtype=torch.float32, device=dev))      # select_best multiplies by beta
         if self.use_dssim:
             self.pair_dssim = torch.zeros(2, B, dtype=torch.float32, device=dev)
@@ -1018,7 +1078,7 @@ class GradientProjectionEngine(ProjectionEngine):
                        "noise_regularize_grad")
 
     def _init_multi(self, G, target, latent_mean, latent_std, args, percept, use_mse, lm_target, lm_steps, lm_valid, eps, noise_mode,
-                    seed, use_graph, biometric, gamma, wing_kind, ls):
+                    seed, use_graph, biometric, gamma, wing_kind, ls, region_weight=None):
         """Loop state of B lockstep projections (the single-target layout of ProjectionEngine with a leading B axis)."""
         self.G, self.args = G, args or ProjectionArgs()
         a, dev = self.args, G.device
@@ -1060,6 +1120,7 @@ class GradientProjectionEngine(ProjectionEngine):
         self.mse_loss = torch.zeros(B, dtype=torch.float32, device=dev)
         self.w_loss = torch.zeros(B, dtype=torch.float64, device=dev)
         self.scratch = torch.empty(B * int(_lib.lib().mgf_reduce_scratch_floats()), dtype=torch.float32, device=dev)
+        self._init_region(region_weight)
         if percept is not None:
             percept.set_target(self.target)
         self.biometric, self.gamma = biometric, float(gamma)
@@ -1113,6 +1174,10 @@ class GradientProjectionEngine(ProjectionEngine):
             c, h, w = img.shape[1:]
             _lib.check(L.mgf_dssim_grad_f32(self.dimg.data_ptr(), self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, c, h, w, tstride,
                                             255.0, float(a.beta), 0, 0, self.dssim_scratch.data_ptr(), st), "dssim_grad")
+        elif self.use_mse and self.pix_w is not None:
+            c, hw = img.shape[1], img.shape[2] * img.shape[3]
+            _lib.check(L.mgf_mse_weighted_grad_f32(self.dimg.data_ptr(), img.data_ptr(), self.target.data_ptr(), self.pix_w.data_ptr(), B, c, hw,
+                                                   tstride, hw if self.pix_w.shape[0] > 1 else 0, float(a.beta), 0, st), "mse_weighted_grad")
         elif self.use_mse:
             _lib.check(L.mgf_mse_grad_f32(self.dimg.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, per, tstride, float(a.beta), 0,
                                           st), "mse_grad")
@@ -1131,7 +1196,13 @@ class GradientProjectionEngine(ProjectionEngine):
         if self.mdf is not None:            # p_loss (+)= MDF, dimg += d MDF / d img (1024_example_mdfloss.py:165 without the detach)
             self.mdf.distance_into(self.p_loss, img, accumulate=self.percept is not None or self.biometric is not None, dimg=self.dimg,
                                    grad_accumulate=True)
-        if self.use_mse and not self.use_dssim:
+        if self.use_mse and not self.use_dssim and self.pix_w is not None:
+            c, hw = img.shape[1], img.shape[2] * img.shape[3]
+            _lib.check(L.mgf_mse_weighted_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), self.pix_w.data_ptr(), B, c, hw,
+                                              tstride, hw if self.pix_w.shape[0] > 1 else 0, 1.0, 0, self.scratch.data_ptr(), st), "mse_weighted")
+            if pair is not None:
+                self.mse_loss.add_(self.pair_mse_off)
+        elif self.use_mse and not self.use_dssim:
             _lib.check(L.mgf_mse_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, per, tstride, 1.0, 0,
                                      self.scratch.data_ptr(), st), "mse")
             if pair is not None:
