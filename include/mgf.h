@@ -413,6 +413,35 @@ int mgf_dssim_f32(float* out, const float* img, const float* target, int32_t n, 
 int mgf_dssim_grad_f32(float* dimg, float* out, const float* img, const float* target, int32_t n, int32_t c, int32_t h, int32_t w,
                        int64_t t_batch_stride, float data_range, float scale, int32_t accumulate_dimg, int32_t accumulate_out, void* scratch,
                        mgf_stream_t stream);
+/* msssim: multi-scale SSIM (Wang, Simoncelli, Bovik 2003, as the common libraries implement it) as a loss, value and gradient (csrc/msssim.hip).
+ *        The reference tree has no such term; this comment is its definition.  img [n,c,h,w], unclamped; target [c,h,w] (t_batch_stride 0) or one
+ *        per sample.  Pixels p = 127.5 img + 127.5, q = 127.5 target + 127.5 (no rint, no clip); C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2;
+ *        float32 loads, float64 arithmetic in a fixed order, no atomics (bit-reproducible).
+ *        Window: 11 taps g[i] ~ exp(-(i - 5)^2 / (2 1.5^2)), normalised to sum 1, separable (rows, then columns), at the positions whose window lies
+ *        whole inside the level's image ((h_j - 10) x (w_j - 10) of them; never clamped).  Per position, with the windowed means ux, uy, exx, eyy,
+ *        exy of p, q, pp, qq, pq:  vx = exx - ux ux, vy = eyy - uy uy, vxy = exy - ux uy (biased covariance; the products are stand-alone
+ *        multiplies),  cs = (2 vxy + C2) / (vx + vy + C2),  l = (2 ux uy + C1) / (ux ux + uy uy + C1),  ssim = l cs.
+ *        Levels j = 0 .. levels-1 (levels in 1..5): v_j = mean over positions of cs, the last level's of ssim.  Level j + 1 is the 2 x 2 mean, stride
+ *        2, of both images of level j; an odd side is zero-padded by one on both ends and the pad counted in the divisor (torch's
+ *        avg_pool2d(x, 2, 2, padding = side % 2): side s -> (s + 1) / 2).  Every level's sides must be >= 11 (else MGF_EINVAL, the message names
+ *        the level and its size).  Per channel ms = prod_j v_j^{weights[j]} if every v_j > 0, otherwise ms = 0 AND ITS GRADIENT IS ZERO (never NaN or
+ *        inf).  msssim_loss = 1 - mean over channels of ms; identical images give exactly 0.
+ *        weights: `levels` float64 values on the HOST, read at call time and passed to the kernels by value (a captured launch sequence carries
+ *        them).  scratch: mgf_msssim_scratch_bytes(n,c,h,w,levels) bytes (0: a size or level count the term does not take), 8-byte aligned: the
+ *        float64 pyramids of both images, the pyramid of gradients, one partial per workgroup and level, the coefficients.
+ *   mgf_msssim_f32:       out[i] (+)= scale * msssim_loss(img[i], target)
+ *   mgf_msssim_grad_f32:  dimg[i] (+)= scale * d msssim_loss(img[i], target) / d img[i], and, when out is not NULL, out[i] (+)= the UNSCALED loss, the
+ *                         bits of mgf_msssim_f32(scale = 1).  d ms / d v_j = w_j ms / v_j; level j's own part of the gradient of its image is
+ *                         -(scale w_j ms / (v_j c positions_j)) sum_pos g(pos - pix) (ga + 2 p gb + q gc) -- three adjoint Gaussian filters of
+ *                         per-position maps -- with, for cs, B2 = vx + vy + C2: ga = 2 (cs ux - uy) / B2, gb = -cs / B2, gc = 2 / B2, and for the
+ *                         last level's ssim, B1 = ux ux + uy uy + C1: ga_s = cs (2 uy - 2 l ux) / B1 + l ga, gb_s = l gb, gc_s = l gc.  A level
+ *                         receives 1/4 of its parent pixel's gradient (the adjoint of the 2 x 2 mean); dimg = 127.5 x the gradient at level 0. */
+int64_t mgf_msssim_scratch_bytes(int32_t n, int32_t c, int32_t h, int32_t w, int32_t levels);
+int mgf_msssim_f32(float* out, const float* img, const float* target, int32_t n, int32_t c, int32_t h, int32_t w, int64_t t_batch_stride,
+                   const double* weights, int32_t levels, float data_range, float scale, int32_t accumulate, void* scratch, mgf_stream_t stream);
+int mgf_msssim_grad_f32(float* dimg, float* out, const float* img, const float* target, int32_t n, int32_t c, int32_t h, int32_t w,
+                        int64_t t_batch_stride, const double* weights, int32_t levels, float data_range, float scale, int32_t accumulate_dimg,
+                        int32_t accumulate_out, void* scratch, mgf_stream_t stream);
 /* The LBP matching distance of 1024_example_LBP_percept.py:34-58,162-166 per candidate, in three steps (csrc/lbp.hip):
  *   lbp_gray224:  gray [n,224,224] u8 = cv2.resize(cv2.cvtColor(to_pil(img), COLOR_BGR2GRAY), (224, 224)) of img [n,3,h,w] in [-1, 1]: misc.to_pil's
  *                 rint quantisation (misc.py:115-116), OpenCV's 8-bit gray weights (1868, 9617, 4899, >> 14) with the FIRST channel in the blue

@@ -114,6 +114,9 @@ _SIGS = {
     "mgf_dssim_u8_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i64, f32, f32, i32, vp, vp]),
     "mgf_dssim_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i64, f32, f32, i32, vp, vp]),
     "mgf_dssim_grad_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i64, f32, f32, i32, i32, vp, vp]),
+    "mgf_msssim_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
+    "mgf_msssim_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i64, vp, i32, f32, f32, i32, vp, vp]),
+    "mgf_msssim_grad_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, i32, f32, f32, i32, i32, vp, vp]),
     "mgf_lbp_scratch_bytes": (i64, [i32]),
     "mgf_lbp_gray224_u8": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "mgf_lbp_codes_u8": (C.c_int, [vp, vp, vp, i32, vp]),

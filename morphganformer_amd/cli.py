@@ -50,12 +50,15 @@ def _loop_arguments(p):
                    help="with --mode gradient: optimise the per-layer latent W+ [k, num_ws, D] instead of z (the reference accepts the flag "
                         "and never reads it; in literal mode it stays unused here too)")
     p.add_argument("--percept_weight", type=float, default=1.0, help="coefficient of the LPIPS term (0.5 with --beta 0.5 = 1024_example_percept_MSE.py)")
-    p.add_argument("--pixel-term", choices=["mse", "psnr", "dssim", "lbp"], default="mse",
+    p.add_argument("--pixel-term", choices=["mse", "psnr", "dssim", "lbp", "msssim"], default="mse",
                    help="psnr = the pixel term of 1024_example_PSNR.py (10 log10(255^2 / MSE), minimised like the script does, and -- see --psnr-layout -- "
                         "with the script's element order; use with --no-lpips); "
                         "dssim = (1 - SSIM) / 2 (1024_example_SSIM.py's `dssim`): of the uint8 images in literal mode, of the unquantised pixels with --mode gradient "
                         "(the quantisation has no gradient; the two agree on uint8-grid images); lbp = the LBP matching distance of "
-                        "1024_example_LBP_percept.py, the whole objective of that script (use with --no-lpips; literal mode)")
+                        "1024_example_LBP_percept.py, the whole objective of that script (use with --no-lpips; literal mode); msssim = 1 - multi-scale SSIM "
+                        "(11-tap Gaussian windows, --msssim-levels levels) of the unquantised pixels, in both modes")
+    p.add_argument("--msssim-levels", type=int, default=5,
+                   help="--pixel-term msssim: levels of the 2 x 2 mean pyramid, 1..5 (every level's sides must be >= 11: 64 x 64 allows 3)")
     p.add_argument("--psnr-layout", choices=["script", "aligned"], default="script",
                    help="script = 1024_example_PSNR.py:150-158 as written: the candidate's C-H-W stream against the target's H-W-C stream (different pixels "
                         "are paired); aligned = the PSNR of corresponding pixels (a deviation from the script)")
@@ -124,7 +127,8 @@ def _refine_arguments(m):
     m.add_argument("--noise", type=float, default=0.05)
     m.add_argument("--n_mean_latent", type=int, default=10000)
     m.add_argument("--percept_weight", type=float, default=1.0)
-    m.add_argument("--pixel-term", choices=["mse", "dssim"], default="mse")
+    m.add_argument("--pixel-term", choices=["mse", "dssim", "msssim"], default="mse")
+    m.add_argument("--msssim-levels", type=int, default=5, help="--pixel-term msssim: pyramid levels, 1..5 (every level's sides must be >= 11)")
     m.add_argument("--no-mse", action="store_true")
     m.add_argument("--latent-space", choices=["auto", "z", "w+"], default="auto",
                    help="--refine: the space of --w1 / --w2 (auto = by their shape: [1,k,D] is z, [1,k,num_ws,D] is W+)")
@@ -153,7 +157,7 @@ def _refine(a, G, alphas):
     if a.latent_space not in ("auto", space):
         raise SystemExit(f"morph --refine: --latent-space {a.latent_space} but {a.w1} holds a {space} latent {w1.shape}")
     args = ProjectionArgs(step=a.step, lamda=a.lamda, beta=a.beta, lr=a.lr, noise=a.noise, n_mean_latent=a.n_mean_latent, ratio=a.ratio,
-                          percept_weight=a.percept_weight, pixel_term=a.pixel_term)
+                          percept_weight=a.percept_weight, pixel_term=a.pixel_term, msssim_levels=a.msssim_levels)
     percept = None
     if not a.no_lpips:
         if a.lpips_backbone is None and not a.lpips_random_backbone:
@@ -406,7 +410,7 @@ def main(argv=None):
     args = ProjectionArgs(step=a.step, lamda=a.lamda, beta=a.beta, lr=a.lr, lr_rampup=a.lr_rampup, lr_rampdown=a.lr_rampdown,
                           noise=a.noise, noise_ramp=a.noise_ramp, truncation_psi=a.truncation_psi, n_mean_latent=a.n_mean_latent,
                           ratio=a.ratio, percept_weight=a.percept_weight, pixel_term=a.pixel_term, psnr_layout=a.psnr_layout, pool_above=a.pool_above,
-                          latent_copies=a.latent_copies, min_loss_init=a.min_loss_init, noise_regularize=a.noise_regularize)
+                          latent_copies=a.latent_copies, min_loss_init=a.min_loss_init, noise_regularize=a.noise_regularize, msssim_levels=a.msssim_levels)
     percept = None
     if not a.no_lpips:
         if a.lpips_backbone is None and not a.lpips_random_backbone:

@@ -65,7 +65,13 @@ class ProjectionArgs:
     # "lbp": the matching distance of 1024_example_LBP_percept.py:34-58,162-166 -- 1 - cos(LBP(24, 3, 'uniform') code map of the saved image at
     # 224 x 224, the target file's code map) in float64 -- in place of every other term (the script scores nothing else); needs
     # ProjectionEngine(lbp_target=lbp.target_feature(file pixels))
+    # "msssim": 1 - multi-scale SSIM (Wang, Simoncelli, Bovik 2003: 11-tap Gaussian windows, sigma 1.5, `msssim_levels` levels of a 2 x 2 mean pyramid,
+    # the usual level weights renormalised over the levels in use -- msssim_weights), the structural term of the MIPGAN family of morph optimisers.
+    # The reference tree has no such script; the definition is include/mgf.h's (mgf_msssim_f32).  BOTH loops use the continuous form on the
+    # unquantised pixels 127.5 x + 127.5 (no script defines a quantised one): the literal loop scores with mgf_msssim_f32, gradient mode descends
+    # mgf_msssim_grad_f32.  Every level's sides must be >= 11: 1024^2, 256^2 and 161 x 176 take five levels, 64^2 three
     pixel_term: str = "mse"
+    msssim_levels: int = 5
     psnr_layout: str = "script"
     # projection_example_v2_percept.py:131-166: the optimised latent holds `latent_copies` (18 there) copies of the start latent, every copy
     # receives its own noise each step and the generator sees their mean (`torch.mean(latent_n, 1)`, reproduced in torch's summation order:
@@ -77,6 +83,29 @@ class ProjectionArgs:
     # `--noise_regularize` of the drivers (:243): the weight of noise_regularize(noises) (:32-52).  Their loop never calls the function (it never
     # back-propagates); GradientProjectionEngine(optimize_noise=True) adds noise_regularize * sum over the maps to its total.  Unused otherwise
     noise_regularize: float = 1e5
+
+    def __post_init__(self):
+        if self.pixel_term == "msssim" and not (isinstance(self.msssim_levels, int) and 1 <= self.msssim_levels <= len(MSSSIM_WEIGHTS)):
+            raise _lib.MgfError(f"projection: msssim_levels must be an integer in 1..{len(MSSSIM_WEIGHTS)} (got {self.msssim_levels!r})")
+
+
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)       # Wang, Simoncelli, Bovik 2003, finest level first
+
+
+def msssim_weights(levels):
+    """The level weights of pixel_term="msssim": the first `levels` of the paper's five, renormalised to sum 1 (one level: plain Gaussian SSIM)."""
+    if not (isinstance(levels, int) and 1 <= levels <= len(MSSSIM_WEIGHTS)):
+        raise _lib.MgfError(f"projection: msssim_levels must be an integer in 1..{len(MSSSIM_WEIGHTS)} (got {levels!r})")
+    w = np.asarray(MSSSIM_WEIGHTS[:levels], dtype=np.float64)
+    return (w / w.sum()).tolist()
+
+
+def msssim_max_levels(h, w):
+    """How many MS-SSIM levels an h x w image allows (every level's sides >= 11; a side s becomes (s + 1) // 2), at most 5."""
+    n = 0
+    while n < len(MSSSIM_WEIGHTS) and min(h, w) >= 11:
+        n, h, w = n + 1, (h + 1) // 2, (w + 1) // 2
+    return n
 
 
 def get_lr(t, initial_lr, rampdown=0.25, rampup=0.05):
@@ -188,7 +217,7 @@ class ProjectionEngine:
         region_weight: a map W [H,W] (or [1,1,H,W]) >= 0 with a positive sum, at the size the image-space losses see (the pooled size with
         pool_above): the LPIPS term becomes sum_l sum_p omega_l[p] m_l[p] (PerceptualLoss.set_region_weight) and the pixel term
         sum_c sum_p W[p] (x - t)^2 / (C sum W) (mgf_mse_weighted_f32).  A constant W is today's objective.  Wing, biometric and MDF terms
-        ignore it; the DSSIM / PSNR / LBP pixel terms and latent_copies > 1 refuse it."""
+        ignore it; the DSSIM / MS-SSIM / PSNR / LBP pixel terms and latent_copies > 1 refuse it."""
         self.G, self.args = G, args or ProjectionArgs()
         self.batch = int(batch)
         assert self.batch >= 1
@@ -265,7 +294,7 @@ class ProjectionEngine:
         self.w_loss = torch.zeros(B, dtype=torch.float64, device=dev)
         self.scratch = torch.empty(B * int(_lib.lib().mgf_reduce_scratch_floats()), dtype=torch.float32, device=dev)
         self._arange = torch.arange(B, dtype=torch.int64, device=dev)
-        assert a.pixel_term in ("mse", "psnr", "dssim", "lbp"), a.pixel_term
+        assert a.pixel_term in ("mse", "psnr", "dssim", "lbp", "msssim"), a.pixel_term
         assert a.psnr_layout in ("script", "aligned"), a.psnr_layout
         # what the pixel term reads as "the target": the image itself, or -- the PSNR script's element order -- its H-W-C stream under the
         # candidate's C-H-W indexing (one permuted copy, refreshed by retarget(); the kernel is the same aligned sum)
@@ -283,6 +312,7 @@ class ProjectionEngine:
             if nbytes <= 0:
                 raise _lib.MgfError(f"projection: pixel_term='dssim' needs images of at least 7x7 pixels, got {h}x{w}")
             self.dssim_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        self._init_msssim(B)
         self._init_region(region_weight)
         if self.percept is not None:
             self.percept.set_target(self.target)
@@ -336,6 +366,25 @@ class ProjectionEngine:
             self._primed = False
             self._seq_launched = 0                                                # host count of launch sequences since the last rewind
 
+    def _init_msssim(self, B):
+        """pixel_term="msssim": the level weights as the float64 host array the entry points read at call time, and the scratch (the float64
+        pyramids of both images and of the gradient, the partials, the coefficients) for B images of the size the image-space losses see."""
+        a = self.args
+        self.use_msssim = bool(self.use_mse) and a.pixel_term == "msssim"
+        if not self.use_msssim:
+            return
+        import ctypes
+        c, h, w = self.target.shape[-3:]
+        weights = msssim_weights(a.msssim_levels)
+        if msssim_max_levels(h, w) < a.msssim_levels:
+            raise _lib.MgfError(f"projection: pixel_term='msssim' with msssim_levels={a.msssim_levels} needs every level's sides to be at least 11 "
+                                f"pixels; a {h}x{w} image allows {msssim_max_levels(h, w)} level(s)")
+        self.msssim_w = (ctypes.c_double * len(weights))(*weights)
+        self.msssim_w_ptr = ctypes.addressof(self.msssim_w)
+        nbytes = int(_lib.lib().mgf_msssim_scratch_bytes(B, c, h, w, a.msssim_levels))
+        assert nbytes > 0, (B, c, h, w, a.msssim_levels)
+        self.msssim_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+
     def _init_region(self, region_weight):
         """The region weight of the image-space terms (None: uniform means, today's kernels).  `pix_w` [nw, H W] holds W / (C sum W), what
         the weighted pixel kernels multiply by; the LPIPS module keeps its per-tap weights itself.  Both are rewritten in place by
@@ -348,7 +397,8 @@ class ProjectionEngine:
             return
         if a.pixel_term != "mse":
             raise _lib.MgfError(f"projection: pixel_term={a.pixel_term!r} does not take a region_weight: the weighted window forms (DSSIM's 7x7 "
-                                "windows, the PSNR script's element order, the LBP histogram) are not built; use pixel_term='mse'")
+                                "windows, MS-SSIM's Gaussian windows, the PSNR script's element order, the LBP histogram) are not built; "
+                                "use pixel_term='mse'")
         if int(a.latent_copies) > 1:
             raise _lib.MgfError("projection: latent_copies > 1 (the v2 driver's averaged latent) does not take a region_weight")
         self._set_region(region_weight)
@@ -426,6 +476,10 @@ class ProjectionEngine:
             c, h, w = img.shape[1:]
             _lib.check(L.mgf_dssim_u8_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, c, h, w, 0, 255.0, 1.0, 0,
                                           self.dssim_scratch.data_ptr(), st), "dssim")
+        elif self.use_msssim:               # the continuous form (see ProjectionArgs); the B candidates share one target pyramid
+            c, h, w = img.shape[1:]
+            _lib.check(L.mgf_msssim_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, c, h, w, 0, self.msssim_w_ptr,
+                                        a.msssim_levels, 255.0, 1.0, 0, self.msssim_scratch.data_ptr(), st), "msssim")
         elif self.use_mse and self.pix_w is not None:
             c, hw = img.shape[1], img.shape[2] * img.shape[3]
             _lib.check(L.mgf_mse_weighted_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.pix_target.data_ptr(), self.pix_w.data_ptr(), B, c, hw,
@@ -833,7 +887,7 @@ class GradientProjectionEngine(ProjectionEngine):
     """Gradient mode: the same loop with the loss back-propagated into the latent.
 
         latent_n = latent_in + eps_i * sigma_i;  img = G(latent_n)
-        total = percept_weight * LPIPS + lamda * Wing + beta * (MSE | DSSIM) [+ gamma * embedding MSE]     (Wing's landmarks come from a
+        total = percept_weight * LPIPS + lamda * Wing + beta * (MSE | DSSIM | MS-SSIM) [+ gamma * embedding MSE]     (Wing's landmarks come from a
                                                                                                            detector: no gradient)
         latent_in <- Adam(lr_i = get_lr(i / steps)).step(d total / d latent_in);  keep (latent_n, i) if total < min_loss
 
@@ -894,11 +948,11 @@ class GradientProjectionEngine(ProjectionEngine):
         if a.latent_copies != 1:
             raise _lib.MgfError("GradientProjectionEngine: latent_copies is the literal-mode v2 driver's averaged latent (projection_example_v2_percept.py); "
                                 "gradient mode optimises one latent")
-        if a.pixel_term not in ("mse", "dssim") or a.pool_above:
+        if a.pixel_term not in ("mse", "dssim", "msssim") or a.pool_above:
             raise _lib.MgfError("GradientProjectionEngine: pixel_term='psnr', pixel_term='lbp' and pool_above are literal-mode objectives with no backward pass "
                                 "here: PSNR as the script minimises it descends towards a LARGER error, the LBP distance is a histogram of integer codes "
                                 "(its gradient is zero almost everywhere), and pool_above is the v1 driver's block mean in front of the losses, which has "
-                                "no adjoint kernel; gradient mode descends Wing / LPIPS / MSE / DSSIM / biometric / MDF")
+                                "no adjoint kernel; gradient mode descends Wing / LPIPS / MSE / DSSIM / MS-SSIM / biometric / MDF")
         assert latent_space in ("z", "w+"), latent_space
         self.latent_space = latent_space
         ls = (G.cfg.k, G.cfg.num_ws, G.cfg.w_dim) if latent_space == "w+" else (G.cfg.k, G.cfg.z_dim)
@@ -916,6 +970,7 @@ class GradientProjectionEngine(ProjectionEngine):
         self.targets = B
         a, dev = self.args, self.device
         self.use_dssim = self.use_mse and a.pixel_term == "dssim"
+        self.win_term = self.use_dssim or self.use_msssim           # a window term: value and gradient from its own kernels, not the MSE ones
         if biometric is not None and hasattr(biometric.embedder, "keep_activations"):
             biometric.embedder.keep_activations = True          # (the FaceNet embedder re-uses its buffers block after block otherwise)
         self.gg = GeneratorGrad(G)
@@ -984,8 +1039,8 @@ class GradientProjectionEngine(ProjectionEngine):
     def _init_pair(self, id_balance, id_metric):
         """Two identities per projection (morph refinement).  Every quadratic term against (Ta weighted 1 - alpha, Tb weighted alpha) equals
         the same term against one blended target plus a constant, so LPIPS, MSE and their backward run once per step on blends -- the cached
-        unit taps (PerceptualLoss.set_target_pair) and the pixel blend `self.target` -- and the constants are added on the device; DSSIM is
-        evaluated against both targets; the identity term (balance |d_a - d_b|, cosine metric) is mgf_embed_pair_loss_f32."""
+        unit taps (PerceptualLoss.set_target_pair) and the pixel blend `self.target` -- and the constants are added on the device; DSSIM and
+        MS-SSIM are evaluated against both targets; the identity term (balance |d_a - d_b|, cosine metric) is mgf_embed_pair_loss_f32."""
         P, a, dev, B = self.pair, self.args, self.device, self.targets
         L, st = _lib.lib(), _lib.stream_ptr()
         al = P["alpha"]
@@ -993,7 +1048,7 @@ class GradientProjectionEngine(ProjectionEngine):
         if self.percept is not None:
             self.percept.set_target_pair(P["ta"], P["tb"], al)
             self.pair_p_off = self.percept.pair_offset * float(a.percept_weight)          # percept_weight * alpha (1 - alpha) LPIPS(Ta, Tb)
-        if self.use_mse and not self.use_dssim:
+        if self.use_mse and not self.win_term:
             per = P["ta"].numel() // B
             self.pair_mse_off = torch.zeros(B, dtype=torch.float32, device=dev)
             if self.pix_w is not None:
@@ -1005,7 +1060,7 @@ class GradientProjectionEngine(ProjectionEngine):
                 _lib.check(L.mgf_mse_f32(self.pair_mse_off.data_ptr(), P["ta"].data_ptr(), P["tb"].data_ptr(), B, per, per, 1.0, 0,
                                          self.scratch.data_ptr(), st), "mse(target pair)")
             self.pair_mse_off.mul_(torch.as_tensor(al * (1.0 - al), dtype=torch.float32, device=dev))      # select_best multiplies by beta
-        if self.use_dssim:
+        if self.win_term:
             self.pair_dssim = torch.zeros(2, B, dtype=torch.float32, device=dev)
             self.pair_w = torch.as_tensor(np.stack([1.0 - al, al]), dtype=torch.float32, device=dev)
         if self.biometric is not None:
@@ -1135,6 +1190,18 @@ class GradientProjectionEngine(ProjectionEngine):
             if nbytes <= 0:
                 raise _lib.MgfError(f"projection: pixel_term='dssim' needs images of at least 7x7 pixels, got {h}x{w}")
             self.dssim_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        self._init_msssim(B)
+
+    def _window_grad(self, dimg, out, img, tgt, n, tstride, scale, accumulate):
+        """dimg (+)= scale * d term / d img and out = the unscaled value, of the window term in use (the continuous DSSIM or MS-SSIM)."""
+        L, st, a = _lib.lib(), _lib.stream_ptr(), self.args
+        c, h, w = img.shape[-3:]
+        if self.use_msssim:
+            _lib.check(L.mgf_msssim_grad_f32(dimg.data_ptr(), out.data_ptr(), img.data_ptr(), tgt.data_ptr(), n, c, h, w, tstride, self.msssim_w_ptr,
+                                             a.msssim_levels, 255.0, scale, accumulate, 0, self.msssim_scratch.data_ptr(), st), "msssim_grad")
+        else:
+            _lib.check(L.mgf_dssim_grad_f32(dimg.data_ptr(), out.data_ptr(), img.data_ptr(), tgt.data_ptr(), n, c, h, w, tstride, 255.0, scale,
+                                            accumulate, 0, self.dssim_scratch.data_ptr(), st), "dssim_grad")
 
     def _state(self):
         st = super()._state() + (self.latent_in, self.exp_avg, self.exp_avg_sq, self.adam_t)
@@ -1161,19 +1228,15 @@ class GradientProjectionEngine(ProjectionEngine):
         per = img.numel() // B
         tstride = per if B > 1 else 0
         pair = self.pair
-        if self.use_dssim and pair is not None:
-            # DSSIM is not quadratic in the image: both targets, sample by sample (the weight is the sample's own), gradients accumulated
-            c, h, w = img.shape[1:]
+        if self.win_term and pair is not None:
+            # DSSIM / MS-SSIM are not quadratic in the image: both targets, sample by sample (the weight is the sample's own), gradients accumulated
             for t, tgt in enumerate((pair["ta"], pair["tb"])):
                 for j in range(B):
                     wt = float(pair["alpha"][j]) if t else 1.0 - float(pair["alpha"][j])
-                    _lib.check(L.mgf_dssim_grad_f32(self.dimg[j:].data_ptr(), self.pair_dssim[t, j:].data_ptr(), img[j:].data_ptr(), tgt[j:].data_ptr(),
-                                                    1, c, h, w, 0, 255.0, float(a.beta) * wt, t, 0, self.dssim_scratch.data_ptr(), st), "dssim_grad")
+                    self._window_grad(self.dimg[j:], self.pair_dssim[t, j:], img[j:], tgt[j:], 1, 0, float(a.beta) * wt, t)
             torch.sum(self.pair_dssim * self.pair_w, 0, out=self.mse_loss)
-        elif self.use_dssim:                 # dimg = beta * d dssim / d img and the unscaled value, one pass (the continuous DSSIM, see ProjectionArgs)
-            c, h, w = img.shape[1:]
-            _lib.check(L.mgf_dssim_grad_f32(self.dimg.data_ptr(), self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, c, h, w, tstride,
-                                            255.0, float(a.beta), 0, 0, self.dssim_scratch.data_ptr(), st), "dssim_grad")
+        elif self.win_term:                  # dimg = beta * d term / d img and the unscaled value, one call (the continuous forms, see ProjectionArgs)
+            self._window_grad(self.dimg, self.mse_loss, img, self.target, B, tstride, float(a.beta), 0)
         elif self.use_mse and self.pix_w is not None:
             c, hw = img.shape[1], img.shape[2] * img.shape[3]
             _lib.check(L.mgf_mse_weighted_grad_f32(self.dimg.data_ptr(), img.data_ptr(), self.target.data_ptr(), self.pix_w.data_ptr(), B, c, hw,
@@ -1196,13 +1259,13 @@ class GradientProjectionEngine(ProjectionEngine):
         if self.mdf is not None:            # p_loss (+)= MDF, dimg += d MDF / d img (1024_example_mdfloss.py:165 without the detach)
             self.mdf.distance_into(self.p_loss, img, accumulate=self.percept is not None or self.biometric is not None, dimg=self.dimg,
                                    grad_accumulate=True)
-        if self.use_mse and not self.use_dssim and self.pix_w is not None:
+        if self.use_mse and not self.win_term and self.pix_w is not None:
             c, hw = img.shape[1], img.shape[2] * img.shape[3]
             _lib.check(L.mgf_mse_weighted_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), self.pix_w.data_ptr(), B, c, hw,
                                               tstride, hw if self.pix_w.shape[0] > 1 else 0, 1.0, 0, self.scratch.data_ptr(), st), "mse_weighted")
             if pair is not None:
                 self.mse_loss.add_(self.pair_mse_off)
-        elif self.use_mse and not self.use_dssim:
+        elif self.use_mse and not self.win_term:
             _lib.check(L.mgf_mse_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, per, tstride, 1.0, 0,
                                      self.scratch.data_ptr(), st), "mse")
             if pair is not None:
