@@ -452,7 +452,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                                       ("noise_mode", engine.noise_mode == noise_mode), ("args", engine.args == args),
                                       ("landmark_fn", engine.landmark_fn is landmark_fn), ("biometric", engine.biometric is biometric),
                                       ("gamma", biometric is None or engine.gamma == float(gamma)), ("mdf", engine.mdf is mdf),
-                                      ("region_weight", (engine.pix_w is not None) == (region_weight is not None))) if not ok]
+                                      ("region_weight", engine.pixel.region_weighted == (region_weight is not None))) if not ok]
         if diff:
             raise ValueError("engine= was built for another objective: " + ", ".join(diff) + " differ(s); build a fresh engine")
         eng = engine.retarget(target, lm_target=lm_target, lm_steps=lm_steps, eps=eps, seed=seed if eps is None else None,

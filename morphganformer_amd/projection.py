@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .pixel_term import MSSSIM_WEIGHTS, PixelTerm, msssim_max_levels, msssim_weights  # noqa: F401  (the MS-SSIM helpers are public here)
 
 
 @dataclass
@@ -89,25 +90,6 @@ class ProjectionArgs:
             raise _lib.MgfError(f"projection: msssim_levels must be an integer in 1..{len(MSSSIM_WEIGHTS)} (got {self.msssim_levels!r})")
 
 
-MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)       # Wang, Simoncelli, Bovik 2003, finest level first
-
-
-def msssim_weights(levels):
-    """The level weights of pixel_term="msssim": the first `levels` of the paper's five, renormalised to sum 1 (one level: plain Gaussian SSIM)."""
-    if not (isinstance(levels, int) and 1 <= levels <= len(MSSSIM_WEIGHTS)):
-        raise _lib.MgfError(f"projection: msssim_levels must be an integer in 1..{len(MSSSIM_WEIGHTS)} (got {levels!r})")
-    w = np.asarray(MSSSIM_WEIGHTS[:levels], dtype=np.float64)
-    return (w / w.sum()).tolist()
-
-
-def msssim_max_levels(h, w):
-    """How many MS-SSIM levels an h x w image allows (every level's sides >= 11; a side s becomes (s + 1) // 2), at most 5."""
-    n = 0
-    while n < len(MSSSIM_WEIGHTS) and min(h, w) >= 11:
-        n, h, w = n + 1, (h + 1) // 2, (w + 1) // 2
-    return n
-
-
 def get_lr(t, initial_lr, rampdown=0.25, rampup=0.05):
     """Learning-rate schedule of the drivers (:63-68).  Inert in literal mode (the optimizer never sees a gradient)."""
     lr_ramp = min(1, (1 - t) / rampdown)
@@ -140,6 +122,18 @@ def _as_latent(latent_mean, shape):
     return t.reshape(*shape).contiguous()
 
 
+def _wing_into(kind, out, table, target, n, ctr):
+    """out[n] (float64) = WingLoss(10, 2) ("wing") or AdaptiveWingLoss(14, 0.5, 1, 2.1) ("awing") of the landmark rows ctr .. ctr + n - 1 of
+    `table` against `target`; rows past the table's end read its last row."""
+    L, st = _lib.lib(), _lib.stream_ptr()
+    if kind == "wing":
+        _lib.check(L.mgf_wing_loss_f64(out.data_ptr(), table.data_ptr(), target.data_ptr(), n, target.numel(), 10.0, 2.0, ctr.data_ptr(),
+                                       table.shape[0] - 1, st), "wing_loss")
+    else:
+        _lib.check(L.mgf_adaptive_wing_loss_f64(out.data_ptr(), table.data_ptr(), target.data_ptr(), n, target.numel(), 14.0, 0.5, 1.0, 2.1,
+                                                ctr.data_ptr(), table.shape[0] - 1, st), "adaptive_wing_loss")
+
+
 def mapping_only(G, z):
     """w [n, k, D] = the mapping network on z [n, k, D] for ANY n, without touching the generator's synthesis workspaces: the kernel
     writes into a buffer of its own (G.mapping / G._mapping_into size the whole synthesis workspace for the batch -- 1.6 GB per sample at
@@ -166,6 +160,7 @@ def latent_stats_w(G, n_mean_latent=10000, device="cuda", generator=None):
 
 class ProjectionEngine:
     """One target image <-> one latent search, replayable as a hipGraph."""
+    _lockstep = False           # several targets per engine: GradientProjectionEngine only
 
     def __init__(self, G, target, latent_mean, latent_std, args: ProjectionArgs = None, percept=None, use_mse=True,
                  lm_target=None, lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, batch=1,
@@ -227,7 +222,8 @@ class ProjectionEngine:
         _lib.require_gpu(target, latent_mean)
         self.steps = a.step
         self.target = target.detach().float().clone(memory_format=torch.contiguous_format)     # the engine's OWN copy: retarget() rewrites it in place
-        assert self.target.shape[0] == 1, "one target per engine (the drivers process images serially)"
+        nt = int(self.target.shape[0])
+        assert nt == 1 or self._lockstep, "one target per engine (the drivers process images serially)"
         self.percept = percept
         self.use_lbp = a.pixel_term == "lbp"
         self.use_mse = use_mse and not self.use_lbp
@@ -240,9 +236,6 @@ class ProjectionEngine:
         # (k, D): the drivers' z latent.  GradientProjectionEngine(latent_space="w+") passes (k, num_ws, D)
         self.latent_shape = ls = tuple(latent_shape) if latent_shape is not None else (k, D)
         self.numel = int(np.prod(ls))
-        self.latent_in = _as_latent(latent_mean, ls).reshape(1, *ls).contiguous().float()
-        sig = noise_schedule(a.step, float(latent_std), a.noise, a.noise_ramp)
-        self.sigma = torch.as_tensor(sig, device=dev)
         self.copies = int(a.latent_copies)
         if not 1 <= self.copies <= 255:
             raise ValueError(f"latent_copies must be 1 .. 255 (got {a.latent_copies})")
@@ -250,13 +243,6 @@ class ProjectionEngine:
             # (torch reduces a width's last numel % 32 columns on another path with another summation order: the bit-exact mean is only
             # claimed for widths it reduces four vector registers at a time -- k D = 17 x 32 = 544 is one)
             raise ValueError(f"latent_copies > 1 needs a latent of a multiple of 32 elements (got {self.numel})")
-        if eps is None:
-            gen = torch.Generator(device=dev)
-            gen.manual_seed(seed)
-            eps = torch.randn(a.step, 1, *(((self.copies,) if self.copies > 1 else ()) + ls), device=dev, generator=gen)
-        self.eps = eps.to(dev).contiguous().float()
-        assert self.eps.shape[0] >= a.step and self.eps[0].numel() == self.numel * self.copies, \
-            f"eps must be [steps, 1{', copies' if self.copies > 1 else ''}, *latent shape] (got {tuple(self.eps.shape)})"
         assert wing_kind in ("wing", "awing")
         self.wing_kind = wing_kind
         self.landmark_fn = landmark_fn
@@ -276,44 +262,16 @@ class ProjectionEngine:
             lm_valid = np.zeros(a.step + spare, np.int32)
             if not self.callback_graphs:
                 use_graph = False
-        if self.use_wing:
-            self.lm_target = torch.as_tensor(lm_target, dtype=torch.float64, device=dev).contiguous()
-            self.lm_steps = torch.as_tensor(lm_steps, dtype=torch.float64, device=dev).contiguous()
-            assert self.lm_steps.shape[0] >= a.step and self.lm_steps.shape[1:] == self.lm_target.shape
-        self.valid = None if lm_valid is None else torch.as_tensor(lm_valid, dtype=torch.int32, device=dev).contiguous()
-        # device-resident loop state
-        self.step_ctr = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.min_loss = torch.full([1], float(a.min_loss_init), dtype=torch.float64, device=dev)
-        self.best_latent = torch.zeros(1, *ls, dtype=torch.float32, device=dev)
-        self.best_step = torch.full([1], -1, dtype=torch.int32, device=dev)
-        self.losses = torch.full([a.step], float("nan"), dtype=torch.float64, device=dev)
-        B = self.batch
-        self.latent_n = torch.empty(B, *ls, dtype=torch.float32, device=dev)
-        self.p_loss = torch.zeros(B, dtype=torch.float32, device=dev)
-        self.mse_loss = torch.zeros(B, dtype=torch.float32, device=dev)
-        self.w_loss = torch.zeros(B, dtype=torch.float64, device=dev)
-        self.scratch = torch.empty(B * int(_lib.lib().mgf_reduce_scratch_floats()), dtype=torch.float32, device=dev)
+        self._init_state(nt, latent_mean, latent_std, eps, seed, lm_target, lm_steps, lm_valid)
+        B = nt * self.batch                         # images per generator call
         self._arange = torch.arange(B, dtype=torch.int64, device=dev)
-        assert a.pixel_term in ("mse", "psnr", "dssim", "lbp", "msssim"), a.pixel_term
-        assert a.psnr_layout in ("script", "aligned"), a.psnr_layout
-        # what the pixel term reads as "the target": the image itself, or -- the PSNR script's element order -- its H-W-C stream under the
-        # candidate's C-H-W indexing (one permuted copy, refreshed by retarget(); the kernel is the same aligned sum)
-        self.pix_target = self._script_order(self.target) if (a.pixel_term == "psnr" and a.psnr_layout == "script") else self.target
-        if self.use_lbp:
-            from . import lbp
-            r = G.cfg.img_resolution
-            self.lbp_ws = lbp.LbpWorkspace(B, r, r, dev)
-            self.lbp_codes = torch.as_tensor(lbp_target, dtype=torch.uint8, device=dev).reshape(-1).contiguous()
-            assert self.lbp_codes.numel() == lbp.SIDE * lbp.SIDE, "lbp_target: the 224 x 224 code map of lbp.target_feature"
         self._init_pool(B)
-        if a.pixel_term == "dssim" and use_mse:
-            c, h, w = self.target.shape[-3:]
-            nbytes = int(_lib.lib().mgf_dssim_scratch_bytes(B, c, h, w))
-            if nbytes <= 0:
-                raise _lib.MgfError(f"projection: pixel_term='dssim' needs images of at least 7x7 pixels, got {h}x{w}")
-            self.dssim_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        self._init_msssim(B)
-        self._init_region(region_weight)
+        self.pixel = PixelTerm(a, self.use_mse, self.target.shape, B, dev, region_weight is not None, G.cfg.img_resolution)
+        self.pixel.refresh_target(self.target, lbp_target)
+        if region_weight is not None:
+            self._set_region(region_weight)
+        elif percept is not None and hasattr(percept, "set_region_weight"):
+            percept.set_region_weight(None)
         if self.percept is not None:
             self.percept.set_target(self.target)
         self.biometric, self.gamma = biometric, float(gamma)
@@ -322,6 +280,10 @@ class ProjectionEngine:
         self.mdf = mdf
         if mdf is not None:
             mdf.set_target(self.target)
+        # the p_loss slot takes LPIPS, the biometric term and MDF in that order: a term accumulates where one in front of it has written
+        self.bio_accumulate = percept is not None
+        self.mdf_accumulate = percept is not None or biometric is not None
+        self.has_p = self.mdf_accumulate or mdf is not None                     # the slot is live
         self.keep_images = int(keep_images)
         if self.keep_images > 0:
             per = G.cfg.img_channels * G.cfg.img_resolution ** 2
@@ -366,58 +328,54 @@ class ProjectionEngine:
             self._primed = False
             self._seq_launched = 0                                                # host count of launch sequences since the last rewind
 
-    def _init_msssim(self, B):
-        """pixel_term="msssim": the level weights as the float64 host array the entry points read at call time, and the scratch (the float64
-        pyramids of both images and of the gradient, the partials, the coefficients) for B images of the size the image-space losses see."""
-        a = self.args
-        self.use_msssim = bool(self.use_mse) and a.pixel_term == "msssim"
-        if not self.use_msssim:
-            return
-        import ctypes
-        c, h, w = self.target.shape[-3:]
-        weights = msssim_weights(a.msssim_levels)
-        if msssim_max_levels(h, w) < a.msssim_levels:
-            raise _lib.MgfError(f"projection: pixel_term='msssim' with msssim_levels={a.msssim_levels} needs every level's sides to be at least 11 "
-                                f"pixels; a {h}x{w} image allows {msssim_max_levels(h, w)} level(s)")
-        self.msssim_w = (ctypes.c_double * len(weights))(*weights)
-        self.msssim_w_ptr = ctypes.addressof(self.msssim_w)
-        nbytes = int(_lib.lib().mgf_msssim_scratch_bytes(B, c, h, w, a.msssim_levels))
-        assert nbytes > 0, (B, c, h, w, a.msssim_levels)
-        self.msssim_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
-
-    def _init_region(self, region_weight):
-        """The region weight of the image-space terms (None: uniform means, today's kernels).  `pix_w` [nw, H W] holds W / (C sum W), what
-        the weighted pixel kernels multiply by; the LPIPS module keeps its per-tap weights itself.  Both are rewritten in place by
-        retarget(region_weight=): captured graphs read them."""
-        a = self.args
-        self.pix_w = None
-        if region_weight is None:
-            if self.percept is not None and hasattr(self.percept, "set_region_weight"):
-                self.percept.set_region_weight(None)
-            return
-        if a.pixel_term != "mse":
-            raise _lib.MgfError(f"projection: pixel_term={a.pixel_term!r} does not take a region_weight: the weighted window forms (DSSIM's 7x7 "
-                                "windows, MS-SSIM's Gaussian windows, the PSNR script's element order, the LBP histogram) are not built; "
-                                "use pixel_term='mse'")
-        if int(a.latent_copies) > 1:
-            raise _lib.MgfError("projection: latent_copies > 1 (the v2 driver's averaged latent) does not take a region_weight")
-        self._set_region(region_weight)
+    def _init_state(self, nt, latent_mean, latent_std, eps, seed, lm_target, lm_steps, lm_valid):
+        """What is shaped by the number of targets: start latent, noise stream and schedule, landmark tables, loop state, the three loss slots.
+        nt = 1 is the drivers' loop, `batch` candidates per call; nt > 1 are GradientProjectionEngine's lockstep projections (batch 1), a row per
+        target of everything: lm_target [nt,68,2], lm_steps [nt,steps,68,2], lm_valid [nt,steps], eps [steps,nt,*latent], losses [nt,steps]."""
+        a, dev, ls = self.args, self.device, self.latent_shape
+        start = latent_mean.detach().float()
+        if nt > 1 and start.numel() == nt * self.numel:                     # one start latent per target
+            self.latent_in = start.reshape(nt, *ls).contiguous().clone()
+        else:
+            self.latent_in = _as_latent(latent_mean, ls).reshape(1, *ls).expand(nt, *ls).contiguous()
+        self.sigma = torch.as_tensor(noise_schedule(a.step, float(latent_std), a.noise, a.noise_ramp), device=dev)
+        copies = (self.copies,) if self.copies > 1 else ()
+        if eps is None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(seed)
+            eps = torch.randn(a.step, nt, *copies, *ls, device=dev, generator=gen)
+        self.eps = eps.to(dev).contiguous().float()
+        assert self.eps.shape[0] >= a.step and (self.eps[0].numel() == self.numel * self.copies if nt == 1
+                                                else tuple(self.eps.shape[1:]) == (nt, *ls)), \
+            f"eps must be [steps, {nt}{', copies' if copies else ''}, *latent shape] (got {tuple(self.eps.shape)})"
+        self.lm_tables = None
+        if self.use_wing:
+            self.lm_target = torch.as_tensor(lm_target, dtype=torch.float64, device=dev).contiguous()
+            self.lm_steps = torch.as_tensor(lm_steps, dtype=torch.float64, device=dev).contiguous()
+            if nt == 1:
+                assert self.lm_steps.shape[0] >= a.step and self.lm_steps.shape[1:] == self.lm_target.shape
+                self.lm_tables = [self.lm_steps]
+            else:
+                assert self.lm_target.shape[0] == nt and self.lm_steps.shape[0] == nt and self.lm_steps.shape[1] >= a.step
+                self.lm_tables = [self.lm_steps[j] for j in range(nt)]
+        self.valid = None if lm_valid is None else torch.as_tensor(lm_valid, dtype=torch.int32, device=dev).contiguous()
+        if nt > 1 and self.valid is not None:
+            self.valid = self.valid.reshape(nt, -1)
+        # device-resident loop state, one row per target (select_best advances a target's own counter)
+        self.step_ctr = torch.zeros(nt, dtype=torch.int32, device=dev)
+        self.min_loss = torch.full([nt], float(a.min_loss_init), dtype=torch.float64, device=dev)
+        self.best_latent = torch.zeros(nt, *ls, dtype=torch.float32, device=dev)
+        self.best_step = torch.full([nt], -1, dtype=torch.int32, device=dev)
+        self.losses = torch.full([a.step] if nt == 1 else [nt, a.step], float("nan"), dtype=torch.float64, device=dev)
+        n = nt * self.batch
+        self.latent_n = torch.empty(n, *ls, dtype=torch.float32, device=dev)
+        self.p_loss = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.mse_loss = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.w_loss = torch.zeros(n, dtype=torch.float64, device=dev)
 
     def _set_region(self, region_weight):
-        from .lpips import check_region_weight
-        w = check_region_weight(region_weight, "region_weight")
-        nt, C, H, W = self.target.shape
-        if tuple(w.shape[1:]) != (H, W):
-            raise ValueError(f"region_weight is {tuple(w.shape[1:])}, the image-space losses see {(H, W)}")
-        if w.shape[0] not in (1, nt):
-            raise ValueError(f"{w.shape[0]} region weights for {nt} target(s): pass one map, or one per target")
-        pix = (w / (C * w.sum(dim=(1, 2), keepdim=True))).to(torch.float32).reshape(w.shape[0], H * W)
-        if self.pix_w is None:
-            self.pix_w = pix.to(self.device).contiguous()
-        elif tuple(self.pix_w.shape) != tuple(pix.shape):
-            raise ValueError(f"retarget: {w.shape[0]} region weight map(s) where the engine was built with {self.pix_w.shape[0]}")
-        else:
-            self.pix_w.copy_(pix)
+        """Write a region weight into the buffers the launch sequence reads (in place: captured graphs reference them)."""
+        w = self.pixel.set_region_weight(region_weight)
         if self.percept is not None:
             self.percept.set_region_weight(w[:, None])
 
@@ -469,43 +427,19 @@ class ProjectionEngine:
             if a.percept_weight != 1.0:
                 self.p_loss.mul_(float(a.percept_weight))
         if self.biometric is not None:      # rides in the p_loss slot: p_loss = LPIPS + gamma * embedding MSE
-            self.biometric.distance_into(self.p_loss, img, scale=self.gamma, accumulate=self.percept is not None)
+            self.biometric.distance_into(self.p_loss, img, scale=self.gamma, accumulate=self.bio_accumulate)
         if self.mdf is not None:            # p_loss (+)= MDF (1024_example_mdfloss.py:165)
-            self.mdf.distance_into(self.p_loss, img, accumulate=self.percept is not None or self.biometric is not None)
-        if self.use_mse and a.pixel_term == "dssim":
-            c, h, w = img.shape[1:]
-            _lib.check(L.mgf_dssim_u8_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, c, h, w, 0, 255.0, 1.0, 0,
-                                          self.dssim_scratch.data_ptr(), st), "dssim")
-        elif self.use_msssim:               # the continuous form (see ProjectionArgs); the B candidates share one target pyramid
-            c, h, w = img.shape[1:]
-            _lib.check(L.mgf_msssim_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, c, h, w, 0, self.msssim_w_ptr,
-                                        a.msssim_levels, 255.0, 1.0, 0, self.msssim_scratch.data_ptr(), st), "msssim")
-        elif self.use_mse and self.pix_w is not None:
-            c, hw = img.shape[1], img.shape[2] * img.shape[3]
-            _lib.check(L.mgf_mse_weighted_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.pix_target.data_ptr(), self.pix_w.data_ptr(), B, c, hw,
-                                              0, 0, 1.0, 0, self.scratch.data_ptr(), st), "mse_weighted")
-        elif self.use_mse:
-            per = img.numel() // B
-            _lib.check(L.mgf_mse_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.pix_target.data_ptr(), B, per, 0, 1.0, 0,
-                                     self.scratch.data_ptr(), st), "mse")
-            if a.pixel_term == "psnr":
-                # 10 * np.log10(peak ** 2 / np.mean(d ** 2)) with peak = 255., in float32 like the script's numpy (1024_example_PSNR.py:113-114)
-                self.mse_loss.reciprocal_().mul_(65025.0).log10_().mul_(10.0)
+            self.mdf.distance_into(self.p_loss, img, accumulate=self.mdf_accumulate)
+        self.pixel.value_into(self.mse_loss, img, self.target, B, 0)           # the B candidates share the one target
         self._landmarks(full_img)
-        if self.use_lbp:        # rides in the float64 slot (the script compares float64 distances, :166-172), coefficient 1
-            self.lbp_ws.distance_into(self.w_loss, full_img, self.lbp_codes)
-        if self.use_wing and self.wing_kind == "wing":
-            _lib.check(L.mgf_wing_loss_f64(self.w_loss.data_ptr(), self.lm_steps.data_ptr(), self.lm_target.data_ptr(), B,
-                                           self.lm_target.numel(), 10.0, 2.0, self.step_ctr.data_ptr(), self.lm_steps.shape[0] - 1, st),
-                       "wing_loss")
-        elif self.use_wing:
-            _lib.check(L.mgf_adaptive_wing_loss_f64(self.w_loss.data_ptr(), self.lm_steps.data_ptr(), self.lm_target.data_ptr(), B,
-                                                    self.lm_target.numel(), 14.0, 0.5, 1.0, 2.1, self.step_ctr.data_ptr(),
-                                                    self.lm_steps.shape[0] - 1, st), "adaptive_wing_loss")
+        if self.use_lbp:        # rides in the float64 slot, coefficient 1
+            self.pixel.lbp_into(self.w_loss, full_img)
+        if self.use_wing:
+            _wing_into(self.wing_kind, self.w_loss, self.lm_steps, self.lm_target, B, self.step_ctr)
         keep = self.keep_images > 0
         _lib.check(L.mgf_select_best(self.min_loss.data_ptr(), self.best_latent.data_ptr(), self.best_step.data_ptr(),
                                      self.losses.data_ptr(), latent_n.data_ptr(), self.numel,
-                                     _lib.ptr(self.p_loss if (self.percept is not None or self.biometric is not None or self.mdf is not None) else None),
+                                     _lib.ptr(self.p_loss if self.has_p else None),
                                      _lib.ptr(self.w_loss if (self.use_wing or self.use_lbp) else None),
                                      _lib.ptr(self.mse_loss if self.use_mse else None), 1.0 if self.use_lbp else float(a.lamda), float(a.beta),
                                      self.step_ctr.data_ptr(), _lib.ptr(self.valid), B, self.steps,
@@ -766,8 +700,8 @@ class ProjectionEngine:
         weakref.finalize(self, G.unpin, G.pin())
 
     def run(self, steps=None):
-        """Advance the loop by `steps` iterations (default: all remaining), `batch` of them per launch sequence."""
-        done = int(self.step_ctr.item()) if steps is None else None
+        """Advance the loop by `steps` iterations (default: all remaining), `batch` of them per launch sequence (lockstep targets advance together)."""
+        done = int(self.step_ctr[0].item()) if steps is None else None
         n = (self.steps - done) if steps is None else steps
         n = (n + self.batch - 1) // self.batch
         if self.pipeline:
@@ -786,11 +720,6 @@ class ProjectionEngine:
                 self._iteration()
         return self
 
-    @staticmethod
-    def _script_order(target):
-        """[1, C, H, W] tensor whose C-H-W stream is the target's H-W-C stream (`tensor2np(imgs).flatten()`, 1024_example_PSNR.py:122,153,158)."""
-        return target.permute(0, 2, 3, 1).contiguous().view(target.shape)
-
     def retarget(self, target, lm_target=None, lm_steps=None, lm_valid=None, eps=None, seed=None, latent_mean=None, latent_std=None,
                  lbp_target=None, region_weight=None):
         """Point this engine at ANOTHER target image and rewind the loop, keeping everything that was expensive to set up: the captured
@@ -807,22 +736,15 @@ class ProjectionEngine:
         assert tuple(target.shape) == tuple(self.target.shape), (tuple(target.shape), tuple(self.target.shape))
         torch.cuda.synchronize(dev)
         if region_weight is not None:
-            if self.pix_w is None:
-                raise _lib.MgfError("retarget: this engine was built without a region_weight (its launch sequence holds the un-weighted kernels); "
-                                    "build a fresh one")
             self._set_region(region_weight)
         self.target.copy_(target)
-        if self.pix_target is not self.target:
-            self.pix_target.copy_(self._script_order(self.target))
+        self.pixel.refresh_target(self.target, lbp_target)
         if self.percept is not None:
             self.percept.set_target(self.target)                  # same shapes: rewrites the cached taps in place
         if self.biometric is not None:
             self.biometric.set_target(self.target)
         if self.mdf is not None:
             self.mdf.set_target(self.target)
-        if self.use_lbp:
-            assert lbp_target is not None, "this engine scores the LBP distance: pass the new target's code map (lbp.target_feature)"
-            self.lbp_codes.copy_(torch.as_tensor(lbp_target, dtype=torch.uint8).reshape(-1))
         if self.use_wing:
             assert lm_target is not None, "this engine has a Wing term: pass the new target's landmarks"
             self.lm_target.copy_(torch.as_tensor(lm_target, dtype=torch.float64).reshape(self.lm_target.shape))
@@ -906,6 +828,7 @@ class GradientProjectionEngine(ProjectionEngine):
         total = percept_weight [(1-a) LPIPS(x,Ta) + a LPIPS(x,Tb)] + beta [(1-a) P(x,Ta) + a P(x,Tb)] + lamda Wing
                 + gamma [(1-a) d_a + a d_b] + id_balance |d_a - d_b|,     d_t = d(embed(x), embed(T_t)), id_metric "mse" or "cosine"
     lm_target_b blends the Wing term's target landmarks the same way; `id_trace` [B,steps,2] holds (d_a, d_b) per step.  See _init_pair."""
+    _lockstep = True
 
     def __init__(self, G, target, latent_mean, latent_std, args: ProjectionArgs = None, percept=None, use_mse=True, lm_target=None,
                  lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, landmark_fn=None, biometric=None,
@@ -957,20 +880,14 @@ class GradientProjectionEngine(ProjectionEngine):
         self.latent_space = latent_space
         ls = (G.cfg.k, G.cfg.num_ws, G.cfg.w_dim) if latent_space == "w+" else (G.cfg.k, G.cfg.z_dim)
         B = int(target.shape[0])
-        if B == 1:
-            super().__init__(G, target, latent_mean, latent_std, args, percept=percept, use_mse=use_mse, lm_target=lm_target,
-                             lm_steps=lm_steps, lm_valid=lm_valid, eps=eps, noise_mode=noise_mode, seed=seed, use_graph=use_graph, batch=1,
-                             landmark_fn=landmark_fn, biometric=biometric, gamma=gamma, wing_kind=wing_kind,
-                             landmark_model=landmark_model, pipeline=False, latent_shape=ls, mdf=mdf, region_weight=region_weight)
-            self.lm_tables = [self.lm_steps] if self.use_wing else None
-        else:
-            self._init_multi(G, target, latent_mean, latent_std, args, percept, use_mse, lm_target, lm_steps, lm_valid, eps, noise_mode,
-                             seed, use_graph, biometric, gamma, wing_kind, ls, region_weight)
-            assert landmark_fn is None and landmark_model is None, "landmark detectors are wired for one target per engine"
+        assert B == 1 or (landmark_fn is None and landmark_model is None), "landmark detectors are wired for one target per engine"
+        # one candidate per target and step, nothing pipelined, no improvement trail; B > 1 targets get a row each of the loop state (_init_state)
+        super().__init__(G, target, latent_mean, latent_std, args, percept=percept, use_mse=use_mse, lm_target=lm_target,
+                         lm_steps=lm_steps, lm_valid=lm_valid, eps=eps, noise_mode=noise_mode, seed=seed, use_graph=use_graph, batch=1,
+                         landmark_fn=landmark_fn, biometric=biometric, gamma=gamma, wing_kind=wing_kind,
+                         landmark_model=landmark_model, pipeline=False, keep_images=0, latent_shape=ls, mdf=mdf, region_weight=region_weight)
         self.targets = B
         a, dev = self.args, self.device
-        self.use_dssim = self.use_mse and a.pixel_term == "dssim"
-        self.win_term = self.use_dssim or self.use_msssim           # a window term: value and gradient from its own kernels, not the MSE ones
         if biometric is not None and hasattr(biometric.embedder, "keep_activations"):
             biometric.embedder.keep_activations = True          # (the FaceNet embedder re-uses its buffers block after block otherwise)
         self.gg = GeneratorGrad(G)
@@ -1040,29 +957,15 @@ class GradientProjectionEngine(ProjectionEngine):
         """Two identities per projection (morph refinement).  Every quadratic term against (Ta weighted 1 - alpha, Tb weighted alpha) equals
         the same term against one blended target plus a constant, so LPIPS, MSE and their backward run once per step on blends -- the cached
         unit taps (PerceptualLoss.set_target_pair) and the pixel blend `self.target` -- and the constants are added on the device; DSSIM and
-        MS-SSIM are evaluated against both targets; the identity term (balance |d_a - d_b|, cosine metric) is mgf_embed_pair_loss_f32."""
+        MS-SSIM are evaluated against both targets (PixelTerm.set_pair); the identity term (balance |d_a - d_b|, cosine metric) is
+        mgf_embed_pair_loss_f32."""
         P, a, dev, B = self.pair, self.args, self.device, self.targets
-        L, st = _lib.lib(), _lib.stream_ptr()
         al = P["alpha"]
         self.pair_alpha = torch.as_tensor(al, dtype=torch.float32, device=dev)
         if self.percept is not None:
             self.percept.set_target_pair(P["ta"], P["tb"], al)
             self.pair_p_off = self.percept.pair_offset * float(a.percept_weight)          # percept_weight * alpha (1 - alpha) LPIPS(Ta, Tb)
-        if self.use_mse and not self.win_term:
-            per = P["ta"].numel() // B
-            self.pair_mse_off = torch.zeros(B, dtype=torch.float32, device=dev)
-            if self.pix_w is not None:
-                c, hw = P["ta"].shape[1], P["ta"].shape[2] * P["ta"].shape[3]
-                _lib.check(L.mgf_mse_weighted_f32(self.pair_mse_off.data_ptr(), P["ta"].data_ptr(), P["tb"].data_ptr(), self.pix_w.data_ptr(), B, c,
-                                                  hw, per, hw if self.pix_w.shape[0] > 1 else 0, 1.0, 0, self.scratch.data_ptr(), st),
-                           "mse_weighted(target pair)")
-            else:
-                _lib.check(L.mgf_mse_f32(self.pair_mse_off.data_ptr(), P["ta"].data_ptr(), P["tb"].data_ptr(), B, per, per, 1.0, 0,
-                                         self.scratch.data_ptr(), st), "mse(target pair)")
-            self.pair_mse_off.mul_(torch.as_tensor(al * (1.0 - al), dtype=torch.float32, device=dev))      # select_best multiplies by beta
-        if self.win_term:
-            self.pair_dssim = torch.zeros(2, B, dtype=torch.float32, device=dev)
-            self.pair_w = torch.as_tensor(np.stack([1.0 - al, al]), dtype=torch.float32, device=dev)
+        self.pixel.set_pair(P["ta"], P["tb"], al)
         if self.biometric is not None:
             self.biometric.set_target_pair(P["ta"], P["tb"], al, id_balance=id_balance, metric=id_metric)
             self.id_trace = torch.full([B, self.steps, 2], float("nan"), dtype=torch.float64, device=dev)
@@ -1071,6 +974,8 @@ class GradientProjectionEngine(ProjectionEngine):
     def retarget(self, *args, **kw):
         if getattr(self, "pair", None) is not None:
             raise _lib.MgfError("GradientProjectionEngine: an engine built on a target pair is not re-targeted; build a fresh one")
+        if self.targets > 1:
+            raise _lib.MgfError("GradientProjectionEngine: an engine of lockstep targets is not re-targeted; build a fresh one")
         return super().retarget(*args, **kw)
 
     def _init_noise(self, noise_init, seed):
@@ -1132,77 +1037,6 @@ class GradientProjectionEngine(ProjectionEngine):
                                                        float(a.noise_regularize), 1, int(has_p or i > 0), self.noise_reg_scratch.data_ptr(), st),
                        "noise_regularize_grad")
 
-    def _init_multi(self, G, target, latent_mean, latent_std, args, percept, use_mse, lm_target, lm_steps, lm_valid, eps, noise_mode,
-                    seed, use_graph, biometric, gamma, wing_kind, ls, region_weight=None):
-        """Loop state of B lockstep projections (the single-target layout of ProjectionEngine with a leading B axis)."""
-        self.G, self.args = G, args or ProjectionArgs()
-        a, dev = self.args, G.device
-        B = int(target.shape[0])
-        self.device, self.batch, self.steps = dev, 1, a.step
-        _lib.require_gpu(target, latent_mean)
-        self.target = target.detach().float().clone(memory_format=torch.contiguous_format)     # the engine's OWN copy: retarget() rewrites it in place
-        self.percept, self.use_mse, self.use_wing, self.noise_mode = percept, use_mse, lm_target is not None, noise_mode
-        self.latent_shape = ls
-        self.numel = int(np.prod(ls))
-        lm0 = latent_mean.detach().float()
-        lm0 = lm0.reshape(B, *ls) if lm0.numel() == B * self.numel else _as_latent(lm0, ls).reshape(1, *ls).expand(B, *ls)
-        self.latent_in = lm0.contiguous().clone()
-        self.sigma = torch.as_tensor(noise_schedule(a.step, float(latent_std), a.noise, a.noise_ramp), device=dev)
-        if eps is None:
-            gen = torch.Generator(device=dev)
-            gen.manual_seed(seed)
-            eps = torch.randn(a.step, B, *ls, device=dev, generator=gen)
-        self.eps = eps.to(dev).contiguous().float()
-        assert tuple(self.eps.shape) == (self.eps.shape[0], B, *ls) and self.eps.shape[0] >= a.step
-        assert wing_kind in ("wing", "awing")
-        self.wing_kind, self.landmark_fn, self.landmark_model = wing_kind, None, None
-        self.landmark_input, self.callback_graphs = "float", False
-        if self.use_wing:
-            self.lm_target = torch.as_tensor(lm_target, dtype=torch.float64, device=dev).contiguous()           # [B,68,2]
-            self.lm_steps = torch.as_tensor(lm_steps, dtype=torch.float64, device=dev).contiguous()             # [B,steps,68,2]
-            assert self.lm_target.shape[0] == B and self.lm_steps.shape[:2] == (B, self.lm_steps.shape[1]) and self.lm_steps.shape[1] >= a.step
-            self.lm_tables = [self.lm_steps[j] for j in range(B)]
-        else:
-            self.lm_tables = None
-        self.valid = None if lm_valid is None else torch.as_tensor(lm_valid, dtype=torch.int32, device=dev).reshape(B, -1).contiguous()
-        self.step_ctr = torch.zeros(B, dtype=torch.int32, device=dev)              # one copy per target (select advances its own)
-        self.min_loss = torch.full([B], float(a.min_loss_init), dtype=torch.float64, device=dev)
-        self.best_latent = torch.zeros(B, *ls, dtype=torch.float32, device=dev)
-        self.best_step = torch.full([B], -1, dtype=torch.int32, device=dev)
-        self.losses = torch.full([B, a.step], float("nan"), dtype=torch.float64, device=dev)
-        self.latent_n = torch.empty(B, *ls, dtype=torch.float32, device=dev)
-        self.p_loss = torch.zeros(B, dtype=torch.float32, device=dev)
-        self.mse_loss = torch.zeros(B, dtype=torch.float32, device=dev)
-        self.w_loss = torch.zeros(B, dtype=torch.float64, device=dev)
-        self.scratch = torch.empty(B * int(_lib.lib().mgf_reduce_scratch_floats()), dtype=torch.float32, device=dev)
-        self._init_region(region_weight)
-        if percept is not None:
-            percept.set_target(self.target)
-        self.biometric, self.gamma = biometric, float(gamma)
-        if biometric is not None:
-            biometric.set_target(self.target)                 # one embedding per target
-        self.use_graph, self.graph, self.pipeline, self.keep_images = use_graph, None, False, 0
-        self.pool_factor = 1
-        self.mdf = None                                       # (refused with B > 1 targets, see __init__)
-        if a.pixel_term == "dssim" and use_mse:
-            c, h, w = self.target.shape[-3:]
-            nbytes = int(_lib.lib().mgf_dssim_scratch_bytes(B, c, h, w))
-            if nbytes <= 0:
-                raise _lib.MgfError(f"projection: pixel_term='dssim' needs images of at least 7x7 pixels, got {h}x{w}")
-            self.dssim_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        self._init_msssim(B)
-
-    def _window_grad(self, dimg, out, img, tgt, n, tstride, scale, accumulate):
-        """dimg (+)= scale * d term / d img and out = the unscaled value, of the window term in use (the continuous DSSIM or MS-SSIM)."""
-        L, st, a = _lib.lib(), _lib.stream_ptr(), self.args
-        c, h, w = img.shape[-3:]
-        if self.use_msssim:
-            _lib.check(L.mgf_msssim_grad_f32(dimg.data_ptr(), out.data_ptr(), img.data_ptr(), tgt.data_ptr(), n, c, h, w, tstride, self.msssim_w_ptr,
-                                             a.msssim_levels, 255.0, scale, accumulate, 0, self.msssim_scratch.data_ptr(), st), "msssim_grad")
-        else:
-            _lib.check(L.mgf_dssim_grad_f32(dimg.data_ptr(), out.data_ptr(), img.data_ptr(), tgt.data_ptr(), n, c, h, w, tstride, 255.0, scale,
-                                            accumulate, 0, self.dssim_scratch.data_ptr(), st), "dssim_grad")
-
     def _state(self):
         st = super()._state() + (self.latent_in, self.exp_avg, self.exp_avg_sq, self.adam_t)
         if getattr(self, "id_trace", None) is not None:
@@ -1225,27 +1059,10 @@ class GradientProjectionEngine(ProjectionEngine):
             img = self.gg.forward(self.latent_n, **nkw)                           # psi lands in `c` in the drivers: no truncation
         if B == 1:
             self._landmarks(img)                                                  # before Adam: a "no face" step must not move the latent
-        per = img.numel() // B
-        tstride = per if B > 1 else 0
+        tstride = img.numel() // B if B > 1 else 0
         pair = self.pair
-        if self.win_term and pair is not None:
-            # DSSIM / MS-SSIM are not quadratic in the image: both targets, sample by sample (the weight is the sample's own), gradients accumulated
-            for t, tgt in enumerate((pair["ta"], pair["tb"])):
-                for j in range(B):
-                    wt = float(pair["alpha"][j]) if t else 1.0 - float(pair["alpha"][j])
-                    self._window_grad(self.dimg[j:], self.pair_dssim[t, j:], img[j:], tgt[j:], 1, 0, float(a.beta) * wt, t)
-            torch.sum(self.pair_dssim * self.pair_w, 0, out=self.mse_loss)
-        elif self.win_term:                  # dimg = beta * d term / d img and the unscaled value, one call (the continuous forms, see ProjectionArgs)
-            self._window_grad(self.dimg, self.mse_loss, img, self.target, B, tstride, float(a.beta), 0)
-        elif self.use_mse and self.pix_w is not None:
-            c, hw = img.shape[1], img.shape[2] * img.shape[3]
-            _lib.check(L.mgf_mse_weighted_grad_f32(self.dimg.data_ptr(), img.data_ptr(), self.target.data_ptr(), self.pix_w.data_ptr(), B, c, hw,
-                                                   tstride, hw if self.pix_w.shape[0] > 1 else 0, float(a.beta), 0, st), "mse_weighted_grad")
-        elif self.use_mse:
-            _lib.check(L.mgf_mse_grad_f32(self.dimg.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, per, tstride, float(a.beta), 0,
-                                          st), "mse_grad")
-        else:
-            self.dimg.zero_()
+        # dimg = beta * d pixel term / d img (zero without one); the window terms write their value with it, the MSE value follows below
+        self.pixel.grad_into(self.dimg, self.mse_loss, img, self.target, B, tstride, float(a.beta), 0)
         if self.percept is not None:
             self.percept.distance_into(self.p_loss, img, keep_taps=True)
             self.percept.grad_into(self.dimg, scale=float(a.percept_weight), accumulate=True)
@@ -1254,30 +1071,18 @@ class GradientProjectionEngine(ProjectionEngine):
             if pair is not None:            # the constant the blended taps leave out: `losses` holds the pair objective, not a shifted one
                 self.p_loss.add_(self.pair_p_off)
         if self.biometric is not None:      # rides in the p_loss slot, like the literal loop (a target pair: one launch of the pair kernel)
-            self.biometric.distance_into(self.p_loss, img, scale=self.gamma, accumulate=self.percept is not None)
+            self.biometric.distance_into(self.p_loss, img, scale=self.gamma, accumulate=self.bio_accumulate)
             self.biometric.grad_into(self.dimg, scale=self.gamma, accumulate=True)
         if self.mdf is not None:            # p_loss (+)= MDF, dimg += d MDF / d img (1024_example_mdfloss.py:165 without the detach)
-            self.mdf.distance_into(self.p_loss, img, accumulate=self.percept is not None or self.biometric is not None, dimg=self.dimg,
-                                   grad_accumulate=True)
-        if self.use_mse and not self.win_term and self.pix_w is not None:
-            c, hw = img.shape[1], img.shape[2] * img.shape[3]
-            _lib.check(L.mgf_mse_weighted_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), self.pix_w.data_ptr(), B, c, hw,
-                                              tstride, hw if self.pix_w.shape[0] > 1 else 0, 1.0, 0, self.scratch.data_ptr(), st), "mse_weighted")
-            if pair is not None:
-                self.mse_loss.add_(self.pair_mse_off)
-        elif self.use_mse and not self.win_term:
-            _lib.check(L.mgf_mse_f32(self.mse_loss.data_ptr(), img.data_ptr(), self.target.data_ptr(), B, per, tstride, 1.0, 0,
-                                     self.scratch.data_ptr(), st), "mse")
-            if pair is not None:
-                self.mse_loss.add_(self.pair_mse_off)
+            self.mdf.distance_into(self.p_loss, img, accumulate=self.mdf_accumulate, dimg=self.dimg, grad_accumulate=True)
+        self.pixel.value_after_grad_into(self.mse_loss, img, self.target, B, tstride)
         if opt_noise:
             dz = self.gg.backward_ws(self.dimg, dnoises=self.dnoises) if self.latent_space == "w+" else self.gg.backward(self.dimg, dnoises=self.dnoises)
         else:
             dz = self.gg.backward_ws(self.dimg) if self.latent_space == "w+" else self.gg.backward(self.dimg)
-        has_p = self.percept is not None or self.biometric is not None or self.mdf is not None
+        has_p = self.has_p or opt_noise
         if opt_noise:
-            self._noise_regularize(has_p)
-            has_p = True
+            self._noise_regularize(self.has_p)
             self.noise_ctr.copy_(self.step_ctr)
         for j in range(B):                   # per-target optimizer step, Wing term and best-of bookkeeping (tiny launches)
             ctr = self.step_ctr[j:]
@@ -1287,13 +1092,7 @@ class GradientProjectionEngine(ProjectionEngine):
                                            _lib.ptr(valid), self.numel, self.steps, float(self.betas[0]), float(self.betas[1]),
                                            self.adam_eps, self.weight_decay, st), "adam_step")
             if self.use_wing:
-                tab, tgt = self.lm_tables[j], (self.lm_target[j] if B > 1 else self.lm_target)
-                if self.wing_kind == "wing":
-                    _lib.check(L.mgf_wing_loss_f64(self.w_loss[j:].data_ptr(), tab.data_ptr(), tgt.data_ptr(), 1, tgt.numel(), 10.0, 2.0,
-                                                   ctr.data_ptr(), tab.shape[0] - 1, st), "wing_loss")
-                else:
-                    _lib.check(L.mgf_adaptive_wing_loss_f64(self.w_loss[j:].data_ptr(), tab.data_ptr(), tgt.data_ptr(), 1, tgt.numel(),
-                                                            14.0, 0.5, 1.0, 2.1, ctr.data_ptr(), tab.shape[0] - 1, st), "adaptive_wing_loss")
+                _wing_into(self.wing_kind, self.w_loss[j:], self.lm_tables[j], self.lm_target[j] if B > 1 else self.lm_target, 1, ctr)
             _lib.check(L.mgf_select_best(self.min_loss[j:].data_ptr(), self.best_latent[j:].data_ptr(), self.best_step[j:].data_ptr(),
                                          self.losses.reshape(B, -1)[j].data_ptr(), self.latent_n[j:].data_ptr(), self.numel,
                                          _lib.ptr(self.p_loss[j:] if has_p else None), _lib.ptr(self.w_loss[j:] if self.use_wing else None),
@@ -1318,18 +1117,6 @@ class GradientProjectionEngine(ProjectionEngine):
             self.noise_trail_count.zero_()
             self.noise_trail_step.fill_(-1)
             self.noise_trail_loss.zero_()
-        return self
-
-    def run(self, steps=None):
-        done = int(self.step_ctr[0].item()) if steps is None else None
-        n = (self.steps - done) if steps is None else steps
-        if self.use_graph and self.graph is None:
-            self._capture()
-        for _ in range(n):
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self._iteration()
         return self
 
     def result(self):

@@ -738,6 +738,23 @@ def test_gradient_projection_lockstep_targets_equal_single_runs(tiny):
     assert np.isnan(losses[1, 2]) and not np.isnan(losses[0, 2])
 
 
+def test_lockstep_engine_refuses_retarget(tiny):
+    """An engine of B = 2 lockstep targets constructs, steps, and states that it is not re-targeted."""
+    from morphganformer_amd._lib import MgfError
+    from morphganformer_amd.projection import GradientProjectionEngine, ProjectionArgs
+    gg, tsd, cfg = tiny
+    G = gg.G
+    torch.manual_seed(23)
+    latent_mean = torch.randn(cfg.k, cfg.z_dim, device="cuda")
+    targets = G(torch.randn(2, cfg.k, cfg.z_dim, device="cuda"), None, noise_mode="const")[0].clamp(-1, 1).clone()
+    eng = GradientProjectionEngine(G, targets, latent_mean, 1.0, ProjectionArgs(step=2), noise_mode="const", use_graph=False)
+    assert eng.targets == 2 and tuple(eng.losses.shape) == (2, 2) and tuple(eng.step_ctr.shape) == (2,)
+    eng.run(1)
+    assert eng.step_ctr.cpu().tolist() == [1, 1] and not np.isnan(eng.losses[:, 0].cpu().numpy()).any()
+    with pytest.raises(MgfError, match="lockstep targets is not re-targeted"):
+        eng.retarget(targets)
+
+
 def test_lockstep_targets_with_the_biometric_term(tiny):
     """B = 2 targets with the full objective (LPIPS + Wing + MSE + embedding MSE, one target embedding each): first-step losses equal
     those of two single-target engines."""
