@@ -172,7 +172,7 @@ def _refine(a, G, alphas):
     if a.biometric != "none":
         if a.biometric_weights is None and not a.biometric_random:
             raise SystemExit(f"morph --refine: --biometric {a.biometric} needs the embedder's weights: --biometric-weights <state dict> (or --biometric-random)")
-        from .iresnet import BiometricLoss
+        from .biometric import BiometricLoss
         state = None
         if a.biometric_weights:
             if a.biometric_weights.endswith(".npz"):
@@ -428,7 +428,7 @@ def main(argv=None):
     if a.biometric != "none":
         if a.biometric_weights is None and not a.biometric_random:
             raise SystemExit(f"{a.cmd}: --biometric {a.biometric} needs the embedder's weights: --biometric-weights <state dict> (or --biometric-random)")
-        from .iresnet import BiometricLoss
+        from .biometric import BiometricLoss
         state = None
         if a.biometric_weights:
             if a.biometric_weights.endswith(".npz"):

@@ -36,9 +36,10 @@ import torch
 
 from . import _lib
 from . import conv as cv
+from .embedder import FaceEmbedder, bn_affine, np64, seeded_bn
 
 BN_EPS = 1e-3
-EMB = 512
+EMB = FaceEmbedder.EMB
 
 # BasicConv2d rows: (cin, cout, (kh, kw), stride, (pad_y, pad_x))
 STEM = [("conv2d_1a", (3, 32, (3, 3), 2, (0, 0))), ("conv2d_2a", (32, 32, (3, 3), 1, (0, 0))), ("conv2d_2b", (32, 64, (3, 3), 1, (1, 1))),
@@ -103,20 +104,14 @@ def random_state(seed=0):
     rng = np.random.Generator(np.random.PCG64(seed))
     sd = {}
 
-    def bn(name, c):
-        sd[name + ".weight"] = rng.uniform(0.5, 1.5, c).astype(np.float32)
-        sd[name + ".bias"] = (rng.standard_normal(c) * 0.1).astype(np.float32)
-        sd[name + ".running_mean"] = (rng.standard_normal(c) * 0.1).astype(np.float32)
-        sd[name + ".running_var"] = rng.uniform(0.5, 1.5, c).astype(np.float32)
-
     for name, cin, cout, (kh, kw) in layer_table():
         sd[name + ".conv.weight"] = (rng.standard_normal((cout, cin, kh, kw)) * math.sqrt(2.0 / (cin * kh * kw))).astype(np.float32)
-        bn(name + ".bn", cout)
+        seeded_bn(rng, sd, name + ".bn", cout)
     for name, ccat, c in residual_table():
         sd[name + ".conv2d.weight"] = (rng.standard_normal((c, ccat, 1, 1)) * math.sqrt(1.0 / ccat)).astype(np.float32)
         sd[name + ".conv2d.bias"] = (rng.standard_normal(c) * 0.05).astype(np.float32)
     sd["last_linear.weight"] = (rng.standard_normal((EMB, 1792)) / math.sqrt(1792)).astype(np.float32)
-    bn("last_bn", EMB)
+    seeded_bn(rng, sd, "last_bn", EMB)
     return sd
 
 
@@ -155,16 +150,21 @@ class _Conv:
     __slots__ = ("pc", "bias", "k", "stride", "pad", "wino", "w_raw", "cin", "cout")
 
 
-class InceptionResnetV1Embedder:
+class InceptionResnetV1Embedder(FaceEmbedder):
     """embed_image(img [n,3,H,W] float32 in the generator's value range) -> [n,512] unit-norm embeddings, like `model(img)` of the driver
     (any H, W >= 75; the driver feeds the un-resized 1024^2 image).  Workspaces are preallocated per (n, H, W): graph-capturable."""
+
+    # a clone starts like a new instance: no size yet (`_alloc(n)` then only sizes `out`), keep_activations off; it shares the gradient taps
+    _MUTABLE = ("bufs", "out", "n", "hw", "_n0", "keep_activations", "_kept", "_x_in")
+    _SHARED = ("_gpacks", "_cslices")
+    n = hw = _kept = None
 
     def __init__(self, state=None, n=1, device="cuda", seed=0):
         _lib.lib()
         self.device = torch.device(device)
         self.random_weights = state is None
         sd = state if state is not None else random_state(seed)
-        g = lambda k: np.asarray(sd[k].detach().cpu() if isinstance(sd[k], torch.Tensor) else sd[k], dtype=np.float64)
+        g = lambda k: np64(sd[k])
         dev = self.device
         t32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=dev)
 
@@ -172,10 +172,10 @@ class InceptionResnetV1Embedder:
             cin, cout, k, stride, pad = spec
             w = g(name + ".conv.weight")
             assert w.shape == (cout, cin, *k), (name, w.shape)
-            s = g(name + ".bn.weight") / np.sqrt(g(name + ".bn.running_var") + BN_EPS)
+            s, t = bn_affine(sd, name + ".bn", BN_EPS)
             L = _Conv()
             wf = t32(w * s[:, None, None, None])
-            L.pc, L.bias = cv.pack_weights(wf), t32(g(name + ".bn.bias") - g(name + ".bn.running_mean") * s)
+            L.pc, L.bias = cv.pack_weights(wf), t32(t)
             L.k, L.stride, L.pad, L.cin, L.cout = k, stride, pad, cin, cout
             L.wino = cv.winograd2_weights(wf) if (k == (3, 3) and stride == 1 and pad == (1, 1) and cin % 4 == 0 and cout % 32 == 0) else None
             L.w_raw = wf if cin <= 4 else None              # the 3-channel stem: the streaming kernel takes the torch layout
@@ -208,23 +208,11 @@ class InceptionResnetV1Embedder:
         self.stages.append(("mixed", 1792, mixed("mixed_7a", MIXED_7A)))
         self.stages.append(("res", 1792, res_blocks("repeat_3", BLOCK8, 5, 0.20) + res_blocks(None, BLOCK8, 1, 1.0, names=["block8"], relu=False)))
         # last_linear (no bias) + last_bn (BatchNorm1d, eval) folded into one affine map
-        sb = g("last_bn.weight") / np.sqrt(g("last_bn.running_var") + BN_EPS)
-        self.fc_w = t32(g("last_linear.weight") * sb[:, None])
-        self.fc_b = t32(g("last_bn.bias") - g("last_bn.running_mean") * sb)
-        self.n, self.hw = None, None
-        self._n0 = n
-        self.keep_activations = False              # gradient mode sets this before the forward pass: backward() reads every layer output
-        self.out = torch.empty(n, EMB, dtype=torch.float32, device=dev)
+        sb, tb = bn_affine(sd, "last_bn", BN_EPS)
+        self.fc_w, self.fc_b = t32(g("last_linear.weight") * sb[:, None]), t32(tb)
+        self._alloc(n)             # (keep_activations: gradient mode sets it before the forward pass, backward() reads every layer output)
 
     # ------------------------------------------------------------------ workspace
-    def clone_for(self, n):
-        """An instance sharing the packed weights but no mutable workspace (BiometricLoss keeps one for the target images)."""
-        other = InceptionResnetV1Embedder.__new__(InceptionResnetV1Embedder)
-        other.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("bufs", "out", "n", "hw", "_g", "_kept", "_x_in")})
-        other.n, other.hw, other._n0, other.keep_activations = None, None, n, False
-        other.out = torch.empty(n, EMB, dtype=torch.float32, device=self.device)
-        return other
-
     def _alloc(self, n, h=None, w=None):
         if h is None:
             if self.hw is None:                              # size not known yet: embed_image allocates on first use
@@ -311,7 +299,7 @@ class InceptionResnetV1Embedder:
         _lib.require_gpu(img, out)
         n, c, h, w = img.shape
         assert c == 3 and img.dtype == torch.float32
-        if (self.n, self.hw, getattr(self, "_kept", None)) != (n, (h, w), self.keep_activations):
+        if (self.n, self.hw, self._kept) != (n, (h, w), self.keep_activations):
             self._alloc(n, h, w)
         B = self.bufs
         x = self._x_in = img.contiguous()
@@ -334,10 +322,7 @@ class InceptionResnetV1Embedder:
                 x = S["cat"]
         L_, st = _lib.lib(), _lib.stream_ptr()
         _lib.check(L_.mgf_spatial_mean_f32(B["mean"].data_ptr(), x.data_ptr(), n * 1792, x.shape[2] * x.shape[3], st), "spatial_mean")
-        for r0 in range(0, n, 16):                                          # the GEMV kernel takes at most 16 rows per launch
-            rows = min(16, n - r0)
-            _lib.check(L_.mgf_linear_f32(B["pre"][r0:].data_ptr(), B["mean"][r0:].data_ptr(), self.fc_w.data_ptr(), self.fc_b.data_ptr(), rows,
-                                         1792, EMB, st), "linear")
+        self.linear(B["pre"], B["mean"], n, 1792)
         out = self.out if out is None else out
         _lib.check(L_.mgf_l2_normalize_f32(out.data_ptr(), B["pre"].data_ptr(), n, EMB, 1e-12, st), "l2_normalize")
         return out
@@ -406,17 +391,14 @@ class InceptionResnetV1Embedder:
         """demb [n, 512] -> the gradient with respect to the image of the latest embed_image() call (keep_activations must have been set
         before that call).  With `dimg` the result is written (added, when `accumulate`) there; otherwise a [n, 3, H, W] tensor is returned."""
         _lib.require_gpu(demb, dimg)
-        if not getattr(self, "_kept", False):
+        if not self._kept:
             raise _lib.MgfError("InceptionResnetV1Embedder.backward: set keep_activations = True before the forward pass (gradient mode)")
         if self._g is None:
             self._g = {}
         L_, st, n, B = _lib.lib(), _lib.stream_ptr(), self.n, self.bufs
         dpre = self._gbuf(("dpre",), (n, EMB))
         _lib.check(L_.mgf_l2_normalize_bwd_f32(dpre.data_ptr(), demb.contiguous().data_ptr(), B["pre"].data_ptr(), n, EMB, 1e-12, st), "l2_normalize_bwd")
-        dmean = self._gbuf(("dmean",), (n, 1792))
-        for r0 in range(0, n, 16):
-            rows = min(16, n - r0)
-            _lib.check(L_.mgf_linear_bwd_f32(dmean[r0:].data_ptr(), dpre[r0:].data_ptr(), self.fc_w.data_ptr(), rows, 1792, EMB, st), "linear_bwd")
+        dmean = self.linear_bwd(self._gbuf(("dmean",), (n, 1792)), dpre, n, 1792)
         last = B["stages"][-1]["blocks"][-1]["x"]
         dx = self._gbuf(("dx", len(self.stages), 0), tuple(last.shape))
         _lib.check(L_.mgf_spatial_mean_bwd_f32(dx.data_ptr(), dmean.data_ptr(), n * 1792, last.shape[2] * last.shape[3], st), "spatial_mean_bwd")
@@ -489,5 +471,3 @@ class InceptionResnetV1Embedder:
             w = close.pc.wp[0, off:off + cb, :close.cout]                     # packed [tap = 1][cin = ccat][cout_pad]: rows = cat channels
             t = cache[key] = cv.pack_weights(w.reshape(cb, close.cout, 1, 1).contiguous())
         return t
-
-    __call__ = embed_image

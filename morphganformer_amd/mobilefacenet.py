@@ -27,9 +27,10 @@ import torch
 
 from . import _lib
 from . import conv as cv
+from .embedder import ArcFaceEmbedder, bn_affine, np64 as _np64, seeded_bn
 
 EPS = 1e-5
-EMB = 512
+EMB = ArcFaceEmbedder.EMB
 # (layers index, in, out, groups, stride, residual blocks) of the trunk behind layers.0 / layers.1 (mobilefacenet.py:92-101)
 TRUNK = [(2, 64, 64, 128, 2, 0), (3, 64, 64, 128, 1, 4), (4, 64, 128, 256, 2, 0), (5, 128, 128, 256, 1, 6), (6, 128, 128, 512, 2, 0),
          (7, 128, 128, 256, 1, 2)]
@@ -55,10 +56,7 @@ def random_state(seed=0):
 
     def conv_bn(name, co, ci_per_group, k, prelu):
         sd[name + ".layers.0.weight"] = (rng.standard_normal((co, ci_per_group, k, k)) * math.sqrt(2.0 / (ci_per_group * k * k))).astype(np.float32)
-        sd[name + ".layers.1.weight"] = rng.uniform(0.5, 1.5, co).astype(np.float32)
-        sd[name + ".layers.1.bias"] = (rng.standard_normal(co) * 0.1).astype(np.float32)
-        sd[name + ".layers.1.running_mean"] = (rng.standard_normal(co) * 0.1).astype(np.float32)
-        sd[name + ".layers.1.running_var"] = rng.uniform(0.5, 1.5, co).astype(np.float32)
+        seeded_bn(rng, sd, name + ".layers.1", co)
         if prelu:
             sd[name + ".layers.2.weight"] = rng.uniform(0.1, 0.4, co).astype(np.float32)
 
@@ -71,26 +69,12 @@ def random_state(seed=0):
     conv_bn("conv_sep", 512, 128, 1, True)
     conv_bn("features.layers.0", 512, 1, 7, False)
     sd["features.layers.2.weight"] = (rng.standard_normal((EMB, 512)) / math.sqrt(512)).astype(np.float32)
-    sd["features.layers.3.weight"] = rng.uniform(0.5, 1.5, EMB).astype(np.float32)
-    sd["features.layers.3.bias"] = (rng.standard_normal(EMB) * 0.1).astype(np.float32)
-    sd["features.layers.3.running_mean"] = (rng.standard_normal(EMB) * 0.1).astype(np.float32)
-    sd["features.layers.3.running_var"] = rng.uniform(0.5, 1.5, EMB).astype(np.float32)
+    seeded_bn(rng, sd, "features.layers.3", EMB)
     return sd
 
 
-def _np64(v):
-    return (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float64)
-
-
-def _bn_affine(sd, name):
-    g = lambda k: _np64(sd[f"{name}.{k}"])
-    s = g("weight") / np.sqrt(g("running_var") + EPS)
-    return s, g("bias") - g("running_mean") * s
-
-
-class MobileFaceNetEmbedder:
-    """embed(x112 [n,3,112,112] in [-1,1]) -> [n,512]; `embed_image` first resizes any [n,3,H,W] image bilinearly to 112x112.
-    The interface of iresnet.IResNetEmbedder (BiometricLoss and both projection engines take either)."""
+class MobileFaceNetEmbedder(ArcFaceEmbedder):
+    """embed(x112 [n,3,112,112] in [-1,1]) -> [n,512]; `embed_image` first resizes any [n,3,H,W] image bilinearly to 112x112."""
 
     _MUTABLE = ("x112", "stem_out", "dw1_out", "bufs", "sep_out", "pool", "out", "stages")
 
@@ -109,12 +93,12 @@ class MobileFaceNetEmbedder:
         t32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=dev)
 
         def folded(name):                # conv -> BN with the scale folded into the weights: (packed taps, shift)
-            s, t = _bn_affine(sd, name + ".layers.1")
+            s, t = bn_affine(sd, name + ".layers.1", EPS)
             w = _np64(sd[name + ".layers.0.weight"]) * s[:, None, None, None]
             return cv.pack_weights(t32(w)), t32(t)
 
         def depthwise(name, prelu):      # (w [c, k*k], scale, shift, slope | None)
-            s, t = _bn_affine(sd, name + ".layers.1")
+            s, t = bn_affine(sd, name + ".layers.1", EPS)
             w = _np64(sd[name + ".layers.0.weight"])
             return t32(w.reshape(w.shape[0], -1)), t32(s), t32(t), t32(_np64(sd[name + ".layers.2.weight"])) if prelu else None
 
@@ -127,16 +111,9 @@ class MobileFaceNetEmbedder:
                                     project=folded(p + ".layers.2"), cin=cin, cout=cout, g=g, stride=stride, residual=res, stage=stage))
         self.sep = (*folded("conv_sep"), slope("conv_sep"))
         self.gdc = depthwise("features.layers.0", False)
-        sf, tf = _bn_affine(sd, "features.layers.3")
+        sf, tf = bn_affine(sd, "features.layers.3", EPS)
         self.fc_w, self.fc_b = t32(_np64(sd["features.layers.2.weight"]) * sf[:, None]), t32(tf)
         self._alloc(n)
-
-    def clone_for(self, n):
-        """An instance sharing the packed weights but no mutable workspace (BiometricLoss keeps one for the target images)."""
-        other = MobileFaceNetEmbedder.__new__(MobileFaceNetEmbedder)
-        other.__dict__.update({k: v for k, v in self.__dict__.items() if k not in self._MUTABLE and not k.startswith("_g")})
-        other._alloc(n)
-        return other
 
     def _alloc(self, n):
         self.n = n
@@ -157,12 +134,6 @@ class MobileFaceNetEmbedder:
         # the outputs of layers.0 .. layers.7 and conv_sep (tests, tools)
         last = {b["stage"]: B["out"] for b, B in zip(self.blocks, self.bufs)}
         self.stages = [self.stem_out, self.dw1_out] + [last[i] for i in range(2, 8)] + [self.sep_out]
-
-    def _prelu(self, x, slope):
-        n, c = x.shape[:2]
-        _lib.check(_lib.lib().mgf_channel_affine_prelu_f32(x.data_ptr(), x.data_ptr(), None, None, slope.data_ptr(), n, c, x.shape[2] * x.shape[3],
-                                                           _lib.stream_ptr()), "channel_affine_prelu")
-        return x
 
     def _dw(self, y, x, p, k, stride, pad):
         w, s, t, slope = p
@@ -189,39 +160,19 @@ class MobileFaceNetEmbedder:
         pc, t, slope = self.sep
         s = self._prelu(cv.conv_forward(x, pc, epilogue=_lib.make_epilogue(bias=t), out=self.sep_out), slope)
         f = self._dw(self.pool, s, self.gdc, 7, 1, 0)
-        out = self.out if out is None else out
-        for r0 in range(0, n, 16):                                   # the GEMV kernel takes at most 16 rows per launch
-            rows = min(16, n - r0)
-            _lib.check(_lib.lib().mgf_linear_f32(out[r0:].data_ptr(), f[r0:].data_ptr(), self.fc_w.data_ptr(), self.fc_b.data_ptr(), rows, 512, EMB,
-                                                 _lib.stream_ptr()), "linear")
-        return out
-
-    def embed_image(self, img, out=None):
-        """img [n,3,H,W] in [-1,1] -> embedding; bilinear resize (align_corners=False) to the 112x112 ArcFace input."""
-        _lib.require_gpu(img)
-        n, c, h, w = img.shape
-        if n != self.n:
-            self._alloc(n)
-        if (h, w) == (112, 112):
-            return self.embed(img.contiguous(), out)
-        _lib.check(_lib.lib().mgf_resize_bilinear_f32(self.x112.data_ptr(), img.contiguous().data_ptr(), n * c, h, w, 112, 112,
-                                                      _lib.stream_ptr()), "resize_bilinear")
-        return self.embed(self.x112, out)
-
-    __call__ = embed_image
+        return self.linear(self.out if out is None else out, f, n, 512)
 
     # ------------------------------------------------------------------ gradient mode
     def _grad_ws(self):
         """Transposed 1x1 taps + workspace of `backward` (built on first use)."""
         n = self.n
-        if getattr(self, "_gp", None) is None:
-            slopes = [self.stem[2], self.dw1[3], self.sep[2]] + [s for b in self.blocks for s in (b["expand"][2], b["dw"][3])]
-            if any(bool((s <= 0).any()) for s in slopes):
-                raise _lib.MgfError("MobileFaceNet backward: PReLU slopes must be positive (the pre-activation sign is read off the output)")
+        if self._gp is None:
+            self._positive_slopes([self.stem[2], self.dw1[3], self.sep[2]] + [s for b in self.blocks for s in (b["expand"][2], b["dw"][3])],
+                                  "MobileFaceNet backward: PReLU slopes must be positive (the pre-activation sign is read off the output)")
             tp = lambda pc: cv.transpose_packed(pc, flip=False)
             self._gp = dict(stem=cv.transpose_packed(self.stem[0], flip=False),     # stride 2: gradient = transposed conv, same taps
                             blocks=[(tp(b["expand"][0]), tp(b["project"][0])) for b in self.blocks], sep=tp(self.sep[0]))
-        if getattr(self, "_gn", None) != n:
+        if self._gn != n:
             self._gn = n
             e = lambda t: torch.empty_like(t)
             self._gb = [dict(d2=e(B["h2"]), d1=e(B["h1"]), dx=torch.empty([n, b["cin"], B["h1"].shape[2], B["h1"].shape[3]], dtype=torch.float32,
@@ -244,10 +195,8 @@ class MobileFaceNetEmbedder:
         scattered through the bilinear resize into it (added when `accumulate`); otherwise the [n,3,112,112] gradient is returned."""
         _lib.require_gpu(demb, dimg)
         self._grad_ws()
-        L, st, n = _lib.lib(), _lib.stream_ptr(), self.n
-        for r0 in range(0, n, 16):
-            rows = min(16, n - r0)
-            _lib.check(L.mgf_linear_bwd_f32(self._gpool[r0:].data_ptr(), demb[r0:].data_ptr(), self.fc_w.data_ptr(), rows, 512, EMB, st), "linear_bwd")
+        n = self.n
+        self.linear_bwd(self._gpool, demb, n, 512)
         # every depthwise adjoint also applies the mask of the PReLU in front of its layer: what comes out is the gradient at the
         # preceding 1x1's (BatchNorm-folded) output, ready for that layer's transposed GEMM
         dsep = self._dw_bwd(self._gsep.view(n, 512, 7, 7), self._gpool.view(n, 512, 1, 1), self.gdc, None, self.sep_out, self.sep[2], 7, 1, 0)
@@ -259,14 +208,4 @@ class MobileFaceNetEmbedder:
         dstem = self._dw_bwd(self._gstem, dx, self.dw1, self.dw1_out, self.stem_out, self.stem[2], 3, 1, 1)
         t = cv.tconv3x3s2_forward(dstem, self._gp["stem"], out=self._gt)                       # T[q + 1] = d x[q]: drop row/column 0
         self._gx112.copy_(t[:, :, 1:, 1:])
-        d112 = self._gx112
-        if dimg is None:
-            return d112
-        if not accumulate:
-            dimg.zero_()
-        h, w = dimg.shape[2:]
-        if (h, w) == (112, 112):
-            dimg += d112
-        else:
-            _lib.check(L.mgf_resize_bilinear_bwd_f32(dimg.data_ptr(), d112.data_ptr(), n * 3, h, w, 112, 112, st), "resize_bilinear_bwd")
-        return dimg
+        return self._image_grad(self._gx112, dimg, accumulate)

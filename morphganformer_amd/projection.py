@@ -888,8 +888,8 @@ class GradientProjectionEngine(ProjectionEngine):
                          landmark_model=landmark_model, pipeline=False, keep_images=0, latent_shape=ls, mdf=mdf, region_weight=region_weight)
         self.targets = B
         a, dev = self.args, self.device
-        if biometric is not None and hasattr(biometric.embedder, "keep_activations"):
-            biometric.embedder.keep_activations = True          # (the FaceNet embedder re-uses its buffers block after block otherwise)
+        if biometric is not None:
+            biometric.embedder.keep_activations = True          # FaceEmbedder's contract (the FaceNet embedder re-uses its buffers block after block otherwise)
         self.gg = GeneratorGrad(G)
         self.betas, self.adam_eps, self.weight_decay = betas, float(adam_eps), float(weight_decay)
         self.lr_table = torch.as_tensor(np.array([get_lr(i / a.step, a.lr, a.lr_rampdown, a.lr_rampup) for i in range(a.step)],

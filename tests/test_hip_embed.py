@@ -241,3 +241,67 @@ def test_gradient_projection_with_the_facenet_term():
     assert np.isfinite(losses).all()
     assert abs(losses[0] - first_literal) < 1e-4 * abs(first_literal)       # step 0: lr = 0, same candidate, same objective
     assert float((eng.latent_in[0] - latent_mean).abs().max()) > 0.01
+
+
+@pytest.mark.parametrize("name,size,grad_size", [("iresnet18", (112, 112), (56, 224)), ("mobilefacenet", (112, 112), (56, 224)),
+                                                 ("facenet", (99, 131), (99, 131))])
+def test_clone_for_shares_the_weights_and_no_workspace(name, size, grad_size):
+    """embedder.FaceEmbedder.clone_for, the same for the three networks: a clone shares `fc_w` (and every packed tap) with its base, owns its
+    `out`, and embeds the same images to the same bits, at 1 row and at 17 (the smallest batch that crosses the 16-row split of the GEMV
+    launches, forward and backward).  Then the shared tail of `backward`: once returned (`dimg=None`), once added (`accumulate=True`) to a
+    known tensor of another size; the second is the first scattered plus that tensor, to the 1e-5 * max|g| of this file's other backward tests.
+    For the two ArcFace networks the scatter is the adjoint of the bilinear resize to 112x112 (float64 autograd through F.interpolate); its
+    size 56x224 has the exact scales 1/2 and 2, so every bilinear weight is exact in float32 and what the gate has to cover is the float32
+    sum of at most 16 products (< 16 * 2^-24); the kernel's weights at ragged sizes have their own per-element gate in
+    test_hip_mobilefacenet.py.  FaceNet scores the un-resized image: its scatter is the identity."""
+    from morphganformer_amd.embedder import ArcFaceEmbedder, FaceEmbedder
+    from morphganformer_amd.iresnet import BiometricLoss
+    gen = torch.Generator().manual_seed(size[0] + size[1])
+    x = (torch.rand(17, 3, *size, generator=gen) * 2 - 1).cuda()
+    base = BiometricLoss(name, n=17, seed=1).embedder
+    assert isinstance(base, FaceEmbedder) and isinstance(base, ArcFaceEmbedder) == (name != "facenet")
+    want17 = base.embed_image(x).clone()
+    want1 = base.embed_image(x[16:]).clone()                                   # (the base re-allocates for one row)
+    c1, c17 = base.clone_for(1), base.clone_for(17)
+    for c in (c1, c17):
+        assert type(c) is type(base) and c.fc_w.data_ptr() == base.fc_w.data_ptr() and c.fc_b.data_ptr() == base.fc_b.data_ptr()
+        assert c.out.data_ptr() != base.out.data_ptr() and c.keep_activations is False
+    assert tuple(c17.out.shape) == (17, 512) and tuple(c1.out.shape) == (1, 512)
+    assert torch.equal(c1.embed_image(x[16:]), want1)
+    assert torch.equal(c17.embed_image(x), want17)
+    assert c17.n == 17 and c1.n == 1 and torch.equal(base.out, want1)          # the clones wrote nothing of the base's
+    # backward, through the contract: keep_activations before the forward pass
+    c17.keep_activations = True
+    assert torch.equal(c17.embed_image(x), want17)
+    v = torch.randn(17, 512, generator=gen).cuda()
+    first = c17.backward(v).clone()
+    known = torch.rand(17, 3, *grad_size, generator=gen).cuda() * float(first.abs().max())      # on the gradient's scale, like the 0.5 above
+    dimg = known.clone()
+    assert c17.backward(v, dimg, accumulate=True) is dimg
+    if name == "facenet":
+        assert tuple(first.shape) == (17, 3, *size)
+        scattered = first.cpu().double()
+    else:
+        assert tuple(first.shape) == (17, 3, 112, 112)
+        z = torch.zeros(17, 3, *grad_size, dtype=torch.float64, requires_grad=True)
+        up = torch.nn.functional.interpolate(z, size=(112, 112), mode="bilinear", align_corners=False)
+        (scattered,) = torch.autograd.grad(up, z, first.cpu().double())
+    err = float((dimg.cpu().double() - (scattered + known.cpu().double())).abs().max())
+    print(name, "accumulated scatter: max |err| / max|g|", err / float(scattered.abs().max()))
+    assert float(scattered.abs().max()) > 0 and err <= 1e-5 * float(scattered.abs().max())
+
+
+def test_iresnet_backward_refuses_non_positive_slopes_every_time():
+    """The PReLU backward reads the sign of its input off its output, so a slope <= 0 is refused; the refusal comes before any of the backward
+    workspace is built, so a second call is refused like the first (it is not run on half a workspace)."""
+    from morphganformer_amd import _lib
+    from morphganformer_amd.iresnet import IResNetEmbedder, random_state
+    sd = random_state(18, 2)
+    sd["layer2.1.prelu.weight"] = sd["layer2.1.prelu.weight"].copy()
+    sd["layer2.1.prelu.weight"][7] = 0.0
+    e = IResNetEmbedder(sd, depth=18, n=1)
+    assert bool(torch.isfinite(e.embed(torch.zeros(1, 3, 112, 112, device="cuda"))).all())          # the forward pass takes any slope
+    for _ in range(2):
+        with pytest.raises(_lib.MgfError, match="PReLU slopes must be positive"):
+            e.backward(torch.ones(1, 512, device="cuda"))
+    assert e._gp is None
