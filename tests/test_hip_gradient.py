@@ -477,6 +477,59 @@ def test_lpips_tap_gradient_fused_with_relu_bwd_is_the_two_kernels_in_sequence(c
         assert torch.equal(dy, a0) or not behind
 
 
+def _bulk(a, b):
+    """(median, rms, max) of |a - b| / max|b|: the shape of the gate of test_lpips_merged_fire_launches_equal_the_separate_ones."""
+    err = (a.double() - b.double()).abs() / b.double().abs().max()
+    return float(err.median()), float(err.square().mean().sqrt()), float(err.max())
+
+
+@pytest.mark.parametrize("nw", [None, 1, 2])
+@pytest.mark.parametrize("net,size", [("squeeze", 65), ("squeeze", 128), ("vgg", 48), ("alex", 96)])
+def test_lpips_switches_equal_the_default_dispatch(net, size, nw, monkeypatch):
+    """The branches behind the LPIPS switches against the default dispatch, at module level (set_target, distance_into(keep_taps=True),
+    grad_into; n = 2; no region weight, one map, n maps): the un-fused tap gradient (FUSE_TAP_RELU), the recomputed tap sums (TAP_STATS) and
+    SqueezeNet's recomputed pool argmax (POOL_ARGMAX), each switched off alone, and the first two together against TAP_STATS alone.
+    Measured on the commit before the backbones moved to a module of their own (the switches then lived in lpips.py), on one MI355X:
+    distance and gradient bit-identical in all 12 cases for every switch, region-weighted cases included (maximum relative error 0
+    throughout), so every comparison is torch.equal; the figures are printed in front of the assertion."""
+    from morphganformer_amd import lpips, lpips_backbones as flags          # (the module that holds the switches)
+    n = 2
+    torch.manual_seed(size + (nw or 0))
+    x0 = (torch.rand(n, 3, size, size) * 2 - 1).cuda()
+    x1 = (x0[:1] + 0.3 * torch.randn(1, 3, size, size).cuda()).clamp(-1, 1)
+    P = lpips.PerceptualLoss(net=net, allow_random_backbone=True)
+    if nw is not None:
+        P.set_region_weight(torch.rand(nw, 1, size, size) + 0.05)
+
+    def run(*off):
+        with monkeypatch.context() as m:
+            for name in off:
+                m.setattr(flags, name, False)
+            P.set_target(x1)
+            out, d = torch.zeros(n, device="cuda"), torch.zeros_like(x0)
+            P.distance_into(out, x0, keep_taps=True)
+            P.grad_into(d, scale=1.0)
+        f = P._last                                                # the switch took hold: what the forward left for the backward
+        assert bool(f.tap_stats) == ("TAP_STATS" not in off)
+        assert net != "squeeze" or f.have_argmax == ("POOL_ARGMAX" not in off)
+        return out, d
+
+    base = run()
+    assert float(base[1].abs().max()) > 0
+    unstat = run("TAP_STATS")
+    pairs = [("FUSE_TAP_RELU+TAP_STATS | TAP_STATS", run("FUSE_TAP_RELU", "TAP_STATS"), unstat), ("TAP_STATS", unstat, base),
+             ("FUSE_TAP_RELU", run("FUSE_TAP_RELU"), base)]
+    if net == "squeeze":
+        pairs.append(("POOL_ARGMAX", run("POOL_ARGMAX"), base))
+    differ = []
+    for what, (va, ga), (vb, gb) in pairs:
+        print(f"SWITCH {net} {size} nw={nw} {what}: distance med/rms/max %.3e %.3e %.3e  gradient med/rms/max %.3e %.3e %.3e"
+              % (*_bulk(va, vb), *_bulk(ga, gb)))
+        if not (torch.equal(va, vb) and torch.equal(ga, gb)):
+            differ.append(what)
+    assert not differ, differ
+
+
 def test_mse_grad_and_pool_bwd():
     from morphganformer_amd import _lib
     L = _lib.lib()

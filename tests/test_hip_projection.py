@@ -396,15 +396,15 @@ def test_lpips_merged_fire_launches_equal_the_separate_ones(size):
     """One image per forward: a Fire's expand1x1 + expand3x3 run as ONE 3x3 launch (expand1x1 in the centre tap) and their data gradients as
     one launch over the concatenated gradient (lpips.MERGE_FIRE) -- distance, per-tap contributions and the image gradient against the
     separate launches (squeezenet Fire: lpips/pretrained_networks.py:7-44)."""
-    from morphganformer_amd import lpips
+    from morphganformer_amd import lpips, lpips_backbones
     torch.manual_seed(size[0])
     x0 = (torch.rand(1, 3, *size) * 2 - 1).cuda()
     x1 = (x0 + 0.3 * torch.randn(1, 3, *size).cuda()).clamp(-1, 1)
     got = {}
-    keep = lpips.MERGE_FIRE
+    keep = lpips_backbones.MERGE_FIRE
     try:
         for merge in (True, False):
-            lpips.MERGE_FIRE = merge
+            lpips_backbones.MERGE_FIRE = merge
             P = lpips.PerceptualLoss(net="squeeze", backbone_state=lpips.random_squeeze_backbone(0))
             P.set_target(x1)
             assert bool(next(iter(P._feats.values())).merge) == merge
@@ -413,7 +413,7 @@ def test_lpips_merged_fire_launches_equal_the_separate_ones(size):
             P.grad_into(d, scale=1.0)
             got[merge] = (float(out), P.distance_per_tap(x0)[:, 0].cpu().numpy(), d.cpu())
     finally:
-        lpips.MERGE_FIRE = keep
+        lpips_backbones.MERGE_FIRE = keep
     (va, ta, ga), (vb, tb, gb) = got[True], got[False]
     assert abs(va - vb) <= 1e-5 * abs(vb) and np.abs(ta - tb).max() <= 1e-5 * np.abs(tb).max()
     # (a ReLU input within float32 rounding of zero may take the other branch in the other arithmetic -- expand1x1 through the Winograd
