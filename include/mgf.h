@@ -795,6 +795,31 @@ int mgf_resize_bilinear_bwd_f32(float* dx, const float* dy, int32_t nc, int32_t 
                                 mgf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * face_crop: the aligned, antialiased crop in front of the ArcFace embedders, and its adjoint (csrc/face_crop.hip).  The reference tree resizes
+ * the whole frame (F.interpolate in front of backbones/iresnet.py); this comment is the operator's definition.
+ *   x [n,3,h,w] float32 -> y [n,3,size,size] under `matrices`: float64 [m_count,2,3] ON THE DEVICE, m_count = n (one per image) or 1 (shared).
+ *   M maps a crop pixel index (u, v) to a source pixel index, (x, y) = M (u, v, 1): cv2.warpAffine(..., WARP_INVERSE_MAP) with a zero border --
+ *   an index is a coordinate, a bilinear tap outside the source reads 0.
+ *   filter MGF_CROP_BILINEAR: one bilinear sample per crop pixel.  MGF_CROP_AREA: the mean of S x S bilinear samples at the crop coordinates
+ *   (u + (i + 0.5)/S - 0.5, v + (j + 0.5)/S - 0.5), i, j < S, with S = clamp(ceil(sqrt(|det M[:, :2]|)), 1, 16) computed BY THE KERNEL from the
+ *   matrix (S = 1 is the bilinear filter; M = [[k,0,k/2-1/2],[0,k,k/2-1/2]] gives exactly the k x k block mean).
+ *   No launch parameter depends on the VALUES of the matrices: a captured launch stays valid when they are rewritten in place.  float32 loads,
+ *   float64 coordinates, weights and sums in a fixed order, one rounding at the store; no atomics (bit-reproducible), no scratch memory.
+ *   mgf_face_crop_check:    matrices [count,2,3] ON THE HOST: MGF_EINVAL (the message names the matrix) for a non-finite entry, |det| < 1e-12,
+ *                           or, with MGF_CROP_AREA, ceil(sqrt(|det|)) > 16.  The kernels cannot return an error: call this once where the matrices
+ *                           are set.  A matrix that was not checked is still safe to run: S is clamped, a singular matrix has a zero adjoint.
+ *   mgf_face_crop_f32:      y = A x
+ *   mgf_face_crop_bwd_f32:  dx (+)= A^T dy, dx [n,3,h,w] written whole (accumulate = 0) or added to; a gather -- a source pixel sums, rows then
+ *                           columns of the sub-sample grid ascending, the sub-samples whose 2 x 2 bilinear footprint contains it, their index
+ *                           range taken from M^-1 of the pixel's 2 x 2 neighbourhood. */
+enum { MGF_CROP_AREA = 0, MGF_CROP_BILINEAR = 1 };
+int mgf_face_crop_check(const double* matrices, int32_t count, int32_t filter);
+int mgf_face_crop_f32(float* y, const float* x, const double* matrices, int32_t n, int32_t h, int32_t w, int32_t size, int32_t m_count,
+                      int32_t filter, mgf_stream_t stream);
+int mgf_face_crop_bwd_f32(float* dx, const float* dy, const double* matrices, int32_t n, int32_t h, int32_t w, int32_t size, int32_t m_count,
+                          int32_t filter, int32_t accumulate, mgf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Depthwise convolutions of the MobileFaceNet embedder (backbones/mobilefacenet.py; csrc/depthwise.hip): what
  * `Conv2d(c, c, k, groups=c, stride, padding, bias=False)` -> BatchNorm2d -> [PReLU(c)] computes in eval mode (ConvBlock :16-26 and
  * LinearBlock :29-38 with groups == channels: the middle step of DepthWise :41-60, layers[1] :94, the 7x7 of GDC :75-85).

@@ -185,6 +185,9 @@ _SIGS = {
     "mgf_prelu_bwd_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, vp]),
     "mgf_linear_bwd_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
     "mgf_resize_bilinear_bwd_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "mgf_face_crop_check": (C.c_int, [vp, i32, i32]),
+    "mgf_face_crop_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "mgf_face_crop_bwd_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "mgf_dwconv_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "mgf_dwconv_bwd_data_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "mgf_cv_warp_triangle_bytes": (i64, []),

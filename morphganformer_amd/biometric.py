@@ -39,6 +39,54 @@ class BiometricLoss:
         self._pair, self._pair_bufs, self._pair_scale, self._pair_dummy = None, None, None, None
         self._demb = None                         # [n, EMB]: the embedding gradient handed to the embedder's backward
         self.pair_trace = None
+        self._crop = None                         # set_crop's dict(target=, target_b=, filter=); the candidates' matrices live in the embedder
+        self._target_src = None                   # the arguments of the latest set_target / set_target_pair: set_crop re-embeds from them
+
+    def set_crop(self, pred, target=None, target_b=None, filter="area"):
+        """Embed through the aligned face crop of `ArcFaceEmbedder.set_crop` instead of the plain resize.  pred: the matrix [2,3] (or B matrices
+        [B,2,3], lockstep) of the candidates; target / target_b: the matrices under which set_target / set_target_pair embed the target
+        image(s), each pred by default.  None for pred restores the resize everywhere.  Call it before set_target*.  The FaceNet embedder scores
+        the un-cropped frame by the reference's definition: MgfError.
+
+        Stored target embeddings never belong to another crop than the one in force.  When a target is already set, it is embedded again here
+        FROM THE TENSORS set_target* WAS HANDED -- this object keeps references to them, not copies, and reads what they hold now -- provided
+        the new target matrices can apply to it (one matrix, or as many as it has images); a remembered target they cannot apply to (another
+        batch size: a BiometricLoss handed from one engine to the next) is dropped with its embeddings, and set_target* must be called again.
+        A caller that is about to call set_target* anyway says so with forget_target() first and saves the embedder pass.  Every matrix is
+        checked before anything is changed: a refused matrix leaves the crop, the embedder and the stored embeddings as they were."""
+        from .embedder import ArcFaceEmbedder
+        if not isinstance(self.embedder, ArcFaceEmbedder):
+            raise _lib.MgfError(f"set_crop: {type(self.embedder).__name__} takes no face crop (the ArcFace embedders iresnet*/mobilefacenet do)")
+        crop, counts = None, ()
+        if pred is not None:
+            crop = dict(target=pred if target is None else target, target_b=pred if target_b is None else target_b, filter=filter)
+            ArcFaceEmbedder.check_crop(pred, filter)
+            counts = [ArcFaceEmbedder.check_crop(crop[k], filter)[0].shape[0] for k in ("target", "target_b")]
+        self.embedder.set_crop(pred, filter)
+        self._crop = crop
+        if self._target_src is None:
+            return
+        setter, args = self._target_src
+        nt = int(args[0].shape[0])
+        if any(c not in (1, nt) for c in (counts if self._pair is not None else counts[:1])):
+            self.forget_target()
+            self._target, self._pair, self.pair_trace = None, None, None
+            return
+        trace = self.pair_trace
+        setter(*args)
+        self.pair_trace = trace
+
+    def forget_target(self):
+        """Drop the references to the target tensors of the latest set_target* call (set_crop re-embeds from them).  The stored embeddings stay:
+        for a caller that calls set_target* next, such as an engine that was just handed this object or is being re-targeted."""
+        self._target_src = None
+
+    def _embed_target(self, net, image, which):
+        if self._crop is not None:               # the target net is a clone: it starts without a crop and is only ever given one here
+            net.set_crop(self._crop[which], self._crop["filter"])
+        elif getattr(net, "_crop", None) is not None:
+            net.set_crop(None)
+        return net.embed_image(image.float())
 
     def _target_net(self, nt):
         """The embedder of the target images: an instance sharing nothing mutable with the candidates' workspace."""
@@ -54,7 +102,8 @@ class BiometricLoss:
     def set_target(self, target):
         """One target [1,3,H,W] shared by every candidate, or B targets that pair up with B candidates (lockstep projections)."""
         nt = int(target.shape[0])
-        emb = self._target_net(nt).embed_image(target.float())
+        emb = self._embed_target(self._target_net(nt), target, "target")
+        self._target_src = (self.set_target, (target,))
         if self._target is not None and self._target.shape == emb.shape:
             self._target.copy_(emb)   # in place: a captured hipGraph of the projection engine keeps reading this buffer (ProjectionEngine.retarget)
         else:
@@ -80,8 +129,9 @@ class BiometricLoss:
             raise ValueError(f"set_target_pair: alpha must be one value or {nt} values in [0, 1] (got {alpha!r})")
         al = np.array(np.broadcast_to(al, (nt,)))
         net = self._target_net(nt)
-        ea = net.embed_image(target_a.float()).clone()
-        eb = net.embed_image(target_b.float())
+        ea = self._embed_target(net, target_a, "target").clone()
+        eb = self._embed_target(net, target_b, "target_b")
+        self._target_src = (self.set_target_pair, (target_a, target_b, alpha, id_balance, metric))
         old = self._pair_bufs
         if old is None or old[0].shape != ea.shape:
             old = self._pair_bufs = (torch.empty_like(ea), torch.empty_like(ea), torch.empty(nt, dtype=torch.float32, device=ea.device))
@@ -120,7 +170,7 @@ class BiometricLoss:
             assert self._target_stride == 0 or self._pair["ta"].shape[0] == n, "B target pairs pair up with B candidates"
             self._pair_launch(out, self.embedder.embed_image(pred), n, scale, accumulate, True)
             return out
-        assert self._target is not None, "call set_target first"
+        assert self._target is not None, "call set_target first (set_crop drops a target its matrices cannot apply to)"
         assert self._target_stride == 0 or self._target.shape[0] == n, "B targets pair up with B candidates"
         emb = self.embedder.embed_image(pred)
         need = n * int(_lib.lib().mgf_reduce_scratch_floats())

@@ -142,6 +142,12 @@ def _refine_arguments(m):
     m.add_argument("--biometric-weights", type=str, default=None, metavar="STATE_DICT")
     m.add_argument("--biometric-random", action="store_true")
     m.add_argument("--seed", type=int, default=None)
+    m.add_argument("--landmarks", type=str, default=None,
+                   help="--refine --biometric-align: an .npz with `target` [68,2], the landmarks of --image-a, and `target_b`, those of --image-b")
+    m.add_argument("--biometric-align", action="store_true",
+                   help="--refine: embed both images and every candidate through the aligned face crop (drivers.arcface_crop of the --landmarks "
+                        "rows; a candidate's crop follows the blended landmarks); iresnetNN / mobilefacenet")
+    m.add_argument("--biometric-crop-filter", choices=["area", "bilinear"], default="area")
     m.add_argument("--region-weight", type=str, default=None, metavar="FILE",
                    help="--refine: weight the LPIPS and pixel terms by region (a .npy float [S,S] map >= 0, or a gray image scaled to [0,1])")
 
@@ -187,11 +193,18 @@ def _refine(a, G, alphas):
         raise SystemExit("morph --refine: --id-balance weighs the two identity distances: it needs --biometric")
     if percept is None and a.no_mse and biometric is None:
         raise SystemExit("morph --refine: every term of the objective is switched off")
+    crop_kw = {}
+    if a.biometric_align:                # (checked by align_arguments before anything was loaded)
+        lm = np.load(a.landmarks)
+        if "target" not in lm or "target_b" not in lm:
+            raise SystemExit(f"morph --refine: --biometric-align needs the rows `target` and `target_b` in {a.landmarks} (found {sorted(lm.keys())})")
+        crop_kw = dict(face_crop=drivers.arcface_crop(lm["target"]), face_crop_b=drivers.arcface_crop(lm["target_b"]),
+                       face_crop_filter=a.biometric_crop_filter)
     ta = drivers.image_transform(a.image_a, size=a.size, device=G.device)
     tb = drivers.image_transform(a.image_b, size=a.size, device=G.device)
     res = drivers.refine_morph(G, w1, w2, ta, tb, alphas, lockstep=not a.no_lockstep, args=args, percept=percept, biometric=biometric,
                                gamma=a.gamma, id_balance=a.id_balance, id_metric=a.id_metric, seed=a.seed, use_mse=not a.no_mse,
-                               out_prefix=a.out, ratio=a.ratio,
+                               out_prefix=a.out, ratio=a.ratio, **crop_kw,
                                region_weight=None if a.region_weight is None else drivers.load_region_weight(a.region_weight))
     for r in res:
         ids = "" if r["id_distances"] is None else "  d_a {:.6f}  d_b {:.6f}".format(*r["id_distances"])
@@ -224,6 +237,11 @@ def build_parser():
     p.add_argument("--region-from-landmarks", type=str, default=None, metavar="INSIDE,OUTSIDE[,FEATHER]",
                    help="the region weight from the target row of --landmarks: INSIDE on the landmarks' convex hull, OUTSIDE elsewhere, the edge "
                         "blurred with a Gaussian of FEATHER pixels (drivers.face_region_weight)")
+    p.add_argument("--biometric-align", action="store_true",
+                   help="embed candidates and target through the aligned, antialiased 112x112 face crop ArcFace networks are trained on "
+                        "(drivers.arcface_crop of the target row of --landmarks) instead of a resize of the whole frame; iresnetNN / mobilefacenet")
+    p.add_argument("--biometric-crop-filter", choices=["area", "bilinear"], default="area",
+                   help="--biometric-align: area = the mean over each crop pixel's footprint (default), bilinear = one sample per crop pixel")
     _loop_arguments(p)
 
     q = sub.add_parser("morph-pairs", help="Project both images of every CSV pair and render their latent morph "
@@ -357,9 +375,29 @@ def region_arguments(a):
     return ("landmarks", vals[0], vals[1], vals[2] if len(vals) == 3 else 0.0)
 
 
+def align_arguments(a):
+    """Checks of --biometric-align (before anything is loaded) -> True when the biometric term embeds through the aligned face crop."""
+    if not getattr(a, "biometric_align", False):
+        return False
+    what = "morph --refine" if a.cmd == "morph" else a.cmd
+    if a.cmd == "morph" and not a.refine:
+        raise SystemExit("morph: --biometric-align belongs to --refine")
+    if a.biometric == "none":
+        raise SystemExit(f"{what}: --biometric-align aligns the input of the biometric term: it needs --biometric iresnetNN or mobilefacenet")
+    if a.biometric == "facenet":
+        raise SystemExit(f"{what}: --biometric-align is the crop of the ArcFace embedders (iresnetNN, mobilefacenet); facenet scores the "
+                         "un-cropped frame by the reference's definition")
+    if not a.landmarks:
+        raise SystemExit(f"{what}: --biometric-align takes the crop from the target's landmarks: it needs --landmarks")
+    if not os.path.isfile(a.landmarks):
+        raise SystemExit(f"{what}: --biometric-align: the landmark file {a.landmarks} does not exist")
+    return True
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
     region = region_arguments(a)
+    align = align_arguments(a)
     if a.cmd == "merge-files":                              # file bookkeeping only (1024_merge_files.py): no generator, no GPU
         from . import drivers
         files = drivers.merge_files(a.src, a.dst)
@@ -497,7 +535,7 @@ def main(argv=None):
                                 out_prefix=os.path.join(a.path_to_gen, stem), mode=a.mode, path_to_gen=a.path_to_gen,
                                 keep_images=a.keep_images, latent_space=space, biometric=biometric, gamma=a.gamma, use_mse=not a.no_mse, pipeline=None if a.pipeline < 0 else (bool(a.pipeline) and a.mode == "literal"),
                                 lbp_target=lbp_target, mdf=mdf, optimize_noise=a.optimize_noise, noise_init=a.noise_init, lpips_map=a.lpips_map,
-                                region_weight=region_weight)
+                                region_weight=region_weight, **(dict(face_crop="landmarks", face_crop_filter=a.biometric_crop_filter) if align else {}))
     print(f"best step {res['step']}  loss {res['loss']:.6f}")
     return 0
 

@@ -168,7 +168,7 @@ def _blend_latents(a1, a2, a):
 def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, args: ProjectionArgs = None, percept=None, biometric=None,
                  gamma=1.0, id_balance=0.0, id_metric="mse", latent_std=None, eps=None, seed=None, use_graph=True, noise_mode="random",
                  use_mse=True, lm_target=None, lm_target_b=None, lm_steps=None, weight_decay=0.0, mode="gradient", out_prefix=None, ratio=None,
-                 region_weight=None):
+                 region_weight=None, face_crop=None, face_crop_b=None, face_crop_filter="area"):
     """Morph refinement: for every alpha start at merge_morph's blend (1 - a) w1 + a w2 (the same float32 arithmetic) and descend it so that
     the image matches BOTH contributing subjects -- target_a weighted 1 - a, target_b weighted a: perceptually, in pixels and in identity
     space, the two identity distances kept in balance by id_balance |d_a - d_b| (GradientProjectionEngine(target_b=...) has the objective).
@@ -179,7 +179,11 @@ def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, ar
     blended landmarks.  Returns one dict per alpha: alpha, w_start (numpy), w (best latent, [1,k,D] or W+), losses, best_step, best_loss,
     id_distances ((d_a, d_b) at the best step; None without a biometric term).  out_prefix: `<prefix>_a{alpha:.2f}_refined.mat / .png`, the
     image rendered like a projection result (no truncation).  region_weight: one map [S,S] >= 0 that weights the LPIPS and pixel terms of
-    every alpha (GradientProjectionEngine(region_weight=...); `face_region_weight` builds one from landmarks)."""
+    every alpha (GradientProjectionEngine(region_weight=...); `face_region_weight` builds one from landmarks).  face_crop / face_crop_b: the
+    identity term embeds through the aligned face crop (BiometricLoss.set_crop) -- the [2,3] matrices under which target_a / target_b are
+    embedded (face_crop_b: face_crop by default), or "landmarks": arcface_crop of lm_target / lm_target_b.  The candidate of alpha is cropped by
+    arcface_crop of the blended landmarks (1 - a) lm_target + a lm_target_b, or, with matrices given, by their blend (a blend of
+    similarities is one).  face_crop_filter: "area" or "bilinear"."""
     if mode != "gradient":
         raise ValueError(f"refine_morph descends the objective: mode must be 'gradient' (got {mode!r}; the literal loop never moves the latent)")
     a1 = np.asarray(w1.detach().cpu() if isinstance(w1, torch.Tensor) else w1, dtype=np.float32)
@@ -211,6 +215,21 @@ def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, ar
         gen.manual_seed(0 if seed is None else seed)
         eps = torch.randn(args.step, B, *ls, device=dev, generator=gen)
     eps = eps.to(dev).float().reshape(-1, B, *ls)
+    crop_kw = lambda js: {}
+    if face_crop is not None or face_crop_b is not None:
+        if face_crop is None or biometric is None:
+            raise ValueError("refine_morph: face_crop_b needs face_crop, and both need a biometric term")
+        ma = _resolve_crop(face_crop, lm_target, "face_crop")
+        mb = ma if face_crop_b is None else _resolve_crop(face_crop_b, lm_target_b, "face_crop_b")
+        if ma.shape != (2, 3) or mb.shape != (2, 3):
+            raise ValueError(f"refine_morph: face_crop / face_crop_b are one [2,3] matrix each (got {ma.shape}, {mb.shape})")
+        if isinstance(face_crop, str) and isinstance(face_crop_b, str):      # the landmarks the engine blends for the Wing term
+            la, lb = np.asarray(lm_target, dtype=np.float64), np.asarray(lm_target_b, dtype=np.float64)
+            pred = lambda a: arcface_crop((1.0 - a) * la + a * lb)
+        else:
+            pred = lambda a: (1.0 - a) * ma + a * mb
+        crop_kw = lambda js: dict(face_crop=np.stack([pred(alphas[j]) for j in js]), face_crop_target=ma, face_crop_target_b=mb,
+                                  face_crop_filter=face_crop_filter)
 
     def run(js):
         n = len(js)
@@ -223,7 +242,7 @@ def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, ar
                                        weight_decay=weight_decay, percept=percept, eps=eps[:, js].contiguous(), noise_mode=noise_mode,
                                        use_graph=use_graph, use_mse=use_mse, latent_space=space, biometric=biometric, gamma=gamma,
                                        target_b=rep(target_b), morph_alpha=[alphas[j] for j in js], id_balance=id_balance, id_metric=id_metric,
-                                       region_weight=region_weight, **lm_kw)
+                                       region_weight=region_weight, **lm_kw, **crop_kw(js))
         w, step, loss, losses = eng.run().result()
         trace = None if eng.id_trace is None else eng.id_trace.cpu().numpy()
         if n == 1:
@@ -296,6 +315,52 @@ def merge_files(src_path, dst_path):
                     for img in sorted(os.listdir(os.path.join(id_dir, name))):
                         out.append(shutil.copy(os.path.join(id_dir, name, img), os.path.join(dst_fold, img)))
     return out
+
+
+# the five points ArcFace networks are trained on, in a 112 x 112 crop (insightface's arcface_dst): eye centres, nose tip, mouth corners
+ARCFACE_TEMPLATE = np.array([[38.2946, 51.6963], [73.5318, 51.5014], [56.0252, 71.7366], [41.5493, 92.3655], [70.7299, 92.2041]], dtype=np.float64)
+
+
+def arcface_crop(landmarks, size=112):
+    """The crop matrix M [2,3] float64 of `BiometricLoss.set_crop` from face landmarks: crop pixel index (u, v) -> image pixel index, the
+    least-squares similarity (Umeyama 1991, a reflection excluded) that carries the ArcFace template, scaled by size / 112, onto the face's five
+    points.  landmarks: [5,2] (x, y) -- left eye, right eye, nose tip, left and right mouth corner as the image shows them -- or the [68,2]
+    set of the Wing term, of which the eye centres mean(36:42) and mean(42:48), the nose tip 30 and the mouth corners 48 and 54 are taken.
+    Host only."""
+    pts = np.asarray(landmarks.detach().cpu().numpy() if isinstance(landmarks, torch.Tensor) else landmarks, dtype=np.float64)
+    if pts.shape == (68, 2):
+        pts = np.stack([pts[36:42].mean(0), pts[42:48].mean(0), pts[30], pts[48], pts[54]])
+    if pts.shape != (5, 2) or not np.all(np.isfinite(pts)):
+        raise ValueError(f"arcface_crop: landmarks must be finite [68,2] or [5,2] points (got {pts.shape})")
+    src = ARCFACE_TEMPLATE * (float(size) / 112.0)
+    mu_s, mu_d = src.mean(0), pts.mean(0)
+    sc, dc = src - mu_s, pts - mu_d
+    U, D, Vt = np.linalg.svd(dc.T @ sc / 5.0)
+    e = np.array([1.0, -1.0 if np.linalg.det(U) * np.linalg.det(Vt) < 0 else 1.0])      # the proper rotation closest to the fit, never a mirror image
+    R = U @ np.diag(e) @ Vt
+    scale = float((D * e).sum() / ((sc ** 2).sum() / 5.0))
+    return np.concatenate([scale * R, (mu_d - scale * R @ mu_s)[:, None]], axis=1)
+
+
+def scale_crop(M, f):
+    """M re-expressed for the image block-averaged by f (ProjectionArgs.pool_above): pixel index x of the image is index x' = (x + 1/2) / f - 1/2
+    of the pooled one (pixel centres; a block's mean sits at the block's centre).  M [2,3] or [n,2,3] -> float64 of the same shape."""
+    M = np.array(M.detach().cpu().numpy() if isinstance(M, torch.Tensor) else M, dtype=np.float64)
+    M[..., :, :2] /= float(f)
+    M[..., :, 2] = (M[..., :, 2] + 0.5) / float(f) - 0.5
+    return M
+
+
+def _resolve_crop(face_crop, landmarks, what):
+    """A face_crop argument as float64 matrices: given as such, or "landmarks" -> arcface_crop of one [68,2] / [5,2] set or of each of B sets."""
+    if isinstance(face_crop, str):
+        if face_crop != "landmarks":
+            raise ValueError(f"{what} must be a [2,3] matrix or 'landmarks' (got {face_crop!r})")
+        if landmarks is None:
+            raise ValueError(f"{what}='landmarks' needs the landmarks it is derived from")
+        lm = np.asarray(landmarks.detach().cpu().numpy() if isinstance(landmarks, torch.Tensor) else landmarks, dtype=np.float64)
+        return arcface_crop(lm) if lm.ndim == 2 else np.stack([arcface_crop(l) for l in lm])
+    return np.asarray(face_crop.detach().cpu().numpy() if isinstance(face_crop, torch.Tensor) else face_crop, dtype=np.float64)
 
 
 def face_region_weight(landmarks, size, inside=1.0, outside=0.0, feather=0.0):
@@ -374,7 +439,8 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                   eps=None, out_prefix=None, batch=DEFAULT_BATCH, use_graph=True, noise_mode="random", use_mse=True, seed=None,
                   landmark_fn=None, mode="literal", weight_decay=0.0, path_to_gen=None, keep_images=64, engine=None,
                   return_engine=False, latent_space="z", landmark_input="float", biometric=None, gamma=1.0, lbp_target=None, pipeline=None,
-                  mdf=None, optimize_noise=False, noise_init="randn", lpips_map=False, region_weight=None):
+                  mdf=None, optimize_noise=False, noise_init="randn", lpips_map=False, region_weight=None, face_crop=None,
+                  face_crop_filter="area"):
     """One full `projection(...)` call (:135-208).  `target`: [1,3,S,S] from image_transform; `lm_target` [68,2] and either
     `lm_steps` [steps,68,2] (injected landmark detections) or `landmark_fn` (host detector called on every generated image,
     see ProjectionEngine; landmark_input="gray_u8" hands it the drivers' gray uint8 image, built on the device).  mode="literal" is the loop as the reference executes it (best-of-N noisy sampling, `batch` steps per
@@ -415,6 +481,11 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     region_weight: a map [H,W] >= 0 at the size the image-space losses see that weights the LPIPS and pixel terms by region (both engines'
     region_weight; `face_region_weight` builds one from landmarks).  A re-targeted engine takes the new target's weight in place.
 
+    face_crop: the biometric term (an ArcFace embedder) embeds candidates and target through the aligned, antialiased face crop
+    (BiometricLoss.set_crop) instead of a resize of the whole frame: a [2,3] matrix, crop pixel index -> pixel index of the GENERATED image
+    (`arcface_crop`), or "landmarks" = arcface_crop(lm_target).  Under args.pool_above it is re-expressed for the pooled image the losses see
+    (`scale_crop`).  face_crop_filter: "area" (default) or "bilinear".  A re-targeted engine takes the new target's matrix in place.
+
     engine: a ProjectionEngine from an earlier call with the same generator, objective, step count and batch (return_engine=True
     hands it out) -- it is re-targeted in place (`ProjectionEngine.retarget`), which keeps its captured hipGraph and workspaces; this is
     how `project_many` walks a list of targets."""
@@ -432,6 +503,14 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     if lpips_map and tuple(target.shape[2:]) != (G.img_resolution, G.img_resolution):
         raise ValueError(f"lpips_map=True: the target is {tuple(target.shape[2:])}, the generated image {G.img_resolution}x{G.img_resolution} "
                          "(args.pool_above): the map is defined at the image's own size")
+    crop = None
+    if face_crop is not None:
+        if biometric is None:
+            raise ValueError("face_crop is the crop of the biometric term: pass biometric= with it")
+        crop = _resolve_crop(face_crop, lm_target, "face_crop")
+        r, pa = G.img_resolution, args.pool_above
+        if pa and r > pa and r // pa > 1:
+            crop = scale_crop(crop, r // pa)
     if latent_mean is None or latent_std is None:
         gen = None
         if seed is not None:
@@ -452,22 +531,25 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                                       ("noise_mode", engine.noise_mode == noise_mode), ("args", engine.args == args),
                                       ("landmark_fn", engine.landmark_fn is landmark_fn), ("biometric", engine.biometric is biometric),
                                       ("gamma", biometric is None or engine.gamma == float(gamma)), ("mdf", engine.mdf is mdf),
-                                      ("region_weight", engine.pixel.region_weighted == (region_weight is not None))) if not ok]
+                                      ("region_weight", engine.pixel.region_weighted == (region_weight is not None)),
+                                      ("face_crop", engine.face_crop_filter == (face_crop_filter if crop is not None else None))) if not ok]
         if diff:
             raise ValueError("engine= was built for another objective: " + ", ".join(diff) + " differ(s); build a fresh engine")
         eng = engine.retarget(target, lm_target=lm_target, lm_steps=lm_steps, eps=eps, seed=seed if eps is None else None,
-                              latent_mean=latent_mean, latent_std=float(latent_std), lbp_target=lbp_target, region_weight=region_weight)
+                              latent_mean=latent_mean, latent_std=float(latent_std), lbp_target=lbp_target, region_weight=region_weight,
+                              face_crop=crop)
     elif mode == "gradient":
         eng = GradientProjectionEngine(G, target, latent_mean, float(latent_std), args, weight_decay=weight_decay, percept=percept,
                                        lm_target=lm_target, lm_steps=lm_steps, eps=eps, noise_mode=noise_mode, use_graph=use_graph,
                                        use_mse=use_mse, landmark_fn=landmark_fn, seed=0 if seed is None else seed, latent_space=latent_space,
                                        biometric=biometric, gamma=gamma, mdf=mdf, optimize_noise=optimize_noise, noise_init=noise_init,
-                                       region_weight=region_weight)
+                                       region_weight=region_weight, face_crop=crop, face_crop_filter=face_crop_filter)
     else:
         eng = ProjectionEngine(G, target, latent_mean, float(latent_std), args, percept=percept, lm_target=lm_target,
                                lm_steps=lm_steps, eps=eps, noise_mode=noise_mode, use_graph=use_graph, batch=batch, use_mse=use_mse,
                                landmark_fn=landmark_fn, keep_images=keep, seed=0 if seed is None else seed, landmark_input=landmark_input,
-                               biometric=biometric, gamma=gamma, lbp_target=lbp_target, pipeline=pipeline, mdf=mdf, region_weight=region_weight)
+                               biometric=biometric, gamma=gamma, lbp_target=lbp_target, pipeline=pipeline, mdf=mdf, region_weight=region_weight,
+                               face_crop=crop, face_crop_filter=face_crop_filter)
     w, step, loss, losses = eng.run().result()
     out = {"w": w, "step": step, "loss": loss, "losses": losses}
     best_noises = None
@@ -494,7 +576,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     return out
 
 
-def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_weights=None, **kw):
+def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_weights=None, face_crops=None, **kw):
     """Pair-level sharding of BASELINE configs 3/5: rank r projects `targets[r::world]` (or, with dynamic=True, whatever the
     shared `distributed.WorkQueue` hands it), then ONE all_gather returns every item's {latent, loss, step} to every rank.
     targets: list of [1,3,S,S] device tensors (or image paths); landmarks: optional list of (lm_target, lm_steps) per item.
@@ -504,10 +586,15 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_w
     re-targets it for the others, as the reference keeps G / percept / latent statistics outside its per-image loop
     (projection_example_v2_percept_morph.py:311-355).
     region_weights: one region weight [H,W] for every item, or a list with one per item (project_image's region_weight).
+    face_crops: one face crop per item (project_image's face_crop: a [2,3] matrix or "landmarks"), set before the item is projected -- a
+    re-targeted engine takes it in place, a lockstep group gets its items' matrices as one [B,2,3] stack.
     Returns dict(latents [N,k,D], losses [N], steps [N], items [N]) ordered by item id, plus `mine`: the items this rank worked on."""
     if isinstance(region_weights, (list, tuple)) and len(region_weights) != len(targets):
         raise ValueError(f"project_many: {len(region_weights)} region weights for {len(targets)} targets")
     rw = lambda i: region_weights[i] if isinstance(region_weights, (list, tuple)) else region_weights
+    if face_crops is not None and len(face_crops) != len(targets):
+        raise ValueError(f"project_many: {len(face_crops)} face crops for {len(targets)} targets")
+    fc = lambda i: {} if face_crops is None else {"face_crop": face_crops[i]}
     import torch.distributed as dist
     from .distributed import gather_many, pack_result, run_sharded, shard_items, unpack_results
     on = dist.is_available() and dist.is_initialized()
@@ -529,7 +616,8 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_w
         for g0 in range(0, len(mine), lockstep):
             ids = mine[g0:g0 + lockstep]
             res = _project_group(G, [load(targets[i]) for i in ids], [landmarks[i] for i in ids] if landmarks is not None else None,
-                                 region_weight=None if region_weights is None else [rw(i) for i in ids], **kw)
+                                 region_weight=None if region_weights is None else [rw(i) for i in ids],
+                                 **({} if face_crops is None else {"face_crop": [face_crops[i] for i in ids]}), **kw)
             recs += [pack_result(res["w"][j:j + 1].to(G.device), float(res["loss"][j]), int(res["step"][j]), item=i) for j, i in enumerate(ids)]
         rows = torch.stack(recs) if recs else torch.empty([0, width], dtype=torch.float64, device=G.device)
         out = unpack_results(gather_many(rows, -(-len(targets) // world)), lshape)
@@ -550,7 +638,7 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_w
         eng = state["eng"]
         if eng is not None and eng.use_wing != (lm_t is not None):
             eng = None                     # an item with / without landmarks after one without / with: another objective, a fresh engine
-        r = project_image(G, load(targets[i]), lm_t, lm_s, engine=eng, return_engine=reuse, region_weight=rw(i), **kw)
+        r = project_image(G, load(targets[i]), lm_t, lm_s, engine=eng, return_engine=reuse, region_weight=rw(i), **fc(i), **kw)
         state["eng"] = r.get("engine")
         return pack_result(r["w"].to(G.device), r["loss"], r["step"], item=i)
 
@@ -616,7 +704,8 @@ def morph_pairs(G, pairs, src_dir, dst_raw, dst_morph, landmarks=None, truncatio
 
 def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=None, latent_mean=None, latent_std=None, eps=None,
                    use_graph=True, noise_mode="random", use_mse=True, seed=None, weight_decay=0.0, mode="gradient", latent_space="z",
-                   biometric=None, gamma=1.0, batch=None, pipeline=None, mdf=None, region_weight=None, **unused):
+                   biometric=None, gamma=1.0, batch=None, pipeline=None, mdf=None, region_weight=None, face_crop=None,
+                   face_crop_filter="area", **unused):
     """B targets through one lockstep GradientProjectionEngine; returns dict(w [B,k,D] (W+: [B,k,num_ws,D]), step [B], loss [B],
     losses [B,steps])."""
     args = args or ProjectionArgs()
@@ -640,10 +729,14 @@ def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=N
         lm_t, lm_s = np.stack([np.asarray(l[0]) for l in landmarks]), np.stack([np.asarray(l[1]) for l in landmarks])
     if len(targets) == 1 and lm_t is not None:
         lm_t, lm_s = lm_t[0], lm_s[0]
+    crop = None
+    if face_crop is not None:                       # one crop per target of the group
+        crop = np.stack([_resolve_crop(c, None if landmarks is None else landmarks[j][0], "face_crops[i]").reshape(2, 3)
+                         for j, c in enumerate(face_crop)])
     eng = GradientProjectionEngine(G, tg, latent_mean, float(latent_std), args, weight_decay=weight_decay, percept=percept,
                                    lm_target=lm_t, lm_steps=lm_s, eps=eps, noise_mode=noise_mode, use_graph=use_graph, use_mse=use_mse,
                                    seed=0 if seed is None else seed, latent_space=latent_space, biometric=biometric, gamma=gamma,
-                                   region_weight=region_weight)
+                                   region_weight=region_weight, face_crop=crop, face_crop_filter=face_crop_filter)
     w, step, loss, losses = eng.run().result()
     if len(targets) == 1:
         return {"w": w, "step": np.array([step]), "loss": np.array([loss]), "losses": losses[None]}

@@ -69,15 +69,56 @@ class FaceEmbedder:
 
 class ArcFaceEmbedder(FaceEmbedder):
     """The ArcFace layout: embed(x112 [n,3,112,112] in [-1,1]) -> [n,512]; `embed_image` first resizes any [n,3,H,W] image bilinearly to
-    112x112 (into `x112`), `backward` ends by scattering the 112x112 gradient back through that resize."""
+    112x112 (into `x112`), `backward` ends by scattering the 112x112 gradient back through that resize.  With `set_crop` the resize becomes
+    the aligned, antialiased crop of mgf_face_crop_f32 and the scatter its adjoint."""
     _gp = _gn = None                 # transposed taps / batch size of the backward workspace (`_grad_ws` of the network, on first use)
+    _crop = None                     # (float64 [m,2,3] device buffer, filter id) of set_crop; in `_MUTABLE`: a clone starts without one
+    CROP_FILTERS = {"area": 0, "bilinear": 1}
+
+    def set_crop(self, matrices, filter="area"):
+        """matrices [2,3], [1,2,3] (shared) or [n,2,3] (one per image): crop pixel index (u, v) -> source pixel index, (x, y) = M (u, v, 1)
+        (cv2.warpAffine's WARP_INVERSE_MAP; drivers.arcface_crop makes one from landmarks); None restores the plain resize.  filter "area":
+        S x S bilinear samples per crop pixel, S from the matrix; "bilinear": one.  The values are checked here, once -- the kernels cannot
+        return an error -- and live in a device buffer that is rewritten IN PLACE while the shape stays (a captured hipGraph keeps reading it)."""
+        if matrices is None:
+            self._crop = None
+            return
+        m, fid = self.check_crop(matrices, filter)
+        buf = self._crop[0] if self._crop is not None and self._crop[0].shape == m.shape else torch.empty(m.shape, dtype=torch.float64, device=self.device)
+        buf.copy_(torch.from_numpy(m))
+        self._crop = (buf, fid)
+
+    @classmethod
+    def check_crop(cls, matrices, filter="area"):
+        """What set_crop refuses, without setting anything: -> (float64 numpy [m,2,3], filter id).  ValueError for a wrong shape or filter name,
+        MgfError for the values mgf_face_crop_check refuses (non-finite, singular, more than 16 sub-samples per side with "area")."""
+        if filter not in cls.CROP_FILTERS:
+            raise ValueError(f"set_crop: filter must be 'area' or 'bilinear' (got {filter!r})")
+        m = np64(matrices)
+        if m.shape != (2, 3) and (m.ndim != 3 or m.shape[1:] != (2, 3) or m.shape[0] < 1):
+            raise ValueError(f"set_crop: matrices must be [2,3], [1,2,3] or [n,2,3] (got {list(m.shape)})")
+        m = np.ascontiguousarray(m.reshape(-1, 2, 3))
+        fid = cls.CROP_FILTERS[filter]
+        _lib.check(_lib.lib().mgf_face_crop_check(m.ctypes.data, m.shape[0], fid), "set_crop")
+        return m, fid
+
+    def _crop_args(self, n):
+        mats, fid = self._crop
+        if mats.shape[0] not in (1, n):
+            raise _lib.MgfError(f"set_crop was given {mats.shape[0]} matrices, the batch has {n} images (one shared matrix, or one per image)")
+        return mats.data_ptr(), int(mats.shape[0]), fid
 
     def embed_image(self, img, out=None):
-        """img [n,3,H,W] in [-1,1] -> embedding; bilinear resize (align_corners=False) to the 112x112 ArcFace input."""
+        """img [n,3,H,W] in [-1,1] -> embedding; bilinear resize (align_corners=False) to the 112x112 ArcFace input, or the crop of set_crop."""
         _lib.require_gpu(img)
         n, c, h, w = img.shape
         if n != self.n:
             self._alloc(n)
+        if self._crop is not None:
+            mp, mc, fid = self._crop_args(n)
+            _lib.check(_lib.lib().mgf_face_crop_f32(self.x112.data_ptr(), img.contiguous().data_ptr(), mp, n, h, w, 112, mc, fid, _lib.stream_ptr()),
+                       "face_crop")
+            return self.embed(self.x112, out)
         if (h, w) == (112, 112):
             return self.embed(img.contiguous(), out)
         _lib.check(_lib.lib().mgf_resize_bilinear_f32(self.x112.data_ptr(), img.contiguous().data_ptr(), n * c, h, w, 112, 112,
@@ -88,6 +129,12 @@ class ArcFaceEmbedder(FaceEmbedder):
         """The tail of `backward`: d112 itself, or scattered through the resize into dimg [n,3,H,W] (added when `accumulate`)."""
         if dimg is None:
             return d112
+        if self._crop is not None:
+            h, w = dimg.shape[2:]
+            mp, mc, fid = self._crop_args(self.n)
+            _lib.check(_lib.lib().mgf_face_crop_bwd_f32(dimg.data_ptr(), d112.data_ptr(), mp, self.n, h, w, 112, mc, fid, int(bool(accumulate)),
+                                                        _lib.stream_ptr()), "face_crop_bwd")
+            return dimg
         if not accumulate:
             dimg.zero_()
         h, w = dimg.shape[2:]

@@ -69,7 +69,7 @@ def random_state(depth=50, seed=0):
 class IResNetEmbedder(ArcFaceEmbedder):
     """embed(x112 [n,3,112,112] in [-1,1]) -> [n,512]; `embed_image` first resizes any [n,3,H,W] image bilinearly to 112x112."""
 
-    _MUTABLE = ("bufs", "x112", "stem_out", "flat", "out")
+    _MUTABLE = ("bufs", "x112", "stem_out", "flat", "out", "_crop")
 
     def __init__(self, state=None, depth=50, n=1, device="cuda", seed=0):
         _lib.lib()

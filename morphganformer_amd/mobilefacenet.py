@@ -76,7 +76,7 @@ def random_state(seed=0):
 class MobileFaceNetEmbedder(ArcFaceEmbedder):
     """embed(x112 [n,3,112,112] in [-1,1]) -> [n,512]; `embed_image` first resizes any [n,3,H,W] image bilinearly to 112x112."""
 
-    _MUTABLE = ("x112", "stem_out", "dw1_out", "bufs", "sep_out", "pool", "out", "stages")
+    _MUTABLE = ("x112", "stem_out", "dw1_out", "bufs", "sep_out", "pool", "out", "stages", "_crop")
 
     def __init__(self, state=None, n=1, device="cuda", seed=0, fp16=False, num_features=EMB):
         if fp16:

@@ -165,7 +165,8 @@ class ProjectionEngine:
     def __init__(self, G, target, latent_mean, latent_std, args: ProjectionArgs = None, percept=None, use_mse=True,
                  lm_target=None, lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, batch=1,
                  landmark_fn=None, biometric=None, gamma=1.0, wing_kind="wing", landmark_model=None, pipeline=False, keep_images=0,
-                 latent_shape=None, landmark_input="float", lbp_target=None, mdf=None, region_weight=None):
+                 latent_shape=None, landmark_input="float", lbp_target=None, mdf=None, region_weight=None, face_crop=None,
+                 face_crop_target=None, face_crop_target_b=None, face_crop_filter="area"):
         """batch = number of consecutive loop steps evaluated per generator forward.  In literal mode the steps do not depend
         on each other (latent_in never changes), so evaluating `batch` candidates at once and examining them in step order
         gives exactly the sequential loop's result while the small 4x4..64x64 layers, the mapping network and the LPIPS tail
@@ -212,7 +213,13 @@ class ProjectionEngine:
         region_weight: a map W [H,W] (or [1,1,H,W]) >= 0 with a positive sum, at the size the image-space losses see (the pooled size with
         pool_above): the LPIPS term becomes sum_l sum_p omega_l[p] m_l[p] (PerceptualLoss.set_region_weight) and the pixel term
         sum_c sum_p W[p] (x - t)^2 / (C sum W) (mgf_mse_weighted_f32).  A constant W is today's objective.  Wing, biometric and MDF terms
-        ignore it; the DSSIM / MS-SSIM / PSNR / LBP pixel terms and latent_copies > 1 refuse it."""
+        ignore it; the DSSIM / MS-SSIM / PSNR / LBP pixel terms and latent_copies > 1 refuse it.
+
+        face_crop: the biometric term embeds through the aligned face crop (BiometricLoss.set_crop; an ArcFace embedder) -- the [2,3] matrix of
+        the candidates, crop pixel index -> pixel index of the image the losses see (the pooled one under pool_above: drivers.scale_crop);
+        face_crop_target / face_crop_target_b: the matrices of the target image(s), face_crop by default; face_crop_filter "area" or
+        "bilinear".  The engine only hands them to `biometric.set_crop` ahead of its set_target calls; without face_crop it never touches the
+        crop, and one set on the BiometricLoss by hand stays."""
         self.G, self.args = G, args or ProjectionArgs()
         self.batch = int(batch)
         assert self.batch >= 1
@@ -275,6 +282,14 @@ class ProjectionEngine:
         if self.percept is not None:
             self.percept.set_target(self.target)
         self.biometric, self.gamma = biometric, float(gamma)
+        self.face_crop_filter = face_crop_filter if face_crop is not None else None
+        if face_crop is not None:
+            if biometric is None:
+                raise ValueError("face_crop is the crop of the biometric term: pass biometric= with it")
+            biometric.forget_target()             # (another engine's, perhaps of another batch size: set_target follows below)
+            biometric.set_crop(face_crop, face_crop_target, face_crop_target_b, filter=face_crop_filter)
+        elif face_crop_target is not None or face_crop_target_b is not None:
+            raise ValueError("face_crop_target / face_crop_target_b need face_crop (the candidates' matrix)")
         if biometric is not None:
             biometric.set_target(self.target)
         self.mdf = mdf
@@ -721,7 +736,7 @@ class ProjectionEngine:
         return self
 
     def retarget(self, target, lm_target=None, lm_steps=None, lm_valid=None, eps=None, seed=None, latent_mean=None, latent_std=None,
-                 lbp_target=None, region_weight=None):
+                 lbp_target=None, region_weight=None, face_crop=None, face_crop_target=None):
         """Point this engine at ANOTHER target image and rewind the loop, keeping everything that was expensive to set up: the captured
         hipGraph(s), the generator workspace, the LPIPS / embedder workspaces, the loss scratch.  Only data changes, in place, in the
         buffers the graph already references: the target image and its cached LPIPS taps / embedding, the landmark tables, the noise
@@ -730,7 +745,8 @@ class ProjectionEngine:
         on the same inputs bit for bit (tests/test_hip_drivers.py).  This is what the reference's serial per-image loop amortises by
         keeping G / percept / latent statistics outside `projection()` (projection_example_v2_percept_morph.py:311-355); BASELINE
         configs 3 and 5 are batches of targets.  region_weight: the new target's region weight, written into the weight buffers in place (an
-        engine built with a weight; without the argument the weight stays)."""
+        engine built with a weight; without the argument the weight stays).  face_crop / face_crop_target: the new target's crop matrices (an
+        engine built with face_crop; the matrix buffer the captured launches read is rewritten in place; without the argument the crop stays)."""
         a, dev = self.args, self.device
         _lib.require_gpu(target)
         assert tuple(target.shape) == tuple(self.target.shape), (tuple(target.shape), tuple(self.target.shape))
@@ -741,6 +757,11 @@ class ProjectionEngine:
         self.pixel.refresh_target(self.target, lbp_target)
         if self.percept is not None:
             self.percept.set_target(self.target)                  # same shapes: rewrites the cached taps in place
+        if face_crop is not None:
+            if self.face_crop_filter is None:
+                raise _lib.MgfError("retarget: this engine was built without a face crop; build a fresh one with face_crop=")
+            self.biometric.forget_target()        # set_target follows: one embedder pass for the new target, not two
+            self.biometric.set_crop(face_crop, face_crop_target, filter=self.face_crop_filter)
         if self.biometric is not None:
             self.biometric.set_target(self.target)
         if self.mdf is not None:
@@ -834,7 +855,8 @@ class GradientProjectionEngine(ProjectionEngine):
                  lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, landmark_fn=None, biometric=None,
                  gamma=1.0, wing_kind="wing", landmark_model=None, betas=(0.9, 0.999), adam_eps=1e-8, weight_decay=0.0,
                  latent_space="z", mdf=None, optimize_noise=False, noise_init="randn", target_b=None, morph_alpha=0.5, id_balance=0.0,
-                 id_metric="mse", lm_target_b=None, region_weight=None, **ignored):
+                 id_metric="mse", lm_target_b=None, region_weight=None, face_crop=None, face_crop_target=None, face_crop_target_b=None,
+                 face_crop_filter="area", **ignored):
         """latent_space: "z" -- the drivers' parameter, the gradient runs on through the mapping network -- or "w+": the parameter is the
         per-layer intermediate latent ws [k, num_ws, D] itself (north_star: "backprops into the k-component latent W+"; layer `slot` reads
         ws[:, slot], networks.py:1252-1253), perturbed, descended by Adam and kept best-of exactly like z.  latent_mean is then a w-space
@@ -885,7 +907,9 @@ class GradientProjectionEngine(ProjectionEngine):
         super().__init__(G, target, latent_mean, latent_std, args, percept=percept, use_mse=use_mse, lm_target=lm_target,
                          lm_steps=lm_steps, lm_valid=lm_valid, eps=eps, noise_mode=noise_mode, seed=seed, use_graph=use_graph, batch=1,
                          landmark_fn=landmark_fn, biometric=biometric, gamma=gamma, wing_kind=wing_kind,
-                         landmark_model=landmark_model, pipeline=False, keep_images=0, latent_shape=ls, mdf=mdf, region_weight=region_weight)
+                         landmark_model=landmark_model, pipeline=False, keep_images=0, latent_shape=ls, mdf=mdf, region_weight=region_weight,
+                         face_crop=face_crop, face_crop_target=face_crop_target, face_crop_target_b=face_crop_target_b,
+                         face_crop_filter=face_crop_filter)
         self.targets = B
         a, dev = self.args, self.device
         if biometric is not None:
