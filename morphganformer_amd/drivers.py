@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib, misc
-from .projection import GradientProjectionEngine, ProjectionArgs, ProjectionEngine, latent_stats, latent_stats_w
+from .projection import GradientProjectionEngine, ProjectionArgs, ProjectionEngine, seeded_generator, seeded_latent_stats, seeded_randn
 
 
 # ----------------------------------------------------------------------------------------------------------------- image I/O
@@ -110,10 +110,7 @@ def load_latent_mat(path):
 # ----------------------------------------------------------------------------------------------------------------- drivers
 def generate_images(G, images_num=32, truncation_psi=0.7, output_dir=None, ratio=1.0, seed=None, noise_mode="random"):
     """1024_generate.py:31-41.  Returns the list of z tensors used (and writes sample_%06d.png when `output_dir` is given)."""
-    gen = None
-    if seed is not None:
-        gen = torch.Generator(device=G.device)
-        gen.manual_seed(seed)
+    gen = seeded_generator(G.device, seed)
     zs = []
     for i in range(images_num):
         z = torch.randn([1, G.cfg.k, G.cfg.z_dim], device=G.device, generator=gen)
@@ -204,16 +201,10 @@ def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, ar
     B = len(alphas)
     dev = G.device
     if latent_std is None:
-        gen = None
-        if seed is not None:
-            gen = torch.Generator(device=dev)
-            gen.manual_seed(seed)
-        _, latent_std = (latent_stats_w if space == "w+" else latent_stats)(G, args.n_mean_latent, dev, generator=gen)
+        _, latent_std = seeded_latent_stats(G, args, space, seed)
     ls = tuple(a1.shape[1:])
     if eps is None:                      # one stream for the whole sweep: lockstep or not, alpha j sees the same noise
-        gen = torch.Generator(device=dev)
-        gen.manual_seed(0 if seed is None else seed)
-        eps = torch.randn(args.step, B, *ls, device=dev, generator=gen)
+        eps = seeded_randn((args.step, B, *ls), dev, 0 if seed is None else seed)
     eps = eps.to(dev).float().reshape(-1, B, *ls)
     crop_kw = lambda js: {}
     if face_crop is not None or face_crop_b is not None:
@@ -512,12 +503,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
         if pa and r > pa and r // pa > 1:
             crop = scale_crop(crop, r // pa)
     if latent_mean is None or latent_std is None:
-        gen = None
-        if seed is not None:
-            gen = torch.Generator(device=G.device)
-            gen.manual_seed(seed)
-        stats = latent_stats_w if latent_space == "w+" else latent_stats
-        latent_mean, latent_std = stats(G, args.n_mean_latent, G.device, generator=gen)
+        latent_mean, latent_std = seeded_latent_stats(G, args, latent_space, seed)
     if pipeline is None:
         pipeline = mode == "literal" and landmark_fn is None and biometric is None and getattr(percept, "net", None) == "squeeze"
     keep = max(int(keep_images), int(batch)) if path_to_gen is not None and mode == "literal" else 0
@@ -625,12 +611,7 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_w
         return out
     reuse = kw.get("mode", "literal") == "literal" and kw.get("landmark_fn") is None and kw.get("eps") is None
     if reuse and (kw.get("latent_mean") is None or kw.get("latent_std") is None):
-        a = kw.get("args") or ProjectionArgs()
-        gen = None
-        if kw.get("seed") is not None:
-            gen = torch.Generator(device=G.device)
-            gen.manual_seed(kw["seed"])
-        kw["latent_mean"], kw["latent_std"] = latent_stats(G, a.n_mean_latent, G.device, generator=gen)     # once per rank, not per item
+        kw["latent_mean"], kw["latent_std"] = seeded_latent_stats(G, kw.get("args") or ProjectionArgs(), "z", kw.get("seed"))   # once per rank, not per item
     state = {"eng": None}
 
     def work(i):
@@ -715,11 +696,7 @@ def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=N
         unused = dict(unused, **({"pipeline": pipeline} if pipeline else {}))
         raise TypeError(f"project_many(lockstep=...): unsupported arguments {sorted(unused)}")
     if latent_mean is None or latent_std is None:
-        gen = None
-        if seed is not None:
-            gen = torch.Generator(device=G.device)
-            gen.manual_seed(seed)
-        latent_mean, latent_std = (latent_stats_w if latent_space == "w+" else latent_stats)(G, args.n_mean_latent, G.device, generator=gen)
+        latent_mean, latent_std = seeded_latent_stats(G, args, latent_space, seed)
     tg = torch.cat([t.reshape(1, *t.shape[-3:]) for t in targets]).contiguous()
     if region_weight is not None:                   # one map per target of the group
         region_weight = torch.stack([torch.as_tensor(np.asarray(w.detach().cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float64)).reshape(

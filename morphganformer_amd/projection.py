@@ -19,20 +19,23 @@ reference makes three crossings of 12.6 MB per step).  Landmark extraction is dl
 (:159-170) -- a third-party detector that is not reproducible offline -- so landmarks enter as an injected [steps,68,2]
 float64 table (and a `valid` table for the "no face found -> continue" branch, :165-166).
 
-`GradientProjectionEngine` below is the gradient-descent reading of the north star (the loss is back-propagated into the
-latent and Adam moves it) -- the loop the drivers set up (optimizer, lr schedule) but never get (the detach severs it).
+`GradientProjectionEngine` (gradient_projection.py, importable from here) is the gradient-descent reading of the north star (the loss is
+back-propagated into the latent and Adam moves it) -- the loop the drivers set up (optimizer, lr schedule) but never get (the detach severs it).
 """
 from __future__ import annotations
 
 import math
 import os
+import weakref
 from dataclasses import dataclass
+from functools import partial
 
 import numpy as np
 import torch
 
 from . import _lib
 from .pixel_term import MSSSIM_WEIGHTS, PixelTerm, msssim_max_levels, msssim_weights  # noqa: F401  (the MS-SSIM helpers are public here)
+from .trail import ImprovementTrail
 
 
 @dataclass
@@ -158,9 +161,27 @@ def latent_stats_w(G, n_mean_latent=10000, device="cuda", generator=None):
     return mean, std
 
 
+def seeded_generator(device, seed):
+    """A generator of its own on `device`, seeded with `seed`; None (torch's global stream) without a seed."""
+    return None if seed is None else torch.Generator(device=device).manual_seed(seed)
+
+
+def seeded_randn(shape, device, seed):
+    """N(0, 1) float32 of `shape` on `device`, the head of the stream `seed` keys."""
+    return torch.randn(*shape, device=device, generator=seeded_generator(device, seed))
+
+
+def seeded_latent_stats(G, args, latent_space="z", seed=None):
+    """(latent_mean, latent_std) of the latent space a projection searches ("z": latent_stats, "w+": latent_stats_w) from
+    args.n_mean_latent samples of the stream `seed` keys (None: torch's global stream)."""
+    stats = latent_stats_w if latent_space == "w+" else latent_stats
+    return stats(G, args.n_mean_latent, G.device, generator=seeded_generator(G.device, seed))
+
+
 class ProjectionEngine:
     """One target image <-> one latent search, replayable as a hipGraph."""
     _lockstep = False           # several targets per engine: GradientProjectionEngine only
+    graph_debug = False         # True (set from outside before the first run()): captures keep their hipGraph_t, so that its nodes can be counted (bench.py)
 
     def __init__(self, G, target, latent_mean, latent_std, args: ProjectionArgs = None, percept=None, use_mse=True,
                  lm_target=None, lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, batch=1,
@@ -269,50 +290,30 @@ class ProjectionEngine:
             lm_valid = np.zeros(a.step + spare, np.int32)
             if not self.callback_graphs:
                 use_graph = False
+        self._table = []                            # the loop state: (tensor, reset value) in registration order, see _reg
         self._init_state(nt, latent_mean, latent_std, eps, seed, lm_target, lm_steps, lm_valid)
         B = nt * self.batch                         # images per generator call
         self._arange = torch.arange(B, dtype=torch.int64, device=dev)
         self._init_pool(B)
         self.pixel = PixelTerm(a, self.use_mse, self.target.shape, B, dev, region_weight is not None, G.cfg.img_resolution)
-        self.pixel.refresh_target(self.target, lbp_target)
-        if region_weight is not None:
-            self._set_region(region_weight)
-        elif percept is not None and hasattr(percept, "set_region_weight"):
-            percept.set_region_weight(None)
-        if self.percept is not None:
-            self.percept.set_target(self.target)
-        self.biometric, self.gamma = biometric, float(gamma)
+        self.biometric, self.gamma, self.mdf = biometric, float(gamma), mdf
         self.face_crop_filter = face_crop_filter if face_crop is not None else None
-        if face_crop is not None:
-            if biometric is None:
-                raise ValueError("face_crop is the crop of the biometric term: pass biometric= with it")
-            biometric.forget_target()             # (another engine's, perhaps of another batch size: set_target follows below)
-            biometric.set_crop(face_crop, face_crop_target, face_crop_target_b, filter=face_crop_filter)
-        elif face_crop_target is not None or face_crop_target_b is not None:
+        if face_crop is not None and biometric is None:
+            raise ValueError("face_crop is the crop of the biometric term: pass biometric= with it")
+        if face_crop is None and (face_crop_target is not None or face_crop_target_b is not None):
             raise ValueError("face_crop_target / face_crop_target_b need face_crop (the candidates' matrix)")
-        if biometric is not None:
-            biometric.set_target(self.target)
-        self.mdf = mdf
-        if mdf is not None:
-            mdf.set_target(self.target)
+        if region_weight is None and percept is not None and hasattr(percept, "set_region_weight"):
+            percept.set_region_weight(None)
+        self._set_targets(None, lbp_target, region_weight, face_crop, face_crop_target, face_crop_target_b)
         # the p_loss slot takes LPIPS, the biometric term and MDF in that order: a term accumulates where one in front of it has written
         self.bio_accumulate = percept is not None
         self.mdf_accumulate = percept is not None or biometric is not None
         self.has_p = self.mdf_accumulate or mdf is not None                     # the slot is live
         self.keep_images = int(keep_images)
+        self.trail = None                           # the improvement trail (keep_images > 0): select_best fills its slot, _loss_phase its images
         if self.keep_images > 0:
-            per = G.cfg.img_channels * G.cfg.img_resolution ** 2
-            self.trail_imgs = torch.empty(self.keep_images, per, dtype=torch.float32, device=dev)
-            self.trail_steps = torch.full([self.keep_images], -1, dtype=torch.int32, device=dev)
-            self.trail_losses = torch.zeros(self.keep_images, dtype=torch.float64, device=dev)
-            self.trail_count = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.take_slot = torch.full([B], -1, dtype=torch.int32, device=dev)
-            if self.keep_images < B:
-                import warnings
-                warnings.warn(f"ProjectionEngine: keep_images={self.keep_images} < batch={B}: one launch sequence can improve more often than "
-                              "there are trail slots, and then only the latest improvement of the overflow keeps its image (the reference "
-                              "writes a PNG at every improvement); use keep_images >= batch", stacklevel=2)
-        self._spilled, self._seq_since_spill, self._trail_lost = [], 0, 0
+            self.trail = ImprovementTrail(self.keep_images, B, (G.cfg.img_channels, G.cfg.img_resolution), dev)
+            self._table += self.trail.state()
         self.use_graph = use_graph
         self.graph = None
         if self.callback_graphs:
@@ -334,7 +335,7 @@ class ProjectionEngine:
                 G._alloc(B, True)
             self.latent_ns = [self.latent_n, torch.empty_like(self.latent_n)]
             self.imgs = [G.img, torch.empty_like(G.img)]
-            self.gen_ctr = torch.zeros(1, dtype=torch.int32, device=dev)          # step counter of the generator side
+            self.gen_ctr = self._reg(torch.zeros(1, dtype=torch.int32, device=dev), 0)   # step counter of the generator side
             self.loss_stream = torch.cuda.Stream(device=dev)
             self.graphs = [None, None]
             self.prime_graph = None
@@ -356,9 +357,7 @@ class ProjectionEngine:
         self.sigma = torch.as_tensor(noise_schedule(a.step, float(latent_std), a.noise, a.noise_ramp), device=dev)
         copies = (self.copies,) if self.copies > 1 else ()
         if eps is None:
-            gen = torch.Generator(device=dev)
-            gen.manual_seed(seed)
-            eps = torch.randn(a.step, nt, *copies, *ls, device=dev, generator=gen)
+            eps = seeded_randn((a.step, nt, *copies, *ls), dev, seed)
         self.eps = eps.to(dev).contiguous().float()
         assert self.eps.shape[0] >= a.step and (self.eps[0].numel() == self.numel * self.copies if nt == 1
                                                 else tuple(self.eps.shape[1:]) == (nt, *ls)), \
@@ -377,22 +376,44 @@ class ProjectionEngine:
         if nt > 1 and self.valid is not None:
             self.valid = self.valid.reshape(nt, -1)
         # device-resident loop state, one row per target (select_best advances a target's own counter)
-        self.step_ctr = torch.zeros(nt, dtype=torch.int32, device=dev)
-        self.min_loss = torch.full([nt], float(a.min_loss_init), dtype=torch.float64, device=dev)
-        self.best_latent = torch.zeros(nt, *ls, dtype=torch.float32, device=dev)
-        self.best_step = torch.full([nt], -1, dtype=torch.int32, device=dev)
-        self.losses = torch.full([a.step] if nt == 1 else [nt, a.step], float("nan"), dtype=torch.float64, device=dev)
+        self.step_ctr = self._reg(torch.zeros(nt, dtype=torch.int32, device=dev), 0)
+        self.min_loss = self._reg(torch.full([nt], float(a.min_loss_init), dtype=torch.float64, device=dev), float(a.min_loss_init))
+        self.best_latent = self._reg(torch.zeros(nt, *ls, dtype=torch.float32, device=dev), 0)
+        self.best_step = self._reg(torch.full([nt], -1, dtype=torch.int32, device=dev), -1)
+        self.losses = self._reg(torch.full([a.step] if nt == 1 else [nt, a.step], float("nan"), dtype=torch.float64, device=dev), float("nan"))
         n = nt * self.batch
         self.latent_n = torch.empty(n, *ls, dtype=torch.float32, device=dev)
         self.p_loss = torch.zeros(n, dtype=torch.float32, device=dev)
         self.mse_loss = torch.zeros(n, dtype=torch.float32, device=dev)
         self.w_loss = torch.zeros(n, dtype=torch.float64, device=dev)
 
-    def _set_region(self, region_weight):
-        """Write a region weight into the buffers the launch sequence reads (in place: captured graphs reference them)."""
-        w = self.pixel.set_region_weight(region_weight)
+    def _reg(self, tensor, reset=None):
+        """Register a loop-state tensor where it is allocated, and return it.  Every registered tensor is saved and restored around a graph
+        capture (_state); `reset` is the value it was allocated with, which rewind() gives it again; None: rewind() leaves it where the run left
+        it (the start latent, the Adam moments, the noise maps and theirs)."""
+        self._table.append((tensor, reset))
+        return tensor
+
+    def _set_targets(self, target, lbp_target, region_weight, face_crop, face_crop_target, face_crop_target_b=None):
+        """Hand the target (and what comes with one: region weight, LBP code map, crop matrices) to every term, in place in the buffers the
+        launch sequence reads -- captured graphs reference them.  The constructor (target None: self.target is the new copy) and retarget();
+        a weight / crop of None stays as it is."""
+        if region_weight is not None:
+            w = self.pixel.set_region_weight(region_weight)
+            if self.percept is not None:
+                self.percept.set_region_weight(w[:, None])
+        if target is not None:
+            self.target.copy_(target)
+        self.pixel.refresh_target(self.target, lbp_target)
         if self.percept is not None:
-            self.percept.set_region_weight(w[:, None])
+            self.percept.set_target(self.target)                  # same shapes on a retarget: rewrites the cached taps in place
+        if face_crop is not None:
+            self.biometric.forget_target()        # (another engine's or the last target's: set_target follows, one embedder pass, not two)
+            self.biometric.set_crop(face_crop, face_crop_target, face_crop_target_b, filter=self.face_crop_filter)
+        if self.biometric is not None:
+            self.biometric.set_target(self.target)
+        if self.mdf is not None:
+            self.mdf.set_target(self.target)
 
     def _init_pool(self, B):
         """projection_example_v1.py:150-155: images above `pool_above` pixels are block-averaged by height // pool_above in front of the
@@ -451,35 +472,56 @@ class ProjectionEngine:
             self.pixel.lbp_into(self.w_loss, full_img)
         if self.use_wing:
             _wing_into(self.wing_kind, self.w_loss, self.lm_steps, self.lm_target, B, self.step_ctr)
-        keep = self.keep_images > 0
-        _lib.check(L.mgf_select_best(self.min_loss.data_ptr(), self.best_latent.data_ptr(), self.best_step.data_ptr(),
-                                     self.losses.data_ptr(), latent_n.data_ptr(), self.numel,
-                                     _lib.ptr(self.p_loss if self.has_p else None),
-                                     _lib.ptr(self.w_loss if (self.use_wing or self.use_lbp) else None),
-                                     _lib.ptr(self.mse_loss if self.use_mse else None), 1.0 if self.use_lbp else float(a.lamda), float(a.beta),
-                                     self.step_ctr.data_ptr(), _lib.ptr(self.valid), B, self.steps,
-                                     _lib.ptr(self.take_slot if keep else None), _lib.ptr(self.trail_count if keep else None),
-                                     self.keep_images, _lib.ptr(self.trail_steps if keep else None),
-                                     _lib.ptr(self.trail_losses if keep else None), st), "select_best")
-        if keep:
-            _lib.check(L.mgf_keep_improvements(self.trail_imgs.data_ptr(), full_img.data_ptr(), self.trail_imgs.shape[1],
-                                               self.take_slot.data_ptr(), B, st), "keep_improvements")
+        self._select_best(latent_n, B, self.trail, valid=self.valid)
+        if self.trail is not None:
+            _lib.check(L.mgf_keep_improvements(self.trail.imgs.data_ptr(), full_img.data_ptr(), self.trail.imgs.shape[1],
+                                               self.trail.take.data_ptr(), B, st), "keep_improvements")
+
+    def _select_best(self, latent_n, n, slot, row=0, valid=None, has_p=None):
+        """The in-order best-so-far selection over the `n` candidates `latent_n` of target `row`: that target's rows of the loop state and of
+        the three loss slots (a slot that no term writes goes in as null), its `valid` table, and `slot`, the ImprovementSlot that learns
+        which candidates improved (None: nobody asks).  The one place that spells mgf_select_best's argument list."""
+        a, j = self.args, row
+        has_p = self.has_p if has_p is None else has_p
+        take, count, slots, steps, losses = (None, None, 0, None, None) if slot is None else (slot.take, slot.count, slot.slots, slot.steps, slot.losses)
+        _lib.check(_lib.lib().mgf_select_best(
+            self.min_loss[j:].data_ptr(), self.best_latent[j:].data_ptr(), self.best_step[j:].data_ptr(),
+            self.losses.reshape(self.min_loss.numel(), -1)[j].data_ptr(), latent_n.data_ptr(), self.numel,
+            _lib.ptr(self.p_loss[j:] if has_p else None), _lib.ptr(self.w_loss[j:] if (self.use_wing or self.use_lbp) else None),
+            _lib.ptr(self.mse_loss[j:] if self.use_mse else None), 1.0 if self.use_lbp else float(a.lamda), float(a.beta),
+            self.step_ctr[j:].data_ptr(), _lib.ptr(valid), n, self.steps, _lib.ptr(take), _lib.ptr(count), slots, _lib.ptr(steps), _lib.ptr(losses),
+            _lib.stream_ptr()), "select_best")
 
     def _landmarks(self, img):
         """Fill this batch's rows of the landmark / valid tables when a detector is attached (host callback or device model)."""
         B = self.batch
         if self.landmark_fn is not None and self.callback_graphs:
-            # the callbacks ran on the host between the two launch sequences (_run_callback); their rows wait in the device staging buffers
-            idx = self.step_ctr.long() + self._arange
-            self.lm_steps.index_copy_(0, idx, self.lm_stage)
-            self.valid.index_copy_(0, idx, self.ok_stage)
+            # the callbacks ran on the host between the two launch sequences (_cb_sequence); their rows wait in the device staging buffers
+            self._scatter_rows(self.lm_stage, self.ok_stage)
         elif self.landmark_fn is not None:
-            self._detect_landmarks(img)
+            s0 = int(self.step_ctr.item())                                     # host sync (the reference syncs three times per step)
+            host = img.permute(0, 2, 3, 1).contiguous().cpu().numpy()         # [B,H,W,3] float32, what the drivers build at :159-161
+            self._detect(host, s0, self.lm_steps[s0:], self.valid[s0:])
         if self.landmark_model is not None:
             lm, ok = self.landmark_model(img)
-            idx = self.step_ctr.long() + self._arange                                    # rows of this batch's steps, on the device
-            self.lm_steps.index_copy_(0, idx, lm.to(torch.float64).reshape(B, *self.lm_target.shape))
-            self.valid.index_copy_(0, idx, ok.to(torch.int32).reshape(B))
+            self._scatter_rows(lm.to(torch.float64).reshape(B, *self.lm_target.shape), ok.to(torch.int32).reshape(B))
+
+    def _scatter_rows(self, lm, ok):
+        """This batch's landmark rows and valid flags, device tensors, into the rows of its steps of the tables (a ragged last batch's surplus
+        lands on the spare rows)."""
+        idx = self.step_ctr.long() + self._arange
+        self.lm_steps.index_copy_(0, idx, lm)
+        self.valid.index_copy_(0, idx, ok)
+
+    def _detect(self, images, s0, lm_rows, ok_rows):
+        """The host detector on every candidate of the batch that starts at step s0, in step order (`images[j]`: what landmark_input names):
+        row j of lm_rows / ok_rows takes candidate j's landmarks and a 1; None = "no face", the rows stay and the step is skipped (:165-166)."""
+        for j in range(min(self.batch, self.steps - s0)):
+            lm = self.landmark_fn(images[j])
+            if lm is None:
+                continue
+            lm_rows[j].copy_(torch.as_tensor(np.asarray(lm, dtype=np.float64).reshape(self.lm_target.shape)))
+            ok_rows[j] = 1
 
     # ------------------------------------------------------------------ pipelined mode
     def _pipe_gen(self, p):
@@ -503,36 +545,14 @@ class ProjectionEngine:
         """The run's last launch sequence: losses + selection of the batch in buffers p, nothing left to synthesise beside them."""
         self._loss_phase(self.imgs[p], self.latent_ns[p])
 
-    def _pipe_capture(self):
-        tensors = self._state() + (self.gen_ctr,)
-        state = [t.clone() for t in tensors]
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            self._pipe_step(0)
-            self._pipe_step(1)
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        for p in (0, 1):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._pipe_step(p)
-            self.graphs[p] = g
-            t = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(t, pool=g.pool()):
-                self._pipe_tail(p)
-            self.tail_graphs[p] = t
-        # the first batch of a run (nothing to score beside it yet) as a graph of its own: a re-targeted engine starts every run with it
-        self.prime_graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.prime_graph, pool=self.graphs[0].pool()):
-            self._pipe_gen(0)
-        for dst, src in zip(tensors, state):
-            dst.copy_(src)
-        self._pin_workspace()
-
-    def _run_pipelined(self, n):
-        if self.use_graph and self.graphs[0] is None:
-            self._pipe_capture()                                          # (its warm-up overwrites both image buffers: capture first)
+    def _pipe_sequence(self):
+        """The pipelined mode's "launch one sequence" (run()): captures on first use, primes the pipeline, and picks steady state or tail."""
+        if self.use_graph and self.graphs[0] is None:                     # (the warm-up overwrites both image buffers: capture before priming)
+            step, tail = [partial(self._pipe_step, p) for p in (0, 1)], [partial(self._pipe_tail, p) for p in (0, 1)]
+            # a tail shares its steady-state graph's pool; the first batch of a run (nothing to score beside it yet) is a graph of its own in
+            # the pool of graphs[0]: a re-targeted engine starts every run with it
+            g = self._capture_graphs(step, [(step[0], None), (tail[0], 0), (step[1], None), (tail[1], 2), (partial(self._pipe_gen, 0), 0)])
+            self.graphs, self.tail_graphs, self.prime_graph = [g[0], g[2]], [g[1], g[3]], g[4]
         if not self._primed:
             if self.use_graph and self._parity == 0:
                 self.prime_graph.replay()                                 # the first batch has no losses to overlap with
@@ -540,17 +560,16 @@ class ProjectionEngine:
                 self._pipe_gen(self._parity)
             self._primed = True
         last = -(-self.steps // self.batch) - 1                          # index of the sequence that scores the run's last candidates
-        for _ in range(n):
-            self._before_sequence()
+
+        def launch():
             final = self._seq_launched >= last                            # (and anything a caller launches past the end: nothing left to score)
             if self.use_graph:
                 (self.tail_graphs if final else self.graphs)[self._parity].replay()
-            elif final:
-                self._pipe_tail(self._parity)
             else:
-                self._pipe_step(self._parity)
+                (self._pipe_tail if final else self._pipe_step)(self._parity)
             self._parity ^= 1
             self._seq_launched += 1
+        return launch
 
     # ------------------------------------------------------------------ callback mode on the gray uint8 image
     def _cb_phase_a(self):
@@ -565,119 +584,43 @@ class ProjectionEngine:
     def _cb_phase_b(self):
         self._loss_phase(self.G.img, self.latent_n)
 
-    def _cb_capture(self):
-        state = [t.clone() for t in self._state()]
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            self._cb_phase_a()
-            self._cb_phase_b()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(ga):
-            self._cb_phase_a()
-        with torch.cuda.graph(gb, pool=ga.pool()):
-            self._cb_phase_b()
-        for dst, src in zip(self._state(), state):
-            dst.copy_(src)
-        if self.use_wing:
-            self.lm_steps.zero_()
-            self.valid.zero_()
-        self.cb_graphs = (ga, gb)
-        self._pin_workspace()
-
-    def _run_callback(self, n):
-        """`n` launch sequences of the callback mode: phase A, one stream synchronisation, the host detector on every candidate's gray image
-        (in step order; None = "no face", the step is skipped, :165-166), ONE host->device copy of the batch's landmark rows, phase B."""
+    def _cb_sequence(self):
+        """The callback mode's "launch one sequence" (run()): phase A, one stream synchronisation, the host detector on every candidate's gray
+        image, ONE host->device copy of the batch's landmark rows, phase B."""
+        a, b = self._cb_phase_a, self._cb_phase_b
         if self.use_graph and self.cb_graphs is None:
-            self._cb_capture()
-        B, st = self.batch, torch.cuda.current_stream(self.device)
-        for _ in range(n):
-            self._before_sequence()
-            if self.cb_graphs is not None:
-                self.cb_graphs[0].replay()
-            else:
-                self._cb_phase_a()
+            self.cb_graphs = tuple(self._capture_graphs([a, b], [(a, None), (b, 0)]))
+            if self.use_wing:                       # the warm-up scattered staging rows no detector has filled
+                self.lm_steps.zero_()
+                self.valid.zero_()
+        if self.cb_graphs is not None:
+            a, b = self.cb_graphs[0].replay, self.cb_graphs[1].replay
+        st = torch.cuda.current_stream(self.device)
+
+        def launch():
+            a()
             st.synchronize()
             s0 = self._host_step
-            gray = self.gray_host.numpy()
             self.ok_stage_host.zero_()
-            for j in range(min(B, self.steps - s0)):
-                lm = self.landmark_fn(gray[j])
-                if lm is None:
-                    continue
-                self.lm_stage_host[j].copy_(torch.as_tensor(np.asarray(lm, dtype=np.float64).reshape(self.lm_target.shape)))
-                self.ok_stage_host[j] = 1
+            self._detect(self.gray_host.numpy(), s0, self.lm_stage_host, self.ok_stage_host)
             self.lm_stage.copy_(self.lm_stage_host, non_blocking=True)
             self.ok_stage.copy_(self.ok_stage_host, non_blocking=True)
-            if self.cb_graphs is not None:
-                self.cb_graphs[1].replay()
-            else:
-                self._cb_phase_b()
-            self._host_step = min(s0 + B, self.steps)
-
-    def _detect_landmarks(self, img):
-        """Host detour of the callback mode: hand every candidate image of this batch to `landmark_fn`, in step order."""
-        s0 = int(self.step_ctr.item())                                     # host sync (the reference syncs three times per step)
-        host = img.permute(0, 2, 3, 1).contiguous().cpu().numpy()         # [B,H,W,3] float32, what the drivers build at :159-161
-        for j in range(min(self.batch, self.steps - s0)):
-            lm = self.landmark_fn(host[j])
-            if lm is None:
-                continue
-            self.lm_steps[s0 + j].copy_(torch.as_tensor(np.asarray(lm, dtype=np.float64).reshape(self.lm_target.shape)))
-            self.valid[s0 + j] = 1
+            b()
+            self._host_step = min(s0 + self.batch, self.steps)
+        return launch
 
     def _state(self):
-        """Device tensors that make up the loop state (saved and restored around the capture warm-up)."""
-        st = (self.step_ctr, self.min_loss, self.best_latent, self.best_step, self.losses)
-        if self.keep_images > 0:
-            st += (self.trail_count, self.trail_steps, self.trail_losses)
-        return st
-
-    def _spill_trail(self):
-        """Move the filled trail slots to host memory and empty the device trail (between launch sequences; one host sync).  `run()`
-        calls this whenever the NEXT launch sequence could overflow the K slots -- a sequence improves at most `batch` times -- so with
-        keep_images >= batch every improvement of a run of any length keeps its scored image, like the reference's PNG per improvement
-        (...sqz_MSE.py:186-195), for K x 12.6 MB of device memory instead of one slot per step."""
-        torch.cuda.synchronize(self.device)
-        total = int(self.trail_count.item())
-        n = min(total, self.keep_images)
-        self._trail_lost += total - n
-        if n:
-            steps, losses = self.trail_steps[:n].cpu().numpy(), self.trail_losses[:n].cpu().numpy()
-            imgs = self.trail_imgs[:n].cpu()
-            c, r = self.G.cfg.img_channels, self.G.cfg.img_resolution
-            self._spilled += [(int(steps[i]), float(losses[i]), imgs[i].view(c, r, r)) for i in range(n)]
-        self.trail_count.zero_()
-        self.trail_steps.fill_(-1)
-        self._seq_since_spill = 0
-
-    def _before_sequence(self):
-        """Trail bookkeeping in front of every launch sequence (see _spill_trail)."""
-        if self.keep_images > 0:
-            if self._seq_since_spill > 0 and (self._seq_since_spill + 1) * self.batch > self.keep_images:
-                self._spill_trail()
-            self._seq_since_spill += 1
+        """Device tensors that make up the loop state (saved and restored around the capture warm-up): every registered one, see _reg."""
+        return tuple(t for t, _ in self._table)
 
     def improvements(self):
         """The improvement trail of a keep_images=K engine: list of (step, loss, image [C,H,W]) in the order the improvements
         happened -- the (step, min_loss, img_gen_raw) triples the drivers turn into PNG files (:186-195).  Images still resident in the
-        device trail are device tensors, those already spilled to the host (see _spill_trail) CPU tensors.  With keep_images >= batch
+        device trail are device tensors, those already spilled to the host (ImprovementTrail.spill) CPU tensors.  With keep_images >= batch
         the list is complete; otherwise a launch sequence with more than K improvements kept its first K-1 and its latest (a warning
         says how many images were lost)."""
-        assert self.keep_images > 0, "construct the engine with keep_images=K"
-        torch.cuda.synchronize(self.device)
-        total = int(self.trail_count.item())
-        n = min(total, self.keep_images)
-        lost = self._trail_lost + total - n
-        if lost:
-            import warnings
-            warnings.warn(f"ProjectionEngine: {lost} improvement image(s) were overwritten: keep_images={self.keep_images} < batch={self.batch} "
-                          "(the reference writes one PNG per improvement)", stacklevel=2)
-        c, r = self.G.cfg.img_channels, self.G.cfg.img_resolution
-        steps, losses = self.trail_steps.cpu().numpy(), self.trail_losses.cpu().numpy()
-        return list(self._spilled) + [(int(steps[i]), float(losses[i]), self.trail_imgs[i].view(c, r, r)) for i in range(n)]
+        assert self.trail is not None, "construct the engine with keep_images=K"
+        return self.trail.listing()
 
     def save_improvements(self, output_dir, ratio=1.0):
         """Write the trail as the drivers do: `{output_dir}/{step:06d}_{loss:04f}.png` of crop(to_pil(img), ratio) (:190-195)."""
@@ -687,52 +630,50 @@ class ProjectionEngine:
             paths.append(save_image(self.G, img.unsqueeze(0).to(self.device), os.path.join(output_dir, "{:06d}_{:04f}.png".format(step, loss)), ratio))
         return paths
 
-    def _capture(self):
-        # warm-up on a side stream (allocations, lazy init) before capture, then restore the loop state
+    def _capture_graphs(self, warmup, bodies):
+        """THE capture protocol of every launch mode.  warmup: bodies run once each, eagerly, in order, on a side stream (allocations, lazy
+        init; they advance the loop for real, and random per-layer noise is drawn in launch order: their number and order are part of a mode's
+        result).  bodies: [(body, index into this list of the graph whose memory pool it shares, or None)], captured in order.  The loop state
+        -- every registered tensor -- is saved in front and put back afterwards, and the generator's workspace is pinned.  Returns the graphs."""
         state = [t.clone() for t in self._state()]
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
+        main, s = torch.cuda.current_stream(self.device), torch.cuda.Stream(device=self.device)
+        s.wait_stream(main)
         with torch.cuda.stream(s):
-            self._iteration()
-        torch.cuda.current_stream(self.device).wait_stream(s)
+            for body in warmup:
+                body()
+        main.wait_stream(s)
         torch.cuda.synchronize(self.device)
-        # graph_debug: keep the hipGraph_t behind the executable graph, so that its nodes can be counted afterwards (bench.py)
-        keep = bool(getattr(self, "graph_debug", False))
-        g = torch.cuda.CUDAGraph(keep_graph=True) if keep else torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._iteration()
-        if keep:
-            g.instantiate()
+        keep = bool(self.graph_debug)       # keep the hipGraph_t behind the executable graph, so that its nodes can be counted afterwards
+        graphs = []
+        for body, share in bodies:
+            g = torch.cuda.CUDAGraph(keep_graph=True) if keep else torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=None if share is None else graphs[share].pool()):
+                body()
+            if keep:
+                g.instantiate()
+            graphs.append(g)
         for dst, src in zip(self._state(), state):
             dst.copy_(src)
-        self.graph = g
-        self._pin_workspace()
+        # the captured graphs reference the generator's workspace of this batch size: keep it alive as long as this engine lives
+        weakref.finalize(self, self.G.unpin, self.G.pin())
+        return graphs
 
-    def _pin_workspace(self):
-        """The captured graph references the generator's workspace of this batch size: keep it alive as long as this engine lives."""
-        import weakref
-        G = self.G
-        weakref.finalize(self, G.unpin, G.pin())
+    def _plain_sequence(self):
+        """The plain mode's "launch one sequence" (run()): the whole iteration, as one graph where graphs are on."""
+        if self.use_graph and self.graph is None:
+            (self.graph,) = self._capture_graphs([self._iteration], [(self._iteration, None)])
+        return self.graph.replay if self.graph is not None else self._iteration
 
     def run(self, steps=None):
         """Advance the loop by `steps` iterations (default: all remaining), `batch` of them per launch sequence (lockstep targets advance together)."""
         done = int(self.step_ctr[0].item()) if steps is None else None
         n = (self.steps - done) if steps is None else steps
         n = (n + self.batch - 1) // self.batch
-        if self.pipeline:
-            self._run_pipelined(n)
-            return self
-        if self.callback_graphs:
-            self._run_callback(n)
-            return self
-        if self.use_graph and self.graph is None:
-            self._capture()
+        launch = (self._pipe_sequence if self.pipeline else self._cb_sequence if self.callback_graphs else self._plain_sequence)()
         for _ in range(n):
-            self._before_sequence()
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self._iteration()
+            if self.trail is not None:
+                self.trail.before_sequence()
+            launch()
         return self
 
     def retarget(self, target, lm_target=None, lm_steps=None, lm_valid=None, eps=None, seed=None, latent_mean=None, latent_std=None,
@@ -751,21 +692,9 @@ class ProjectionEngine:
         _lib.require_gpu(target)
         assert tuple(target.shape) == tuple(self.target.shape), (tuple(target.shape), tuple(self.target.shape))
         torch.cuda.synchronize(dev)
-        if region_weight is not None:
-            self._set_region(region_weight)
-        self.target.copy_(target)
-        self.pixel.refresh_target(self.target, lbp_target)
-        if self.percept is not None:
-            self.percept.set_target(self.target)                  # same shapes: rewrites the cached taps in place
-        if face_crop is not None:
-            if self.face_crop_filter is None:
-                raise _lib.MgfError("retarget: this engine was built without a face crop; build a fresh one with face_crop=")
-            self.biometric.forget_target()        # set_target follows: one embedder pass for the new target, not two
-            self.biometric.set_crop(face_crop, face_crop_target, filter=self.face_crop_filter)
-        if self.biometric is not None:
-            self.biometric.set_target(self.target)
-        if self.mdf is not None:
-            self.mdf.set_target(self.target)
+        if face_crop is not None and self.face_crop_filter is None:
+            raise _lib.MgfError("retarget: this engine was built without a face crop; build a fresh one with face_crop=")
+        self._set_targets(target, lbp_target, region_weight, face_crop, face_crop_target)
         if self.use_wing:
             assert lm_target is not None, "this engine has a Wing term: pass the new target's landmarks"
             self.lm_target.copy_(torch.as_tensor(lm_target, dtype=torch.float64).reshape(self.lm_target.shape))
@@ -786,9 +715,7 @@ class ProjectionEngine:
             assert eps.shape[0] >= a.step
             self.eps[:a.step].copy_(eps[:a.step].reshape(a.step, *self.eps.shape[1:]))
         elif seed is not None:
-            gen = torch.Generator(device=dev)
-            gen.manual_seed(seed)
-            self.eps.copy_(torch.randn(self.eps.shape, device=dev, generator=gen))       # same draw as the constructor's
+            self.eps.copy_(seeded_randn(self.eps.shape, dev, seed))                      # same draw as the constructor's
         if latent_mean is not None:
             self.latent_in.copy_(latent_mean.detach().reshape(self.latent_in.shape))
         if latent_std is not None:
@@ -797,22 +724,17 @@ class ProjectionEngine:
         return self
 
     def rewind(self):
-        """Loop state back to step 0 (graph, workspaces and inputs untouched)."""
-        a = self.args
-        self.step_ctr.zero_()
-        self.min_loss.fill_(float(a.min_loss_init))
-        self.best_latent.zero_()
-        self.best_step.fill_(-1)
-        self.losses.fill_(float("nan"))
-        if self.keep_images > 0:
-            self.trail_count.zero_()
-            self.trail_steps.fill_(-1)
-            self.trail_losses.zero_()
-        self._spilled, self._seq_since_spill, self._trail_lost = [], 0, 0
+        """Loop state back to step 0 (graph, workspaces and inputs untouched): every registered tensor that has a reset value (_reg) takes
+        it again; the host-side counters follow.  GradientProjectionEngine: like the latent and its Adam moments, the noise maps and theirs
+        stay where the run left them; the best step's maps and the improvement flag are cleared with the best-so-far they belong to."""
+        for t, value in self._table:
+            if value is not None:
+                t.zero_() if value == 0 else t.fill_(value)
+        if self.trail is not None:
+            self.trail.forget()
         if self.callback_graphs:
             self._host_step = 0
         if self.pipeline:
-            self.gen_ctr.zero_()
             self._parity, self._primed, self._seq_launched = 0, False, 0
         return self
 
@@ -824,335 +746,6 @@ class ProjectionEngine:
         if bs < 0:
             raise IndexError("projection: no iteration improved on the initial min_loss (reference: latent_path[-1] on an empty list)")
         return self.best_latent.cpu().clone(), bs, float(self.min_loss.item()), self.losses.cpu().numpy()
-
-
-class GradientProjectionEngine(ProjectionEngine):
-    """Gradient mode: the same loop with the loss back-propagated into the latent.
-
-        latent_n = latent_in + eps_i * sigma_i;  img = G(latent_n)
-        total = percept_weight * LPIPS + lamda * Wing + beta * (MSE | DSSIM | MS-SSIM) [+ gamma * embedding MSE]     (Wing's landmarks come from a
-                                                                                                           detector: no gradient)
-        latent_in <- Adam(lr_i = get_lr(i / steps)).step(d total / d latent_in);  keep (latent_n, i) if total < min_loss
-
-    i.e. the drivers' loop (...sqz_MSE.py:143-189) with the `.cpu().detach().numpy()` at :158 removed.  One candidate per target
-    and step (the steps now depend on each other); forward, losses, backward (grad.GeneratorGrad, LPIPS / embedder backward),
-    Adam and the best-of bookkeeping are one device-resident launch sequence, replayed as a hipGraph.  The oracle is torch
-    autograd + torch.optim.Adam through the CPU restatement (oracle/loss_ref.py: projection_gradient_ref).
-
-    `target` may hold B > 1 images: B independent projections (own latent, Adam state, noise stream, landmarks, best-so-far)
-    advance in lockstep through ONE generator forward/backward per step -- the batch that lifts the 4x4..64x64 layers off
-    their batch-1 latency floor (BASELINE configs 3 and 5 are batches of independent targets).  lm_target is then [B,68,2],
-    lm_steps [B,steps,68,2], lm_valid [B,steps], eps [steps,B,k,D]; `result()` returns per-target lists.
-
-    target_b (morph refinement): every projection matches TWO identities, `target` weighted 1 - morph_alpha and target_b weighted morph_alpha
-    (merge_morph's convention; a float or one value per pair):
-        total = percept_weight [(1-a) LPIPS(x,Ta) + a LPIPS(x,Tb)] + beta [(1-a) P(x,Ta) + a P(x,Tb)] + lamda Wing
-                + gamma [(1-a) d_a + a d_b] + id_balance |d_a - d_b|,     d_t = d(embed(x), embed(T_t)), id_metric "mse" or "cosine"
-    lm_target_b blends the Wing term's target landmarks the same way; `id_trace` [B,steps,2] holds (d_a, d_b) per step.  See _init_pair."""
-    _lockstep = True
-
-    def __init__(self, G, target, latent_mean, latent_std, args: ProjectionArgs = None, percept=None, use_mse=True, lm_target=None,
-                 lm_steps=None, lm_valid=None, eps=None, noise_mode="random", seed=0, use_graph=True, landmark_fn=None, biometric=None,
-                 gamma=1.0, wing_kind="wing", landmark_model=None, betas=(0.9, 0.999), adam_eps=1e-8, weight_decay=0.0,
-                 latent_space="z", mdf=None, optimize_noise=False, noise_init="randn", target_b=None, morph_alpha=0.5, id_balance=0.0,
-                 id_metric="mse", lm_target_b=None, region_weight=None, face_crop=None, face_crop_target=None, face_crop_target_b=None,
-                 face_crop_filter="area", **ignored):
-        """latent_space: "z" -- the drivers' parameter, the gradient runs on through the mapping network -- or "w+": the parameter is the
-        per-layer intermediate latent ws [k, num_ws, D] itself (north_star: "backprops into the k-component latent W+"; layer `slot` reads
-        ws[:, slot], networks.py:1252-1253), perturbed, descended by Adam and kept best-of exactly like z.  latent_mean is then a w-space
-        start -- [k, D] (broadcast over the slots, e.g. latent_stats_w's mean) or [k, num_ws, D] -- and latent_std a w-space scale.  The
-        reference has no such driver (its "W+" averages 18 copies of z, projection_example_v2_percept.py:133-162); the oracle is torch autograd
-        + Adam on ws through the CPU restatement (tests/test_hip_gradient.py).
-
-        optimize_noise: the generator's per-layer noise inputs become parameters next to the latent, as in the StyleGAN2-style projectors the
-        drivers derive from (they still carry noise_regularize / noise_normalize_ and the --noise_regularize flag, :32-60, :243): the maps are
-        engine-owned tensors (`noise_init`: "randn", seeded, or "const", a copy of every layer's noise_const) the generator runs with
-        (`noise_mode` is then irrelevant), the total gains args.noise_regularize * sum over the maps of the regulariser, and every step the maps take
-        an Adam step with the latent's learning rate and betas followed by noise_normalize_.  `noises` holds the current maps, `best_noises`
-        those of the best step's image ({layer name: [1, res, res]}), both filled inside the launch sequence.  One target per engine.
-
-        region_weight: as ProjectionEngine's; with B lockstep targets one map for all of them or [B,1,H,W], one per target.  A target pair's
-        constants (alpha (1 - alpha) LPIPS_W(Ta, Tb) and the same of the pixel term) use the weighted values.  The noise regulariser ignores it."""
-        from .grad import GeneratorGrad
-        pair = self._pair_arguments(target, target_b, morph_alpha, id_balance, id_metric, biometric, mdf, optimize_noise, lm_target, lm_target_b)
-        if pair is not None:
-            # the pixel target of the MSE term and the Wing term's landmarks are the blends: what the single-target code below is handed
-            target, lm_target = pair["blend"], pair["lm_blend"]
-        if noise_init not in ("randn", "const"):
-            raise ValueError(f"noise_init must be 'randn' or 'const' (got {noise_init!r})")
-        if optimize_noise and int(target.shape[0]) > 1:
-            raise _lib.MgfError("GradientProjectionEngine: optimize_noise runs with one target per engine (lockstep targets share one generator "
-                                "forward, whose noise maps are shared by the batch; per-target maps are not built); project the targets one after the other")
-        if mdf is not None and not getattr(mdf, "differentiable", False):
-            raise _lib.MgfError("GradientProjectionEngine: this MDF loss was built without its backward pass -- build it with "
-                                "mdf.MDFLoss(..., differentiable=True) for gradient mode (ProjectionEngine(mdf=...), the literal loop, takes either)")
-        if mdf is not None and int(target.shape[0]) > 1:
-            raise _lib.MgfError("GradientProjectionEngine: the MDF objective runs with one target per engine (lockstep targets would need "
-                                "per-target discriminator activations); project the targets one after the other")
-        a = args or ProjectionArgs()
-        if a.latent_copies != 1:
-            raise _lib.MgfError("GradientProjectionEngine: latent_copies is the literal-mode v2 driver's averaged latent (projection_example_v2_percept.py); "
-                                "gradient mode optimises one latent")
-        if a.pixel_term not in ("mse", "dssim", "msssim") or a.pool_above:
-            raise _lib.MgfError("GradientProjectionEngine: pixel_term='psnr', pixel_term='lbp' and pool_above are literal-mode objectives with no backward pass "
-                                "here: PSNR as the script minimises it descends towards a LARGER error, the LBP distance is a histogram of integer codes "
-                                "(its gradient is zero almost everywhere), and pool_above is the v1 driver's block mean in front of the losses, which has "
-                                "no adjoint kernel; gradient mode descends Wing / LPIPS / MSE / DSSIM / MS-SSIM / biometric / MDF")
-        assert latent_space in ("z", "w+"), latent_space
-        self.latent_space = latent_space
-        ls = (G.cfg.k, G.cfg.num_ws, G.cfg.w_dim) if latent_space == "w+" else (G.cfg.k, G.cfg.z_dim)
-        B = int(target.shape[0])
-        assert B == 1 or (landmark_fn is None and landmark_model is None), "landmark detectors are wired for one target per engine"
-        # one candidate per target and step, nothing pipelined, no improvement trail; B > 1 targets get a row each of the loop state (_init_state)
-        super().__init__(G, target, latent_mean, latent_std, args, percept=percept, use_mse=use_mse, lm_target=lm_target,
-                         lm_steps=lm_steps, lm_valid=lm_valid, eps=eps, noise_mode=noise_mode, seed=seed, use_graph=use_graph, batch=1,
-                         landmark_fn=landmark_fn, biometric=biometric, gamma=gamma, wing_kind=wing_kind,
-                         landmark_model=landmark_model, pipeline=False, keep_images=0, latent_shape=ls, mdf=mdf, region_weight=region_weight,
-                         face_crop=face_crop, face_crop_target=face_crop_target, face_crop_target_b=face_crop_target_b,
-                         face_crop_filter=face_crop_filter)
-        self.targets = B
-        a, dev = self.args, self.device
-        if biometric is not None:
-            biometric.embedder.keep_activations = True          # FaceEmbedder's contract (the FaceNet embedder re-uses its buffers block after block otherwise)
-        self.gg = GeneratorGrad(G)
-        self.betas, self.adam_eps, self.weight_decay = betas, float(adam_eps), float(weight_decay)
-        self.lr_table = torch.as_tensor(np.array([get_lr(i / a.step, a.lr, a.lr_rampdown, a.lr_rampup) for i in range(a.step)],
-                                                 dtype=np.float32), device=dev)
-        self.exp_avg = torch.zeros_like(self.latent_in)
-        self.exp_avg_sq = torch.zeros_like(self.latent_in)
-        self.adam_t = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.dimg = torch.zeros_like(self.target)
-        self.optimize_noise = bool(optimize_noise)
-        self.noises = self.best_noises = None
-        if self.optimize_noise:
-            self._init_noise(noise_init, seed)
-        self.pair, self.id_trace = pair, None
-        if pair is not None:
-            self._init_pair(float(id_balance), id_metric)
-
-    @staticmethod
-    def _pair_arguments(target, target_b, morph_alpha, id_balance, id_metric, biometric, mdf, optimize_noise, lm_target, lm_target_b):
-        """Checks of the two-identity objective, and its blended single-target inputs.  None without target_b."""
-        if target_b is None:
-            if lm_target_b is not None or float(id_balance) != 0.0:
-                raise ValueError("GradientProjectionEngine: lm_target_b and id_balance belong to a target pair: pass target_b")
-            return None
-        if mdf is not None:
-            raise _lib.MgfError("GradientProjectionEngine: target_b (morph refinement) does not combine with mdf=: the MDF loss is not a sum of "
-                                "quadratic terms against stored target activations, so it would need a second evaluation per step, which is not built")
-        if optimize_noise:
-            raise _lib.MgfError("GradientProjectionEngine: target_b (morph refinement) does not combine with optimize_noise=True (noise maps fitted "
-                                "to two images at once are not built)")
-        if float(id_balance) != 0.0 and biometric is None:
-            raise ValueError("GradientProjectionEngine: id_balance weighs |d_a - d_b| of the biometric term: pass biometric= with it")
-        if float(id_balance) < 0.0:
-            raise ValueError(f"GradientProjectionEngine: id_balance must be >= 0 (got {id_balance})")
-        if id_metric not in ("mse", "cosine"):
-            raise ValueError(f"GradientProjectionEngine: id_metric must be 'mse' or 'cosine' (got {id_metric!r})")
-        _lib.require_gpu(target, target_b)
-        if tuple(target_b.shape) != tuple(target.shape):
-            raise ValueError(f"GradientProjectionEngine: target and target_b do not pair up: {tuple(target.shape)} vs {tuple(target_b.shape)}")
-        B = int(target.shape[0])
-        al = np.asarray(morph_alpha.detach().cpu() if isinstance(morph_alpha, torch.Tensor) else morph_alpha, dtype=np.float64).reshape(-1)
-        if al.size not in (1, B):
-            raise ValueError(f"GradientProjectionEngine: morph_alpha must be one value or one per pair ({B}), got {al.size}")
-        if not np.all((al >= 0.0) & (al <= 1.0)):
-            raise ValueError(f"GradientProjectionEngine: morph_alpha must lie in [0, 1] (got {al.tolist()}): the objective's reduction to one "
-                             "blended target holds for convex weights only")
-        al = np.array(np.broadcast_to(al, (B,)))
-        ta = target.detach().float().clone(memory_format=torch.contiguous_format)
-        tb = target_b.detach().float().clone(memory_format=torch.contiguous_format)
-        blend = torch.empty_like(ta)
-        for j in range(B):                  # alpha exactly 0 or 1: that target's own bits (the end points equal the single-target engine)
-            a = float(al[j])
-            blend[j] = ta[j] if a == 0.0 else (tb[j] if a == 1.0 else ta[j] * (1.0 - a) + tb[j] * a)
-        lm_blend = lm_target
-        if lm_target_b is not None:
-            if lm_target is None:
-                raise ValueError("GradientProjectionEngine: lm_target_b needs lm_target (the first identity's landmarks)")
-            la, lb = np.asarray(lm_target, dtype=np.float64), np.asarray(lm_target_b, dtype=np.float64)
-            if la.shape != lb.shape:
-                raise ValueError(f"GradientProjectionEngine: lm_target and lm_target_b do not pair up: {la.shape} vs {lb.shape}")
-            w = al.reshape((B,) + (1,) * (la.ndim - 1)) if (B > 1 or la.ndim == 3) else float(al[0])
-            lm_blend = (1.0 - w) * la + w * lb
-        return dict(ta=ta, tb=tb, alpha=al, blend=blend, lm_blend=lm_blend)
-
-    def _init_pair(self, id_balance, id_metric):
-        """Two identities per projection (morph refinement).  Every quadratic term against (Ta weighted 1 - alpha, Tb weighted alpha) equals
-        the same term against one blended target plus a constant, so LPIPS, MSE and their backward run once per step on blends -- the cached
-        unit taps (PerceptualLoss.set_target_pair) and the pixel blend `self.target` -- and the constants are added on the device; DSSIM and
-        MS-SSIM are evaluated against both targets (PixelTerm.set_pair); the identity term (balance |d_a - d_b|, cosine metric) is
-        mgf_embed_pair_loss_f32."""
-        P, a, dev, B = self.pair, self.args, self.device, self.targets
-        al = P["alpha"]
-        self.pair_alpha = torch.as_tensor(al, dtype=torch.float32, device=dev)
-        if self.percept is not None:
-            self.percept.set_target_pair(P["ta"], P["tb"], al)
-            self.pair_p_off = self.percept.pair_offset * float(a.percept_weight)          # percept_weight * alpha (1 - alpha) LPIPS(Ta, Tb)
-        self.pixel.set_pair(P["ta"], P["tb"], al)
-        if self.biometric is not None:
-            self.biometric.set_target_pair(P["ta"], P["tb"], al, id_balance=id_balance, metric=id_metric)
-            self.id_trace = torch.full([B, self.steps, 2], float("nan"), dtype=torch.float64, device=dev)
-            self.biometric.pair_trace = (self.id_trace, self.step_ctr)
-
-    def retarget(self, *args, **kw):
-        if getattr(self, "pair", None) is not None:
-            raise _lib.MgfError("GradientProjectionEngine: an engine built on a target pair is not re-targeted; build a fresh one")
-        if self.targets > 1:
-            raise _lib.MgfError("GradientProjectionEngine: an engine of lockstep targets is not re-targeted; build a fresh one")
-        return super().retarget(*args, **kw)
-
-    def _init_noise(self, noise_init, seed):
-        """The noise maps as parameters: ONE flat buffer each for the maps, their gradient, the two Adam moments and the best step's maps
-        (Adam is elementwise: one launch moves all of them), per-layer views for the generator, the backward pass and the per-map kernels."""
-        G, dev, L = self.G, self.device, _lib.lib()
-        layers = [lp for lp in G.plan.layers if lp.noise_strength is not None]
-        total = sum(lp.res * lp.res for lp in layers)
-        z = lambda: torch.zeros(total, dtype=torch.float32, device=dev)
-        self.noise_flat, self.noise_grad, self.noise_m, self.noise_v, self.best_noise_flat = z(), z(), z(), z(), z()
-        if noise_init == "randn":
-            gen = torch.Generator(device=dev)
-            gen.manual_seed(int(seed) + 0x6E6F6973)                # (a stream of its own, not the head of the latent's eps stream)
-            self.noise_flat.copy_(torch.randn(total, device=dev, generator=gen))
-        self.noises, self.best_noises, self.dnoises, self.noise_layers = {}, {}, {}, []
-        off = 0
-        for lp in layers:
-            r = lp.res
-            if noise_init == "const":
-                self.noise_flat[off:off + r * r].copy_(lp.noise_const.reshape(-1))
-            self.noises[lp.name] = self.noise_flat[off:off + r * r].view(1, r, r)
-            self.best_noises[lp.name] = self.best_noise_flat[off:off + r * r].view(1, r, r)
-            self.dnoises[lp.name] = self.noise_grad[off:off + r * r].view(1, r, r)
-            self.noise_layers.append((lp.name, r))
-            off += r * r
-        self.noise_adam_t = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.noise_ctr = torch.zeros(1, dtype=torch.int32, device=dev)      # the step counter as it stood before select_best advanced it
-        # the improvement flag of select_best, through its one-slot trail: take_slot[0] = 0 where this step improved, else -1
-        self.noise_take = torch.full([1], -1, dtype=torch.int32, device=dev)
-        self.noise_trail_count = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.noise_trail_step = torch.full([1], -1, dtype=torch.int32, device=dev)
-        self.noise_trail_loss = torch.zeros(1, dtype=torch.float64, device=dev)
-        nbytes = max(int(L.mgf_noise_regularize_scratch_bytes(r)) for _, r in self.noise_layers)
-        self.noise_reg_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        self.noise_norm_scratch = torch.empty(int(L.mgf_noise_normalize_scratch_bytes()) // 8, dtype=torch.float64, device=dev)
-        self.gg.noise_grads = True
-
-    def _noise_update(self):
-        """After select_best: keep the maps of an improving step (they still are the ones its image was generated with), then move them --
-        Adam on d total / d maps = the generator's d<img, dimg>/d maps (already in noise_grad) + noise_regularize * d reg / d maps, then
-        noise_normalize_ per map; a skipped step moves nothing (every kernel reads the step counter and the `valid` table itself)."""
-        L, st, a = _lib.lib(), _lib.stream_ptr(), self.args
-        _lib.check(L.mgf_keep_improvements(self.best_noise_flat.data_ptr(), self.noise_flat.data_ptr(), self.noise_flat.numel(),
-                                           self.noise_take.data_ptr(), 1, st), "keep_improvements(noise maps)")
-        _lib.check(L.mgf_adam_elementwise_f32(self.noise_flat.data_ptr(), self.noise_m.data_ptr(), self.noise_v.data_ptr(),
-                                              self.noise_adam_t.data_ptr(), self.noise_grad.data_ptr(), self.lr_table.data_ptr(),
-                                              self.noise_ctr.data_ptr(), _lib.ptr(self.valid), self.noise_flat.numel(), self.steps,
-                                              float(self.betas[0]), float(self.betas[1]), self.adam_eps, self.weight_decay, st), "adam_elementwise")
-        for name, r in self.noise_layers:
-            _lib.check(L.mgf_noise_normalize_f32(self.noises[name].data_ptr(), r * r, self.noise_ctr.data_ptr(), _lib.ptr(self.valid), self.steps,
-                                                 self.noise_norm_scratch.data_ptr(), st), "noise_normalize")
-
-    def _noise_regularize(self, has_p):
-        """p_loss (+)= noise_regularize * sum_maps reg and noise_grad += noise_regularize * d reg / d maps, map after map on one stream (the
-        regulariser rides in the float32 p_loss slot like the biometric and MDF terms; select_best forms the total in float64)."""
-        L, st, a = _lib.lib(), _lib.stream_ptr(), self.args
-        for i, (name, r) in enumerate(self.noise_layers):
-            _lib.check(L.mgf_noise_regularize_grad_f32(self.dnoises[name].data_ptr(), self.p_loss.data_ptr(), self.noises[name].data_ptr(), r,
-                                                       float(a.noise_regularize), 1, int(has_p or i > 0), self.noise_reg_scratch.data_ptr(), st),
-                       "noise_regularize_grad")
-
-    def _state(self):
-        st = super()._state() + (self.latent_in, self.exp_avg, self.exp_avg_sq, self.adam_t)
-        if getattr(self, "id_trace", None) is not None:
-            st += (self.id_trace,)
-        if self.optimize_noise:
-            st += (self.noise_flat, self.noise_m, self.noise_v, self.noise_adam_t, self.best_noise_flat, self.noise_take, self.noise_trail_count,
-                   self.noise_trail_step, self.noise_trail_loss)
-        return st
-
-    def _iteration(self):
-        L, st, a, B = _lib.lib(), _lib.stream_ptr(), self.args, self.targets
-        # B targets: one flat parameter of B * numel floats, one noise row [B * numel] per step
-        _lib.check(L.mgf_latent_perturb(self.latent_n.data_ptr(), self.latent_in.data_ptr(), self.eps.data_ptr(), self.sigma.data_ptr(),
-                                        self.step_ctr.data_ptr(), 1, self.steps, B * self.numel, st), "latent_perturb")
-        opt_noise = self.optimize_noise
-        nkw = dict(noise_mode="inject", noises=self.noises) if opt_noise else dict(noise_mode=self.noise_mode)
-        if self.latent_space == "w+":
-            img = self.gg.forward(ws=self.latent_n, **nkw)                        # [B, k, num_ws, D]: every layer reads its own slot
-        else:
-            img = self.gg.forward(self.latent_n, **nkw)                           # psi lands in `c` in the drivers: no truncation
-        if B == 1:
-            self._landmarks(img)                                                  # before Adam: a "no face" step must not move the latent
-        tstride = img.numel() // B if B > 1 else 0
-        pair = self.pair
-        # dimg = beta * d pixel term / d img (zero without one); the window terms write their value with it, the MSE value follows below
-        self.pixel.grad_into(self.dimg, self.mse_loss, img, self.target, B, tstride, float(a.beta), 0)
-        if self.percept is not None:
-            self.percept.distance_into(self.p_loss, img, keep_taps=True)
-            self.percept.grad_into(self.dimg, scale=float(a.percept_weight), accumulate=True)
-            if a.percept_weight != 1.0:
-                self.p_loss.mul_(float(a.percept_weight))
-            if pair is not None:            # the constant the blended taps leave out: `losses` holds the pair objective, not a shifted one
-                self.p_loss.add_(self.pair_p_off)
-        if self.biometric is not None:      # rides in the p_loss slot, like the literal loop (a target pair: one launch of the pair kernel)
-            self.biometric.distance_into(self.p_loss, img, scale=self.gamma, accumulate=self.bio_accumulate)
-            self.biometric.grad_into(self.dimg, scale=self.gamma, accumulate=True)
-        if self.mdf is not None:            # p_loss (+)= MDF, dimg += d MDF / d img (1024_example_mdfloss.py:165 without the detach)
-            self.mdf.distance_into(self.p_loss, img, accumulate=self.mdf_accumulate, dimg=self.dimg, grad_accumulate=True)
-        self.pixel.value_after_grad_into(self.mse_loss, img, self.target, B, tstride)
-        if opt_noise:
-            dz = self.gg.backward_ws(self.dimg, dnoises=self.dnoises) if self.latent_space == "w+" else self.gg.backward(self.dimg, dnoises=self.dnoises)
-        else:
-            dz = self.gg.backward_ws(self.dimg) if self.latent_space == "w+" else self.gg.backward(self.dimg)
-        has_p = self.has_p or opt_noise
-        if opt_noise:
-            self._noise_regularize(self.has_p)
-            self.noise_ctr.copy_(self.step_ctr)
-        for j in range(B):                   # per-target optimizer step, Wing term and best-of bookkeeping (tiny launches)
-            ctr = self.step_ctr[j:]
-            valid = None if self.valid is None else (self.valid[j] if B > 1 else self.valid)
-            _lib.check(L.mgf_adam_step_f32(self.latent_in[j:].data_ptr(), self.exp_avg[j:].data_ptr(), self.exp_avg_sq[j:].data_ptr(),
-                                           self.adam_t[j:].data_ptr(), dz[j:].data_ptr(), self.lr_table.data_ptr(), ctr.data_ptr(),
-                                           _lib.ptr(valid), self.numel, self.steps, float(self.betas[0]), float(self.betas[1]),
-                                           self.adam_eps, self.weight_decay, st), "adam_step")
-            if self.use_wing:
-                _wing_into(self.wing_kind, self.w_loss[j:], self.lm_tables[j], self.lm_target[j] if B > 1 else self.lm_target, 1, ctr)
-            _lib.check(L.mgf_select_best(self.min_loss[j:].data_ptr(), self.best_latent[j:].data_ptr(), self.best_step[j:].data_ptr(),
-                                         self.losses.reshape(B, -1)[j].data_ptr(), self.latent_n[j:].data_ptr(), self.numel,
-                                         _lib.ptr(self.p_loss[j:] if has_p else None), _lib.ptr(self.w_loss[j:] if self.use_wing else None),
-                                         _lib.ptr(self.mse_loss[j:] if self.use_mse else None), float(a.lamda), float(a.beta),
-                                         ctr.data_ptr(), _lib.ptr(valid), 1, self.steps, _lib.ptr(self.noise_take if opt_noise else None),
-                                         _lib.ptr(self.noise_trail_count if opt_noise else None), int(opt_noise),
-                                         _lib.ptr(self.noise_trail_step if opt_noise else None),
-                                         _lib.ptr(self.noise_trail_loss if opt_noise else None), st), "select_best")
-        if opt_noise:
-            self._noise_update()
-        return img
-
-    def rewind(self):
-        """Loop state back to step 0.  Like the latent and its Adam moments, the noise maps and theirs stay where the run left them; the
-        best step's maps and the improvement flag's trail are cleared with the best-so-far they belong to."""
-        super().rewind()
-        if getattr(self, "id_trace", None) is not None:
-            self.id_trace.fill_(float("nan"))
-        if self.optimize_noise:
-            self.best_noise_flat.zero_()
-            self.noise_take.fill_(-1)
-            self.noise_trail_count.zero_()
-            self.noise_trail_step.fill_(-1)
-            self.noise_trail_loss.zero_()
-        return self
-
-    def result(self):
-        """One target: like ProjectionEngine.result().  B targets: (best_latents [B,k,D] cpu, best_steps [B], best_losses [B],
-        losses [B,steps]) as numpy / tensors; a target that never improved on min_loss_init raises like the reference."""
-        if self.targets == 1:
-            return super().result()
-        torch.cuda.synchronize(self.device)
-        bs = self.best_step.cpu().numpy()
-        if (bs < 0).any():
-            raise IndexError(f"projection: targets {np.nonzero(bs < 0)[0].tolist()} never improved on the initial min_loss")
-        return self.best_latent.cpu().clone(), bs, self.min_loss.cpu().numpy(), self.losses.cpu().numpy()
 
 
 def save_best_png(G, latent, path, ratio=1.0, noise_mode="const", noises=None):
@@ -1178,3 +771,11 @@ def synthetic_landmarks(steps, res, seed):
     target = rng.integers(res // 4, 3 * res // 4, size=(68, 2)).astype(np.float64)
     per_step = target[None] + rng.integers(-max(res // 64, 1), max(res // 64, 1) + 1, size=(steps, 68, 2)).astype(np.float64)
     return target, per_step
+
+
+def __getattr__(name):
+    """`GradientProjectionEngine` lives in gradient_projection.py, which imports this module: importable from here as before, on first use."""
+    if name == "GradientProjectionEngine":
+        from .gradient_projection import GradientProjectionEngine
+        return GradientProjectionEngine
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -836,3 +836,31 @@ def test_lockstep_targets_with_the_biometric_term(tiny):
     got = multi.losses.cpu().numpy()
     for j in range(B):
         assert np.abs(got[j, :2] - firsts[j]).max() < 1e-3 * np.abs(firsts[j]).max()
+
+
+@pytest.mark.parametrize("mode", ["plain", "optimize_noise"])
+def test_graph_capture_saves_and_restores_the_whole_loop_state(tiny, mode):
+    """The capture's warm-up pass moves the latent, the Adam moments and (optimize_noise) the noise maps for real, and the state is put back
+    afterwards: an engine that captures and replays ends on exactly the state of an engine that never captures -- every tensor of _state().
+    10 steps in two run() calls, LPIPS + Wing + MSE."""
+    from morphganformer_amd.lpips import PerceptualLoss
+    from morphganformer_amd.projection import GradientProjectionEngine, ProjectionArgs, synthetic_landmarks
+    from morphganformer_amd.synth_weights import synthetic_latents
+    gg, tsd, cfg = tiny
+    G = gg.G
+    steps = 10
+    z = torch.from_numpy(synthetic_latents(cfg, 2, seed=11)).cuda()
+    target = G(z[:1], None, noise_mode="const")[0].clamp(-1, 1).clone()
+    lm_t, lm_s = synthetic_landmarks(steps, cfg.img_resolution, 40)
+    state = []
+    for use_graph in (True, False):
+        eng = GradientProjectionEngine(G, target, z[1], 1.0, ProjectionArgs(step=steps, lr=0.05, lr_rampup=0.2, noise_regularize=1.0),
+                                       percept=PerceptualLoss(net="squeeze", allow_random_backbone=True), lm_target=lm_t, lm_steps=lm_s,
+                                       noise_mode="const", seed=9, use_graph=use_graph, optimize_noise=mode == "optimize_noise", noise_init="const")
+        eng.run(4).run()
+        torch.cuda.synchronize()
+        state.append([t.clone() for t in eng._state()])
+        assert int(eng.step_ctr.item()) == steps and int(eng.best_step.item()) >= 0
+    assert len(state[0]) == len(state[1]) >= 9
+    for i, (a, b) in enumerate(zip(*state)):
+        assert torch.equal(a, b), i

@@ -493,7 +493,7 @@ def test_wplus_with_noise_optimisation_runs_and_moves_the_maps(tiny):
         assert not torch.equal(v, start[k]) and abs(float(v.double().mean())) < 1e-6 and abs(float(v.double().std()) - 1) < 1e-6, k
     assert any(bool(v.abs().max() > 0) for v in eng.best_noises.values())
     eng.rewind()
-    assert int(eng.step_ctr.item()) == 0 and int(eng.noise_trail_count.item()) == 0 and all(not bool(v.any()) for v in eng.best_noises.values())
+    assert int(eng.step_ctr.item()) == 0 and int(eng.noise_slot.count.item()) == 0 and all(not bool(v.any()) for v in eng.best_noises.values())
 
 
 # ---------------------------------------------------------------------------------------------- refusals, defaults, CLI

@@ -884,3 +884,37 @@ def test_config3_full_size_properties():
     img = G((eng.latent_in + eng.eps[bstep] * eng.sigma[bstep]), None, noise_mode="const")[0]
     want = gamma * float(eng.biometric(img[:1], target))
     assert abs(extra[bstep] - want) < 1e-3 * want + 1e-6 * abs(hist[0][bstep]), (extra[bstep], want)
+
+
+@pytest.mark.parametrize("mode", ["plain", "pipelined", "gray_u8", "trail"])
+def test_graph_capture_saves_and_restores_the_whole_loop_state(mode):
+    """The capture's warm-up passes run the loop for real and the state is put back afterwards: an engine that captures and replays ends
+    on exactly the state of an engine that never captures -- every tensor of _state(), and the generator side's step counter where there is
+    one.  10 steps at batch 4 (a ragged last batch) in two run() calls, LPIPS + Wing + MSE."""
+    from morphganformer_amd.lpips import PerceptualLoss
+    from morphganformer_amd.projection import ProjectionArgs, ProjectionEngine, synthetic_landmarks
+    from morphganformer_amd.synth_weights import TINY, synthetic_latents
+    G = _tiny_gen()
+    steps, batch = 10, 4
+    z = torch.from_numpy(synthetic_latents(TINY, 2, seed=11)).cuda()
+    target = G(z[:1], None, noise_mode="const")[0].clamp(-1, 1).clone()
+    lm_t, lm_s = synthetic_landmarks(steps, TINY.img_resolution, 40)
+    kw = dict(lm_target=lm_t, noise_mode="const", seed=9, batch=batch)
+    if mode == "gray_u8":       # a detector that reads its input: landmarks shifted by the gray image's mean, "no face" on every fifth value of it
+        def detect(gray):
+            m = int(gray.astype(np.int64).sum())
+            return None if m % 5 == 0 else lm_t + (m % 7)
+        kw.update(landmark_fn=detect, landmark_input="gray_u8")
+    else:
+        kw.update(lm_steps=lm_s, pipeline=mode == "pipelined", keep_images=batch if mode == "trail" else 0)
+    state = []
+    for use_graph in (True, False):
+        eng = ProjectionEngine(G, target, z[1], 1.0, ProjectionArgs(step=steps), percept=PerceptualLoss(net="squeeze", allow_random_backbone=True),
+                               use_graph=use_graph, **kw)
+        eng.run(4).run()
+        torch.cuda.synchronize()
+        state.append([t.clone() for t in eng._state()] + ([eng.gen_ctr.clone()] if mode == "pipelined" else []))
+        assert int(eng.step_ctr.item()) == steps and int(eng.best_step.item()) >= 0
+    assert len(state[0]) == len(state[1]) >= 5
+    for i, (a, b) in enumerate(zip(*state)):
+        assert torch.equal(a.view(torch.uint8), b.view(torch.uint8)), i        # (bytes: a skipped step's loss stays the NaN it was filled with)
