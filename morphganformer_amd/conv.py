@@ -107,6 +107,11 @@ def _workspace(dev_index):
     return ws
 
 
+def _scale_stride(out_scale):
+    """Sample stride (floats) of an output scale: a [n, cout] table has one row per sample, a [cout] vector (or none) serves them all."""
+    return out_scale.stride(0) if out_scale is not None and out_scale.ndim == 2 else 0
+
+
 def conv_forward(x, pc: PackedConv, stride=1, pad=(0, 0), in_scale=None, out_scale=None, epilogue=None, out=None,
                  out_choff=0, rgb=None, taps=None, ksize=None, bf=None):
     """Correlation with the packed taps: y[oy,ox] = sum w[kh,kw] x[oy*stride + kh - pad_y, ox*stride + kw - pad_x].
@@ -132,7 +137,7 @@ def conv_forward(x, pc: PackedConv, stride=1, pad=(0, 0), in_scale=None, out_sca
         _lib.require_gpu(rgb_w, rgb_b, rgb_out)
         assert rgb_w.is_contiguous() and rgb_out.is_contiguous() and tuple(rgb_out.shape) == (n, rgb_w.shape[1], oh, ow)
         d = _desc(n, cin, h, w, pc.cout, pc.cout_pad, oh, ow, stride, 1, taps, None, [0], [0], oh, ow, ow, oh * ow,
-                  pc.cout * oh * ow, 0, 0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0)
+                  pc.cout * oh * ow, 0, _scale_stride(out_scale))
         d.rgb_w, d.rgb_bias, d.rgb_out, d.rgb_channels = rgb_w.data_ptr(), _lib.ptr(rgb_b), rgb_out.data_ptr(), rgb_w.shape[1]
         rc = launch(None, x.data_ptr(), wptr, _lib.ptr(in_scale), _lib.ptr(out_scale),
                     C.byref(d), C.byref(epilogue) if epilogue is not None else None, _lib.stream_ptr())
@@ -152,7 +157,7 @@ def conv_forward(x, pc: PackedConv, stride=1, pad=(0, 0), in_scale=None, out_sca
         return out
     d = _desc(n, cin, h, w, pc.cout, pc.cout_pad, oh, ow, stride, 1, taps, None, [0], [0], oh, ow,
               ow, oh * ow, out.shape[1] * oh * ow, out_choff,
-              0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0)
+              _scale_stride(out_scale))
     rc = launch(out.data_ptr(), x.data_ptr(), wptr, _lib.ptr(in_scale), _lib.ptr(out_scale),
                 C.byref(d), C.byref(epilogue) if epilogue is not None else None, _lib.stream_ptr())
     _lib.check(rc, "conv_taps")
@@ -205,48 +210,31 @@ def winograd3_ok(x, out, out_choff):
 
 
 def winograd2_forward(x, u, in_scale=None, out_scale=None, epilogue=None, out=None, out_choff=0, residual_low=None):
-    """3x3 / stride 1 / pad 1 correlation on weights in the [16, cin/4, cout, 4] layout.  Form 3 serves dense outputs on even maps;
-    form 2 (and only it) may write channels [out_choff, out_choff + cout) of a wider `out` and takes odd map sides.
+    """3x3 / stride 1 / pad 1 correlation on weights in the [16, cin/4, cout, 4] layout, into channels [out_choff, out_choff + cout) of
+    `out`: form 3 (winograd3_ok), or form 2 where it is pinned.
     residual_low [n, cout, h/2, w/2] (form 3 only): the epilogue adds upsample2d(residual_low, [1,3,3,1], up=2) -- the resnet skip branch
     without its full-resolution tensor (mgf_conv3x3_winograd3_up2res_f32)."""
     _lib.require_gpu(x, u, in_scale, out_scale, out, residual_low)
-    if residual_low is not None:
-        n, cin, h, w = x.shape
-        cout = u.shape[2]
-        assert winograd3_ok(x, out, out_choff) and epilogue is not None, "residual_low needs the form-3 kernel and an epilogue"
-        assert residual_low.is_contiguous() and tuple(residual_low.shape) == (n, cout, h // 2, w // 2) and residual_low.dtype == torch.float32
-        if out is None:
-            out = torch.empty([n, cout, h, w], dtype=torch.float32, device=x.device)
-        assert out.is_contiguous() and tuple(out.shape) == (n, cout, h, w)
-        os_stride = 0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0
-        _lib.check(_lib.lib().mgf_conv3x3_winograd3_up2res_f32(out.data_ptr(), x.data_ptr(), u.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale),
-                                                               residual_low.data_ptr(), n, cin, h, w, cout, os_stride, C.byref(epilogue),
-                                                               _lib.stream_ptr()), "conv3x3_winograd3_up2res")
-        return out
-    if winograd3_ok(x, out, out_choff):
-        assert x.dtype == torch.float32 and x.is_contiguous() and x.ndim == 4 and u.ndim == 4 and x.shape[1] == u.shape[1] * 4
-        n, cin, h, w = x.shape
-        cout = u.shape[2]
-        if out is None:
-            out = torch.empty([n, cout, h, w], dtype=torch.float32, device=x.device)
-        assert out.is_contiguous() and out.shape[0] == n and tuple(out.shape[2:]) == (h, w) and out_choff + cout <= out.shape[1]
-        os_stride = 0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0
-        rc = _lib.lib().mgf_conv3x3_winograd3_slice_f32(out.data_ptr(), x.data_ptr(), u.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale), n, cin, h,
-                                                        w, cout, os_stride, out.shape[1] * h * w, out_choff,
-                                                        C.byref(epilogue) if epilogue is not None else None, _lib.stream_ptr())
-        _lib.check(rc, "conv3x3_winograd3")
-        return out
     assert x.dtype == torch.float32 and x.is_contiguous() and x.ndim == 4 and u.ndim == 4 and x.shape[1] == u.shape[1] * 4
     n, cin, h, w = x.shape
     cout = u.shape[2]
     if out is None:
         out = torch.empty([n, cout, h, w], dtype=torch.float32, device=x.device)
     assert out.is_contiguous() and out.shape[0] == n and tuple(out.shape[2:]) == (h, w) and out_choff + cout <= out.shape[1]
-    os_stride = 0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0
-    rc = _lib.lib().mgf_conv3x3_winograd2_slice_f32(out.data_ptr(), x.data_ptr(), u.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale), n, cin, h,
-                                                    w, cout, os_stride, out.shape[1] * h * w, out_choff,
-                                                    C.byref(epilogue) if epilogue is not None else None, _lib.stream_ptr())
-    _lib.check(rc, "conv3x3_winograd2")
+    form3 = winograd3_ok(x, out, out_choff)
+    ep = C.byref(epilogue) if epilogue is not None else None
+    if residual_low is not None:
+        assert form3 and epilogue is not None, "residual_low needs the form-3 kernel and an epilogue"
+        assert residual_low.is_contiguous() and tuple(residual_low.shape) == (n, cout, h // 2, w // 2) and residual_low.dtype == torch.float32
+        assert out.shape[1] == cout
+        _lib.check(_lib.lib().mgf_conv3x3_winograd3_up2res_f32(out.data_ptr(), x.data_ptr(), u.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale),
+                                                               residual_low.data_ptr(), n, cin, h, w, cout, _scale_stride(out_scale), ep,
+                                                               _lib.stream_ptr()), "conv3x3_winograd3_up2res")
+        return out
+    launch, what = ((_lib.lib().mgf_conv3x3_winograd3_slice_f32, "conv3x3_winograd3") if form3 else
+                    (_lib.lib().mgf_conv3x3_winograd2_slice_f32, "conv3x3_winograd2"))
+    _lib.check(launch(out.data_ptr(), x.data_ptr(), u.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale), n, cin, h, w, cout,
+                      _scale_stride(out_scale), out.shape[1] * h * w, out_choff, ep, _lib.stream_ptr()), what)
     return out
 
 
@@ -257,15 +245,10 @@ def winograd2_rgb_forward(x, u, rgb_w, rgb_bias, rgb_out, in_scale=None, out_sca
     cout = u.shape[2]
     assert x.is_contiguous() and u.ndim == 4 and u.shape[3] == 4 and rgb_w.is_contiguous() and rgb_out.is_contiguous()
     assert tuple(rgb_out.shape) == (n, rgb_w.shape[1], h, w) and rgb_w.shape[2] == cout
-    os_stride = 0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0
-    if WINOGRAD_FORM == 3 and h % 2 == 0 and w % 2 == 0 and rgb_w.shape[1] <= 3:
-        _lib.check(_lib.lib().mgf_conv3x3_winograd3_rgb_f32(rgb_out.data_ptr(), x.data_ptr(), u.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale),
-                                                            rgb_w.data_ptr(), _lib.ptr(rgb_bias), n, cin, h, w, cout, os_stride, rgb_w.shape[1],
-                                                            _lib.stream_ptr()), "conv3x3_winograd3_rgb")
-        return rgb_out
-    _lib.check(_lib.lib().mgf_conv3x3_winograd2_rgb_f32(rgb_out.data_ptr(), x.data_ptr(), u.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale),
-                                                        rgb_w.data_ptr(), _lib.ptr(rgb_bias), n, cin, h, w, cout, os_stride, rgb_w.shape[1],
-                                                        _lib.stream_ptr()), "conv3x3_winograd2_rgb")
+    form3 = WINOGRAD_FORM == 3 and h % 2 == 0 and w % 2 == 0 and rgb_w.shape[1] <= 3
+    launch = _lib.lib().mgf_conv3x3_winograd3_rgb_f32 if form3 else _lib.lib().mgf_conv3x3_winograd2_rgb_f32
+    _lib.check(launch(rgb_out.data_ptr(), x.data_ptr(), u.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale), rgb_w.data_ptr(), _lib.ptr(rgb_bias),
+                      n, cin, h, w, cout, _scale_stride(out_scale), rgb_w.shape[1], _lib.stream_ptr()), "conv3x3_winograd3_rgb" if form3 else "conv3x3_winograd2_rgb")
     return rgb_out
 
 
@@ -308,11 +291,60 @@ def winograd_forward(x, u, in_scale=None, out_scale=None, epilogue=None, out=Non
     if out is None:
         out = torch.empty([n, cout, h, w], dtype=torch.float32, device=x.device)
     assert out.is_contiguous() and tuple(out.shape) == (n, cout, h, w)
-    os_stride = 0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0
     rc = _lib.lib().mgf_conv3x3_winograd_f32(out.data_ptr(), x.data_ptr(), u.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale), n, cin, h, w,
-                                             cout, os_stride, C.byref(epilogue) if epilogue is not None else None, _lib.stream_ptr())
+                                             cout, _scale_stride(out_scale), C.byref(epilogue) if epilogue is not None else None, _lib.stream_ptr())
     _lib.check(rc, "conv3x3_winograd")
     return out
+
+
+@dataclass
+class Conv3x3:
+    """One 3x3 / stride-1 / pad-1 layer in every layout its kernels read (pack_conv3x3, transpose_conv3x3, or wrapped around a pack)."""
+    pc: PackedConv                      # the tap-list image: always there
+    u: torch.Tensor | None = None       # Winograd planes: [16, cin, cout] (form 1, 16 px maps) or [16, cin / 4, cout, 4] (forms 2 / 3, larger maps)
+
+    def __post_init__(self):
+        self.cin, self.cout = self.pc.cin, self.pc.cout
+        assert (self.pc.kh, self.pc.kw) == (3, 3)
+        assert self.u is None or tuple(self.u.shape) in ((16, self.cin, self.cout), (16, self.cin // 4, self.cout, 4)), tuple(self.u.shape)
+
+
+def pack_conv3x3(w: torch.Tensor, gain: float = 1.0, want_wsq: bool = False, winograd: bool = False, res: int | None = None) -> Conv3x3:
+    """[cout, cin, 3, 3] -> Conv3x3.  winograd: with the Winograd planes -- the caller says whether the layer is eligible -- in the forms-2/3
+    layout, or, given the one map side `res` the layer runs at, in the layout of the form that is faster there (winograd_pack)."""
+    u = None if not winograd else winograd2_weights(w, gain) if res is None else winograd_pack(w, gain, res)
+    return Conv3x3(pack_weights(w, gain=gain, want_wsq=want_wsq), u)
+
+
+def transpose_conv3x3(layer: Conv3x3, winograd: bool = False, res: int | None = None) -> Conv3x3:
+    """The layer of the data gradient -- a true convolution with the same kernel, cout -> cin channels: transpose_packed(flip=True) and,
+    with `winograd` (as in pack_conv3x3), the planes of the transposed, flipped kernel, rebuilt from the packed taps (gain already folded in)."""
+    pc, u = layer.pc, None
+    if winograd:
+        wt = pc.wp[:, :, :pc.cout].reshape(3, 3, pc.cin, pc.cout).permute(2, 3, 0, 1).flip(2, 3).contiguous()       # [cin, cout, kh, kw]
+        u = winograd2_weights(wt, 1.0) if res is None else winograd_pack(wt, 1.0, res)
+    return Conv3x3(transpose_packed(pc, flip=True), u)
+
+
+def conv3x3_takes_winograd(layer: Conv3x3, n, h, w) -> bool:
+    """THE rule for which kernel runs a 3x3 / stride-1 / pad-1 layer on n maps of h x w: the Winograd kernel where the layer has planes, their
+    layout is the one of this map size (form 1 on maps 16 px short, forms 2 / 3 above: winograd_pack) and the launch fills the chip
+    (winograd_fills_chip, looked up at call time); the tap-list kernel otherwise."""
+    if layer.u is None or (layer.u.ndim == 3) != (min(h, w) <= 16):
+        return False
+    return bool(winograd_fills_chip(n, layer.cout, h, w))
+
+
+def conv3x3_forward(x, layer: Conv3x3, in_scale=None, out_scale=None, epilogue=None, out=None, out_choff=0, residual_low=None):
+    """The layer on the kernel conv3x3_takes_winograd names; arguments as conv_forward(pad=(1, 1)) and winograd2_forward (residual_low needs
+    the form-3 Winograd launch).  It calls the wrappers below it through the module's globals (tests/conv_replay.py swaps them)."""
+    if not conv3x3_takes_winograd(layer, x.shape[0], x.shape[2], x.shape[3]):
+        assert residual_low is None, "residual_low needs the form-3 Winograd launch"
+        return conv_forward(x, layer.pc, pad=(1, 1), in_scale=in_scale, out_scale=out_scale, epilogue=epilogue, out=out, out_choff=out_choff)
+    if layer.u.ndim == 4:
+        return winograd2_forward(x, layer.u, in_scale, out_scale, epilogue, out, out_choff, residual_low)
+    assert out_choff == 0, "form 1 writes whole tensors"
+    return winograd_forward(x, layer.u, in_scale, out_scale, epilogue, out, residual_low)
 
 
 def conv_large_forward(x, w, bias, stride, pad, act="relu", out=None):
@@ -507,23 +539,26 @@ def tconv3x3s2_forward(x, pc: PackedConv, in_scale=None, out_scale=None, out=Non
                                                        pitch, oh * pitch, pc.cout * oh * pitch, _lib.stream_ptr())
         _lib.check(rc, "tconv3x3s2_few_outputs")
         return out[:, :, :, :ow]
-    if wt is not None and tconv_winograd_ok(n, cin, h, w, pc.cout, out, bf):
-        assert tuple(wt.shape) == (25, cin // 4, pc.cout, 4)
-        os_stride = 0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0
-        rc = _lib.lib().mgf_tconv3x3s2_winograd_f32(out.data_ptr(), x.data_ptr(), wt.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale), n, cin, h,
-                                                    w, pc.cout, pitch, oh * pitch, pc.cout * oh * pitch, os_stride, _lib.stream_ptr())
-        _lib.check(rc, "tconv3x3s2_winograd")
+    os_stride = _scale_stride(out_scale)
+
+    def border():                                      # the last row and column of the split forms
         rc = _lib.lib().mgf_tconv3x3s2_border_f32(out.data_ptr(), x.data_ptr(), pc.wp.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale),
                                                   n, cin, h, w, pc.cout, pc.cout_pad, pitch, oh * pitch, pc.cout * oh * pitch, os_stride,
                                                   _lib.stream_ptr())
         _lib.check(rc, "tconv3x3s2_border")
+
+    if wt is not None and tconv_winograd_ok(n, cin, h, w, pc.cout, out, bf):
+        assert tuple(wt.shape) == (25, cin // 4, pc.cout, 4)
+        rc = _lib.lib().mgf_tconv3x3s2_winograd_f32(out.data_ptr(), x.data_ptr(), wt.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale), n, cin, h,
+                                                    w, pc.cout, pitch, oh * pitch, pc.cout * oh * pitch, os_stride, _lib.stream_ptr())
+        _lib.check(rc, "tconv3x3s2_winograd")
+        border()
         return out[:, :, :, :ow]
     # (one or two images -- gradient mode at a single target -- keep the single launch up to 64 px: the border kernel's few workgroups then
     # cost more than the padded tiles, 6.76 -> 6.64 ms per gradient step; from four images on the split wins from 16 px, 686 vs 677 iters/s)
     split = SPLIT_TCONV_BORDER and min(h, w) >= (TCONV_SPLIT_MIN if n >= 4 else max(TCONV_SPLIT_MIN, 128))
     # bf: the main launch in the opt-in bf16x3 arithmetic (needs the split form: whole 32-wide tiles of quads); the border stays float32
     use_bf = bf is not None and split and w % 32 == 0 and cin % 16 == 0
-    os_stride = 0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0
     d = _desc(n, cin, h, w, pc.cout, pc.cout_pad, h if split else h + 1, w if split else w + 1, 1, 2, TCONV_TAPS, TCONV_GROUPS,
               [0, 0, 1, 1], [0, 1, 0, 1], oh, ow, pitch, oh * pitch, pc.cout * oh * pitch, 0, os_stride)
     if use_bf:
@@ -534,10 +569,7 @@ def tconv3x3s2_forward(x, pc: PackedConv, in_scale=None, out_scale=None, out=Non
                                           C.byref(d), None, _lib.stream_ptr())
     _lib.check(rc, "conv_taps(tconv)")
     if split:
-        rc = _lib.lib().mgf_tconv3x3s2_border_f32(out.data_ptr(), x.data_ptr(), pc.wp.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale),
-                                                  n, cin, h, w, pc.cout, pc.cout_pad, pitch, oh * pitch, pc.cout * oh * pitch, os_stride,
-                                                  _lib.stream_ptr())
-        _lib.check(rc, "tconv3x3s2_border")
+        border()
     return out[:, :, :, :ow]
 
 
@@ -597,10 +629,9 @@ def tconv3x3s2_blur_forward(x, pc: PackedConv, f1d, gain, in_scale=None, out_sca
     assert tuple(out.shape) == (n, pc.cout, 2 * h, 2 * w) and out.dtype == torch.float32
     if tconv_blur_ok(n, cin, h, w, pc.cout, out, f1d, epilogue, bf):
         sy = out.stride()
-        os_stride = 0 if out_scale is None else out_scale.stride(0) if out_scale.ndim == 2 else 0
         rc = _lib.lib().mgf_tconv3x3s2_blur_f32(out.data_ptr(), x.data_ptr(), pc.wp.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale),
                                                 f1d.data_ptr(), float(gain), n, cin, h, w, pc.cout, pc.cout_pad, sy[2], sy[1], sy[0],
-                                                os_stride, C.byref(epilogue) if epilogue is not None else None, _lib.stream_ptr())
+                                                _scale_stride(out_scale), C.byref(epilogue) if epilogue is not None else None, _lib.stream_ptr())
         if rc != -2:                                   # MGF_EUNSUPPORTED: the three launches below
             _lib.check(rc, "tconv3x3s2_blur")
             return out

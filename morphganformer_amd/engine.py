@@ -91,7 +91,8 @@ class ConvLayerPlan:
     up: int
     slot: int
     kind: str                       # "conv3" | "tconv" | "torgb"
-    pc: cv.PackedConv = None
+    pc: cv.PackedConv = None        # "tconv" and "torgb" layers: the tap-list image
+    conv: cv.Conv3x3 = None         # "conv3" layers: the tap-list image and, on 16^2 .. WINOGRAD_MAX_RES^2 maps, the Winograd planes (csrc/wino*.hip)
     aff_w: torch.Tensor = None
     aff_b: torch.Tensor = None
     style_gain: float = 1.0
@@ -103,11 +104,15 @@ class ConvLayerPlan:
     attn: "AttnPlan" = None
     w_raw: torch.Tensor = None      # toRGB only: [img_channels, cin] un-packed weights for the fused projection
     w_gained: torch.Tensor = None   # conv_last only: [cout, cin, 3, 3] weights times w_gain, un-packed, for the composition with ToRGB
-    wino_u: torch.Tensor = None     # 3x3 stride-1 layers on 16^2 .. 256^2 maps: Winograd-transformed weights (csrc/wino.hip)
     wino_t: torch.Tensor = None     # transposed convs of the blocks up to TCONV_WINO_MAX_RES: polyphase Winograd weights (csrc/wino_tconv.hip)
     pcb: torch.Tensor = None        # arith="bf16x3" only: the weights split into two bfloat16 terms (conv.pack_weights_bf16x3)
     s_off: int = 0                  # offsets (floats) into the per-sample style / demod arenas
     d_off: int = 0
+
+    @property
+    def packed(self) -> cv.PackedConv:
+        """The tap-list image of a layer of any kind."""
+        return self.pc if self.conv is None else self.conv.pc
 
 
 @dataclass
@@ -158,20 +163,22 @@ class SynthesisPlan:
             else:
                 wg = 1.0 / math.sqrt(cin * 9)
                 # up=1: correlation (flip_weight=True); up=2: conv_transpose2d on the un-flipped weights
-                lp.pc = cv.pack_weights(t32(w), gain=wg, flip=False, want_wsq=True)
                 # Winograd F(2x2,3x3) where it beats the 9-tap kernel IN the iteration (rocprofv3 trace, conv1 layers with their residual
                 # epilogue): every 3x3 stride-1 layer from 32^2 up (1024^2: +1 % iterations/s, the smallest margin), conv_last with the
                 # ToRGB projection fused into its epilogue like the tap-list launch.  MGF_WINOGRAD=0 (tuning hook) = direct kernel
                 # everywhere, MGF_WINOGRAD_MAX_RES limits the map size
-                if kind == "conv3" and USE_WINOGRAD and cv.winograd_ok(cin, cout, res, res) and res <= WINOGRAD_MAX_RES:
-                    lp.wino_u = cv.winograd_pack(t32(w), wg, res)
+                if kind == "conv3":
+                    lp.conv = cv.pack_conv3x3(t32(w), wg, want_wsq=True, res=res,
+                                              winograd=USE_WINOGRAD and cv.winograd_ok(cin, cout, res, res) and res <= WINOGRAD_MAX_RES)
+                else:
+                    lp.pc = cv.pack_weights(t32(w), gain=wg, flip=False, want_wsq=True)
                 # polyphase Winograd transposed conv (float32 mode): the up-sampling layers into the blocks up to TCONV_WINO_MAX_RES
                 if (kind == "tconv" and arith != "bf16x3" and cv.TCONV_WINO and res <= TCONV_WINO_MAX_RES and cin % 4 == 0
                         and cout % 32 == 0):
                     lp.wino_t = cv.tconv_winograd_weights(t32(w), wg)
                 # the opt-in bf16x3 arithmetic: every transposed conv and 3x3 layer the kernel serves (maps at least 32 wide, cin % 16 == 0)
                 if arith == "bf16x3" and cin % 16 == 0 and res // up >= 32:
-                    lp.pcb = cv.pack_weights_bf16x3(lp.pc)
+                    lp.pcb = cv.pack_weights_bf16x3(lp.packed)
             lp.aff_w = t32(f64(p + ".affine.weight"))
             lp.aff_b = t32(f64(p + ".affine.bias"))
             if (p + ".biasAct.bias") in sd:
@@ -321,8 +328,8 @@ class Generator:
         res = l1.res
         if l1.pcb is not None and res <= BF_DIRECT_MAX_RES:       # bf16x3 mode: this layer takes the direct kernel (full-resolution residual)
             return False
-        return bool(self.fuse_skip_up and self.plan.fir_is_1331 and cv.WINOGRAD_FORM == 3 and l1.attn is None and l1.wino_u is not None
-                    and l1.wino_u.ndim == 4 and res % 2 == 0 and cv.winograd_fills_chip(n, l1.cout, res, res))
+        return bool(self.fuse_skip_up and self.plan.fir_is_1331 and cv.WINOGRAD_FORM == 3 and l1.attn is None and res % 2 == 0
+                    and cv.conv3x3_takes_winograd(l1.conv, n, res, res) and l1.conv.u.ndim == 4)
 
     def _lean_arenas(self, n):
         """Floats per sample of the lean flavour's arenas: T (transposed-conv workspace, also conv_last's output), U (conv0; conv1 before its
@@ -427,7 +434,7 @@ class Generator:
             aj = []
             for i, lp in enumerate(P.layers):
                 g_off = ((cfg.k - 1) * NW + lp.slot) * D if per_layer else (cfg.k - 1) * D          # the global component (get_global)
-                sj[i] = _lib.StyleJob(lp.aff_w.data_ptr(), lp.aff_b.data_ptr(), _lib.ptr(lp.pc.wsq) if lp.demod else 0,
+                sj[i] = _lib.StyleJob(lp.aff_w.data_ptr(), lp.aff_b.data_ptr(), _lib.ptr(lp.packed.wsq) if lp.demod else 0,
                                       self.styles.data_ptr() + 4 * lp.s_off * n,
                                       (self.demods.data_ptr() + 4 * lp.d_off * n) if lp.demod else 0,
                                       lp.cin, lp.cout, g_off, 1.0 / math.sqrt(D), lp.style_gain)
@@ -618,16 +625,13 @@ class Generator:
                     # conv_last + ToRGB in one kernel: the [n,32,R,R] conv_last activation never goes to HBM
                     _lib.check(L.mgf_rgb_weights_f32(self.rgbw.data_ptr(), lt.w_raw.data_ptr(), self._s(lt).data_ptr(), n, lt.w_raw.shape[0],
                                                      lt.w_raw.shape[1], st), "rgb_weights")                       # W[c,co] * s[n,co]
-                    if lp.wino_u is not None and lp.wino_u.ndim == 4 and lp.cout == 32 and cv.winograd_fills_chip(n, lp.cout, res, res):
-                        cv.winograd2_rgb_forward(x, lp.wino_u, self.rgbw, lt.bias, self.img, in_scale=self._s(lp), out_scale=self._d(lp))
+                    if lp.cout == 32 and cv.conv3x3_takes_winograd(lp.conv, n, res, res) and lp.conv.u.ndim == 4:
+                        cv.winograd2_rgb_forward(x, lp.conv.u, self.rgbw, lt.bias, self.img, in_scale=self._s(lp), out_scale=self._d(lp))
                     else:
-                        cv.conv_forward(x, lp.pc, pad=(1, 1), in_scale=self._s(lp), out_scale=self._d(lp),
+                        cv.conv_forward(x, lp.conv.pc, pad=(1, 1), in_scale=self._s(lp), out_scale=self._d(lp),
                                         rgb=(self.rgbw, lt.bias, self.img))
                 else:
-                    if lp.wino_u is not None and cv.winograd_fills_chip(n, lp.cout, res, res):
-                        x = cv.winograd_forward(x, lp.wino_u, in_scale=self._s(lp), out_scale=self._d(lp), out=B["last"])
-                    else:
-                        x = cv.conv_forward(x, lp.pc, pad=(1, 1), in_scale=self._s(lp), out_scale=self._d(lp), out=B["last"])
+                    x = cv.conv3x3_forward(x, lp.conv, in_scale=self._s(lp), out_scale=self._d(lp), out=B["last"])
                     if self.taps is not None:
                         self.taps[b] = x
                     ep = _lib.make_epilogue(bias=lt.bias)
@@ -731,12 +735,9 @@ class Generator:
                                 separable=True)
         elif self._bf_direct(lp, n, residual_low):
             # bf16x3 mode: the direct 3x3 form at three bf16 matrix instructions per 16 channels beats float32 Winograd below 256^2
-            y = cv.conv_forward(x, lp.pc, pad=(1, 1), in_scale=s, out_scale=d, epilogue=None if has_att else ep, out=B[key], bf=lp.pcb)
-        elif lp.wino_u is not None and cv.winograd_fills_chip(n, lp.cout, lp.res, lp.res):
-            y = cv.winograd_forward(x, lp.wino_u, in_scale=s, out_scale=d, epilogue=None if has_att else ep, out=B[key],
-                                    residual_low=residual_low)
+            y = cv.conv_forward(x, lp.conv.pc, pad=(1, 1), in_scale=s, out_scale=d, epilogue=None if has_att else ep, out=B[key], bf=lp.pcb)
         else:
-            y = cv.conv_forward(x, lp.pc, pad=(1, 1), in_scale=s, out_scale=d, epilogue=None if has_att else ep, out=B[key])
+            y = cv.conv3x3_forward(x, lp.conv, in_scale=s, out_scale=d, epilogue=None if has_att else ep, out=B[key], residual_low=residual_low)
         if self.taps is not None:
             self.taps[lp.name + ":conv"] = y
         if has_att:

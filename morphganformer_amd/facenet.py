@@ -146,8 +146,9 @@ def conv_gflop(h, w):
 
 
 class _Conv:
-    """One BasicConv2d (BatchNorm folded) or closing 1x1, packed for the kernels."""
-    __slots__ = ("pc", "bias", "k", "stride", "pad", "wino", "w_raw", "cin", "cout")
+    """One BasicConv2d (BatchNorm folded) or closing 1x1, packed for the kernels: `c3` (conv.Conv3x3) where it is 3x3 / stride 1 / pad 1,
+    `pc` otherwise."""
+    __slots__ = ("pc", "c3", "bias", "k", "stride", "pad", "w_raw", "cin", "cout")
 
 
 class InceptionResnetV1Embedder(FaceEmbedder):
@@ -175,9 +176,10 @@ class InceptionResnetV1Embedder(FaceEmbedder):
             s, t = bn_affine(sd, name + ".bn", BN_EPS)
             L = _Conv()
             wf = t32(w * s[:, None, None, None])
-            L.pc, L.bias = cv.pack_weights(wf), t32(t)
-            L.k, L.stride, L.pad, L.cin, L.cout = k, stride, pad, cin, cout
-            L.wino = cv.winograd2_weights(wf) if (k == (3, 3) and stride == 1 and pad == (1, 1) and cin % 4 == 0 and cout % 32 == 0) else None
+            L.k, L.stride, L.pad, L.cin, L.cout, L.bias = k, stride, pad, cin, cout, t32(t)
+            c3 = k == (3, 3) and stride == 1 and pad == (1, 1)
+            L.c3 = cv.pack_conv3x3(wf, winograd=cin % 4 == 0 and cout % 32 == 0) if c3 else None
+            L.pc = None if c3 else cv.pack_weights(wf)
             L.w_raw = wf if cin <= 4 else None              # the 3-channel stem: the streaming kernel takes the torch layout
             return L
 
@@ -185,7 +187,7 @@ class InceptionResnetV1Embedder(FaceEmbedder):
             L = _Conv()
             L.pc = cv.pack_weights(t32(g(name + ".conv2d.weight") * scale))
             L.bias = t32(g(name + ".conv2d.bias") * scale)
-            L.k, L.stride, L.pad, L.cin, L.cout, L.wino, L.w_raw = (1, 1), 1, (0, 0), ccat, c, None, None
+            L.k, L.stride, L.pad, L.cin, L.cout, L.c3, L.w_raw = (1, 1), 1, (0, 0), ccat, c, None, None
             return L
 
         self.stem = [(name, basic(name, spec) if spec is not None else None) for name, spec in STEM]
@@ -273,11 +275,10 @@ class InceptionResnetV1Embedder(FaceEmbedder):
     # ------------------------------------------------------------------ forward
     def _conv(self, x, L, out, choff=0, act="relu", residual=None):
         ep = _lib.make_epilogue(bias=L.bias, act=act, residual=residual)
-        n, _, h, w = x.shape
         if L.w_raw is not None and L.stride == 2 and L.k == (3, 3) and L.pad == (0, 0) and choff == 0 and act == "relu":
             return cv.conv3x3s2_few_inputs(x, L.w_raw, bias=L.bias, relu=True, out=out)
-        if L.wino is not None and cv.winograd_fills_chip(n, L.cout, h, w):
-            return cv.winograd2_forward(x, L.wino, epilogue=ep, out=out, out_choff=choff)
+        if L.c3 is not None:
+            return cv.conv3x3_forward(x, L.c3, epilogue=ep, out=out, out_choff=choff)
         return cv.conv_forward(x, L.pc, stride=L.stride, pad=L.pad, epilogue=ep, out=out, out_choff=choff)
 
     def _pool(self, y, x):
@@ -336,7 +337,7 @@ class InceptionResnetV1Embedder(FaceEmbedder):
             gp = self._gpacks = {}
         t = gp.get(id(L))
         if t is None:
-            t = gp[id(L)] = cv.transpose_packed(L.pc, flip=(L.stride == 1 and L.k != (1, 1)))
+            t = gp[id(L)] = cv.transpose_packed(L.pc if L.c3 is None else L.c3.pc, flip=(L.stride == 1 and L.k != (1, 1)))
         return t
 
     def _gbuf(self, key, shape):

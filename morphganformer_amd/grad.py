@@ -46,19 +46,11 @@ class GeneratorGrad:
     def __init__(self, G: Generator):
         self.G = G
         P = G.plan
-        self.T = {}
-        for lp in P.layers:
-            # 3x3 stride-1 correlation -> true convolution (taps reversed); the transposed conv's gradient is a plain stride-2
-            # correlation with the same taps; 1x1 needs no flip
-            self.T[lp.name] = cv.transpose_packed(lp.pc, flip=(lp.kind == "conv3"))
+        # the data-gradient layers.  3x3 stride-1 correlation -> true convolution (taps reversed), on the Winograd kernel too where the
+        # forward has its planes; the transposed conv's gradient is a plain stride-2 correlation with the same taps; 1x1 needs no flip
+        self.T = {lp.name: cv.transpose_packed(lp.pc, flip=False) if lp.conv is None else
+                  cv.transpose_conv3x3(lp.conv, winograd=lp.conv.u is not None, res=lp.res) for lp in P.layers}
         self.Tskip = {res: cv.transpose_packed(pc, flip=False) for res, pc in P.skips.items()}
-        # layers the forward runs through the Winograd kernel take it for their data gradient too: the transposed, flipped kernel
-        # is rebuilt from the packed taps (gain already folded in) and transformed once
-        self.Tw = {}
-        for lp in P.layers:
-            if lp.wino_u is not None:
-                w = lp.pc.wp[:, :, :lp.cout].reshape(3, 3, lp.cin, lp.cout).permute(3, 2, 0, 1)        # [cout, cin, kh, kw]
-                self.Tw[lp.name] = cv.winograd_pack(w.permute(1, 0, 2, 3).flip(2, 3).contiguous(), 1.0, lp.res)
         self._bufs = {}
         self._n = None
         self._gen = None                  # generation id of the generator workspace the job tables below point into
@@ -106,7 +98,7 @@ class GeneratorGrad:
             self.ds_part[lp.name] = e(n, lp.cin, sc)
             if lp.demod:
                 self.dc_part[lp.name] = e(n, lp.cout, dc)
-            sj.append(_lib.StyleBwdJob(lp.aff_w.data_ptr(), _lib.ptr(lp.pc.wsq) if lp.demod else 0, G._s(lp).data_ptr(),
+            sj.append(_lib.StyleBwdJob(lp.aff_w.data_ptr(), _lib.ptr(lp.packed.wsq) if lp.demod else 0, G._s(lp).data_ptr(),
                                        G._d(lp).data_ptr() if lp.demod else 0, self.ds_part[lp.name].data_ptr(),
                                        self.dc_part[lp.name].data_ptr() if lp.demod else 0, lp.cin, lp.cout, sc, dc,
                                        1.0 / math.sqrt(D), lp.style_gain))
@@ -314,10 +306,7 @@ class GeneratorGrad:
             dT = self.buf("dT", (n, c, h + 1, w + 1))
             cv.upfirdn_into(dT, dc, G.plan.fir, up=1, pad=(2, 2, 2, 2), gain=4.0, flip=True, separable=True)    # (plan.fir is an outer product, cf. engine._layer)
             return cv.conv_forward(dT, self.T[lp.name], stride=2, pad=(0, 0), in_scale=d, out=self.buf("g", x_in.shape))
-        pad = (1, 1) if lp.kind == "conv3" else (0, 0)
-        if lp.name in self.Tw and cv.winograd_fills_chip(n, x_in.shape[1], h, w):
-            return cv.winograd_forward(dc, self.Tw[lp.name], in_scale=d, out=self.buf("g", x_in.shape))
-        return cv.conv_forward(dc, self.T[lp.name], pad=pad, in_scale=d, out=self.buf("g", x_in.shape))
+        return cv.conv3x3_forward(dc, self.T[lp.name], in_scale=d, out=self.buf("g", x_in.shape))     # (conv1 / conv_last: ToRGB has its own path in _backward_layers_body)
 
     def _style_bwd(self, lp, g, x_in, dx_role, accumulate=False):
         """<x_in, g> partials of the style gradient and d(x_in) (+)= s * g."""

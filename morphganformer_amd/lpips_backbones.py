@@ -149,7 +149,7 @@ class TapFeatures:
 class SequentialFeatures(TapFeatures):
     """LPIPS taps of a plain conv/ReLU/max-pool stack (VGG16, AlexNet) for a fixed input size, preallocated workspace.
     The ScalingLayer runs as its own element-wise step (these nets zero-pad the SCALED input, so it cannot be folded)."""
-    _SHARED = ("convs", "shift", "scale", "gp", "wino")
+    _SHARED = ("convs", "first4", "shift", "scale", "gp")
 
     def __init__(self, net, backbone_state, n, h, w, device, share=None):
         super().__init__(n, device, share)
@@ -158,29 +158,27 @@ class SequentialFeatures(TapFeatures):
         t32 = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32), device=dev)
         if share is None:
             self.gp = {}                                   # channel-transposed packs of the backward pass, built on first use
-            self.convs = {}
+            # (Conv3x3 | [cout, cin, k, k] weights of the layers with > 9 taps: packed per tap group at run time, bias) of every conv.
             # 3x3 / stride-1 / pad-1 layers with whole 32-channel tiles (every VGG16 layer but the first, AlexNet's last three): Winograd
             # F(2x2,3x3) form 3 when the launch fills the chip -- 4/9 of the matrix work of the tap-list kernel, which runs these layers at
             # 0.80 of the FP32-MFMA peak and cannot get much closer (MGF_WINOGRAD_LPIPS=0: tap-list kernel everywhere)
-            self.wino = {}
+            self.convs, self.first4 = {}, None
             for row in self.spec:
                 if row[0] == "conv":
                     _, idx, ci, co, k, st_, pd_ = row
+                    assert k != 3 or (st_, pd_) == (1, 1)
                     wt, b = t32(backbone_state[f"features.{idx}.weight"]), t32(backbone_state[f"features.{idx}.bias"])
-                    self.convs[idx] = (cv.pack_weights(wt) if k == 3 else wt, b)          # > 9 taps: packed per tap group at run time
-                    if USE_WINOGRAD_LPIPS and k == 3 and st_ == 1 and pd_ == 1 and ci % 4 == 0 and co % 32 == 0:
-                        self.wino[idx] = cv.winograd2_weights(wt)
-                    elif USE_WINOGRAD_LPIPS and k == 3 and st_ == 1 and pd_ == 1 and ci == 3 and co % 32 == 0 and row is self.spec[0]:
+                    self.convs[idx] = (cv.pack_conv3x3(wt, winograd=USE_WINOGRAD_LPIPS and ci % 4 == 0 and co % 32 == 0) if k == 3 else wt, b)
+                    if USE_WINOGRAD_LPIPS and k == 3 and ci == 3 and co % 32 == 0 and row is self.spec[0]:
                         # VGG16's first layer (3 -> 64 at the full image size: 4.3 GB of output per 16 images, 58 GFLOP): a FOURTH, all-zero
                         # input channel makes it a Winograd launch (the tap-list kernel stages 3 channels synchronously: 2.85 ms per 16 images)
-                        self.wino[idx] = cv.winograd2_weights(torch.cat([wt, torch.zeros_like(wt[:, :1])], dim=1).contiguous())
+                        self.first4 = cv.pack_conv3x3(torch.cat([wt, torch.zeros_like(wt[:, :1])], dim=1).contiguous(), winograd=True)
             self.shift, self.scale = t32(SHIFT).reshape(1, 3, 1, 1), t32(SCALE).reshape(1, 3, 1, 1)
         e = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
         self.xs = e(n, 3, h, w)
         # the scaled input with a fourth, zero channel: what the first layer's Winograd form reads (see above)
-        first = self.spec[0]
         self.xs4 = (torch.zeros(n, 4, h, w, dtype=torch.float32, device=dev)
-                    if first[1] in self.wino and first[2] == 3 and min(h, w) > 16 and cv.winograd_fills_chip(n, first[3], h, w) else None)
+                    if self.first4 is not None and cv.conv3x3_takes_winograd(self.first4, n, h, w) else None)
         self.bufs, self.shapes = [], {}
         c, hh, ww = 3, h, w
         for row in self.spec:
@@ -212,11 +210,9 @@ class SequentialFeatures(TapFeatures):
                 dst = out[len(taps)] if (out is not None and nxt[0] == "tap") else buf
                 if pos == 0 and self.xs4 is not None:
                     self.xs4[:, :3].copy_(h)                          # channel 3 stays zero
-                    h = cv.winograd2_forward(self.xs4, self.wino[idx], epilogue=_lib.make_epilogue(bias=b, act="relu"), out=dst)
-                elif idx in self.wino and ci % 4 == 0 and min(h.shape[2:]) > 16 and cv.winograd_fills_chip(h.shape[0], co, h.shape[2], h.shape[3]):
-                    h = cv.winograd2_forward(h, self.wino[idx], epilogue=_lib.make_epilogue(bias=b, act="relu"), out=dst)
+                    h = cv.winograd2_forward(self.xs4, self.first4.u, epilogue=_lib.make_epilogue(bias=b, act="relu"), out=dst)
                 elif k == 3:
-                    h = cv.conv_forward(h, wt, stride=s, pad=(p, p), epilogue=_lib.make_epilogue(bias=b, act="relu"), out=dst)
+                    h = cv.conv3x3_forward(h, wt, epilogue=_lib.make_epilogue(bias=b, act="relu"), out=dst)
                 else:
                     h = cv.conv_large_forward(h, wt, b, s, p, act="relu", out=dst)
             elif row[0] == "pool":
@@ -238,7 +234,7 @@ class SequentialFeatures(TapFeatures):
         if not self.gp:
             for row in self.spec:
                 if row[0] == "conv" and row[4] == 3:
-                    self.gp[row[1]] = cv.transpose_packed(self.convs[row[1]][0], flip=True)
+                    self.gp[row[1]] = cv.transpose_packed(self.convs[row[1]][0].pc, flip=True)
         if self.gbufs is None:
             self.gbufs = [None if b is None else torch.empty_like(b) for b in self.bufs]
             self.gxs = torch.empty_like(self.xs)
@@ -285,14 +281,14 @@ def _pool_out(n):
 
 class SqueezeFeatures(TapFeatures):
     """The 7 LPIPS taps of SqueezeNet1.1 for a fixed input size, with a preallocated workspace."""
-    _SHARED = ("c0", "fires", "wino3", "merged", "wino3m", "stem_w", "stem_b", "gp", "gpw", "gpm", "gpwm")   # packed weights are size independent
+    _SHARED = ("c0", "fires", "merged", "stem_w", "stem_b", "gp", "gpm")   # packed weights are size independent
 
     def __init__(self, backbone_state, n, h, w, device, share=None):
         super().__init__(n, device, share)
         dev = self.device
         if share is None:
-            self.gp, self.gpw = {}, {}                            # channel-transposed packs of the backward pass (+ Winograd images), built on first use
-            self.gpm, self.gpwm = {}, {}                          # ... of the merged expand launch (one image per forward)
+            self.gp = {}                                          # channel-transposed packs of the backward pass (+ Winograd images), built on first use
+            self.gpm = {}                                         # ... of the merged expand launch (one image per forward)
             g = lambda k: np.asarray(backbone_state[k], dtype=np.float64)
             t32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=dev)
             w0, b0 = g("features.0.weight"), g("features.0.bias")
@@ -301,16 +297,15 @@ class SqueezeFeatures(TapFeatures):
             b0f = b0 - (w0 * (sh / sc)[None, :, None, None]).sum(axis=(1, 2, 3))
             self.c0 = (cv.pack_weights(t32(w0f)), t32(b0f))
             self.stem_w, self.stem_b = t32(w0f.reshape(64, 27)), t32(b0f)       # operands of the fused stem kernel
+            # (squeeze, expand1x1: PackedConv; expand3x3: Conv3x3 with its Winograd planes -- odd maps, concat slice), each with its bias
             self.fires = {}
-            self.wino3 = {}                                       # expand3x3 in Winograd form (csrc/wino.hip form 2: odd maps, concat slice)
             for idx in FIRES:
                 p = f"features.{idx}"
-                self.fires[idx] = tuple((cv.pack_weights(t32(g(f"{p}.{nm}.weight"))), t32(g(f"{p}.{nm}.bias")))
-                                        for nm in ("squeeze", "expand1x1", "expand3x3"))
-                if USE_WINOGRAD_LPIPS:
-                    self.wino3[idx] = cv.winograd2_weights(t32(g(f"{p}.expand3x3.weight")))
+                wt, bs = (lambda nm: t32(g(f"{p}.{nm}.weight"))), (lambda nm: t32(g(f"{p}.{nm}.bias")))
+                self.fires[idx] = ((cv.pack_weights(wt("squeeze")), bs("squeeze")), (cv.pack_weights(wt("expand1x1")), bs("expand1x1")),
+                                   (cv.pack_conv3x3(wt("expand3x3"), winograd=USE_WINOGRAD_LPIPS), bs("expand3x3")))
             # the merged expand launch of the one-image path (MERGE_FIRE): [2 ex, sq, 3, 3], expand1x1 in the centre tap of the first ex kernels
-            self.merged, self.wino3m = {}, {}
+            self.merged = {}
             for idx in FIRES:
                 p = f"features.{idx}"
                 w1, w3 = g(f"{p}.expand1x1.weight"), g(f"{p}.expand3x3.weight")
@@ -318,9 +313,7 @@ class SqueezeFeatures(TapFeatures):
                 wm[:w1.shape[0], :, 1, 1] = w1[:, :, 0, 0]
                 wm[w1.shape[0]:] = w3
                 bm = np.concatenate([g(f"{p}.expand1x1.bias"), g(f"{p}.expand3x3.bias")])
-                self.merged[idx] = (cv.pack_weights(t32(wm)), t32(bm))
-                if USE_WINOGRAD_LPIPS:
-                    self.wino3m[idx] = cv.winograd2_weights(t32(wm))
+                self.merged[idx] = (cv.pack_conv3x3(t32(wm), winograd=USE_WINOGRAD_LPIPS), t32(bm))
         self.merge = set()           # Fire modules whose expand branches run merged (filled below: one image, maps the Winograd launch fills the chip with)
         e = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
         hh, ww = (h - 3) // 2 + 1, (w - 3) // 2 + 1
@@ -339,7 +332,7 @@ class SqueezeFeatures(TapFeatures):
                 self.sq[idx] = e(n, sq, hh, ww)
                 # merged only where the merged launch is a Winograd launch (255^2 / 127^2 maps of a 1024^2 image): there both branches sit on
                 # their launch latency; on the 63^2 maps the tap-list kernel does real work and twice of it costs more than a launch saves
-                if MERGE_FIRE and n == 1 and idx in self.wino3m and min(hh, ww) > 16 and cv.winograd_fills_chip(n, 2 * ex, hh, ww):
+                if MERGE_FIRE and n == 1 and cv.conv3x3_takes_winograd(self.merged[idx][0], n, hh, ww):
                     self.merge.add(idx)
                 c = 2 * ex
                 self.buf[idx] = e(n, c, hh, ww)
@@ -351,18 +344,13 @@ class SqueezeFeatures(TapFeatures):
         if not self.gp:
             self.gp["c0"] = cv.transpose_packed(self.c0[0], flip=False)       # stride-2 conv -> stride-2 transposed conv, same taps
             for idx, ((ps, _), (p1, _), (p3, _)) in self.fires.items():
-                self.gp[idx] = (cv.transpose_packed(ps, False), cv.transpose_packed(p1, False), cv.transpose_packed(p3, True))
-                if USE_WINOGRAD_LPIPS and p3.cin % 32 == 0:
-                    # the expand-3x3 data gradient (E -> S channels) on the Winograd kernel where S is a multiple of its 32-channel tile
-                    w = p3.wp[:, :, :p3.cout].reshape(3, 3, p3.cin, p3.cout).permute(3, 2, 0, 1)        # [E, S, kh, kw]
-                    # (the form-3 image whatever this instance's map size: the packs are shared between sizes)
-                    self.gpw[idx] = cv.winograd2_weights(w.permute(1, 0, 2, 3).flip(2, 3).contiguous(), 1.0)
+                # the expand-3x3 data gradient (E -> S channels) on the Winograd kernel where S is a multiple of its 32-channel tile
+                # (the forms-2/3 planes whatever this instance's map size: the packs are shared between sizes)
+                self.gp[idx] = (cv.transpose_packed(ps, False), cv.transpose_packed(p1, False),
+                                cv.transpose_conv3x3(p3, winograd=USE_WINOGRAD_LPIPS and p3.cin % 32 == 0))
             for idx, (pm, _) in self.merged.items():
                 # the merged data gradient: one true convolution over the concatenated gradient [d expand1x1 | d expand3x3] (2 ex -> sq channels)
-                self.gpm[idx] = cv.transpose_packed(pm, True)
-                if USE_WINOGRAD_LPIPS and pm.cin % 32 == 0:
-                    w = pm.wp[:, :, :pm.cout].reshape(3, 3, pm.cin, pm.cout).permute(3, 2, 0, 1)        # [2 ex, sq, kh, kw]
-                    self.gpwm[idx] = cv.winograd2_weights(w.permute(1, 0, 2, 3).flip(2, 3).contiguous(), 1.0)
+                self.gpm[idx] = cv.transpose_conv3x3(pm, winograd=USE_WINOGRAD_LPIPS and pm.cin % 32 == 0)
         if self.gbufs is None:
             e = lambda t: torch.empty_like(t)
             self.gbufs = {idx: e(t) for idx, t in self.buf.items()}
@@ -410,21 +398,11 @@ class SqueezeFeatures(TapFeatures):
             if not fused:
                 self._relu_bwd(gh, h, da, db)
             s, gs = self.sq[idx], self.gsq[idx]
-            merged = idx in self.merge
-            if merged:
-                gc = self.gcat[idx]
-                if idx in self.gpwm and min(hh, ww) > 16 and cv.winograd_fills_chip(n, gs.shape[1], hh, ww):
-                    cv.winograd_forward(gc, self.gpwm[idx], out=gs)
-                else:
-                    cv.conv_forward(gc, self.gpm[idx], pad=(1, 1), out=gs)
+            if idx in self.merge:
+                cv.conv3x3_forward(self.gcat[idx], self.gpm[idx], out=gs)
             else:
                 cv.conv_forward(da, e1T, out=gs)
-            if merged:
-                pass
-            elif idx in self.gpw and cv.winograd_fills_chip(n, gs.shape[1], hh, ww):
-                cv.winograd_forward(db, self.gpw[idx], epilogue=_lib.make_epilogue(residual=gs), out=gs)
-            else:
-                cv.conv_forward(db, e3T, pad=(1, 1), epilogue=_lib.make_epilogue(residual=gs), out=gs)
+                cv.conv3x3_forward(db, e3T, epilogue=_lib.make_epilogue(residual=gs), out=gs)
             self._relu_bwd(gs, s)
             cv.conv_forward(gs, sqT, out=self.gbufs[idx - 1])
         raise AssertionError("unreachable")
@@ -485,17 +463,15 @@ class SqueezeFeatures(TapFeatures):
                 y = dest(idx)
                 ex = p1.cout
                 if idx in self.merge:
-                    cv.winograd2_forward(s, self.wino3m[idx], epilogue=_lib.make_epilogue(bias=self.merged[idx][1], act="relu"), out=y)
+                    pm, bm = self.merged[idx]
+                    cv.conv3x3_forward(s, pm, epilogue=_lib.make_epilogue(bias=bm, act="relu"), out=y)
                     h = y
                     if idx in TAPS_AFTER:
                         taps.append(h)
                     continue
                 cv.conv_forward(s, p1, epilogue=_lib.make_epilogue(bias=b1, act="relu"), out=y, out_choff=0)
                 # Winograd when its grid (no split-K) fills the chip: the 25-candidate literal iteration, not a single small image
-                if idx in self.wino3 and min(s.shape[2:]) > 16 and cv.winograd_fills_chip(s.shape[0], ex, s.shape[2], s.shape[3]):
-                    cv.winograd2_forward(s, self.wino3[idx], epilogue=_lib.make_epilogue(bias=b3, act="relu"), out=y, out_choff=ex)
-                else:
-                    cv.conv_forward(s, p3, pad=(1, 1), epilogue=_lib.make_epilogue(bias=b3, act="relu"), out=y, out_choff=ex)
+                cv.conv3x3_forward(s, p3, epilogue=_lib.make_epilogue(bias=b3, act="relu"), out=y, out_choff=ex)
                 h = y
             if idx in TAPS_AFTER:
                 taps.append(h)

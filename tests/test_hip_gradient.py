@@ -417,7 +417,7 @@ def test_lpips_squeeze_gradient_with_winograd_data_gradients(monkeypatch):
     and GPU forwards at an arbitrary size, which says nothing about these kernels; test_lpips_gradient_matches_autograd pins the rest)."""
     from morphganformer_amd import conv as cv
     from morphganformer_amd.lpips import PerceptualLoss
-    monkeypatch.setattr(cv, "winograd_fills_chip", lambda *a: True)
+    monkeypatch.setattr(cv, "conv3x3_takes_winograd", lambda layer, n, h, w: layer.u is not None)      # Winograd wherever planes exist
     torch.manual_seed(11)
     n, size = 2, 140                                               # maps 69, 34, 17 (odd) and 8
     pred = torch.rand(n, 3, size, size, device="cuda") * 2 - 1
@@ -426,11 +426,18 @@ def test_lpips_squeeze_gradient_with_winograd_data_gradients(monkeypatch):
     out = torch.empty(n, device="cuda")
     pl.distance_into(out, pred, keep_taps=True)
     g_wino, g_taps = torch.empty_like(pred), torch.empty_like(pred)
+    wino3 = lambda recs: [r[0] for r in recs if r[0].startswith("wino3")]
+    cv.profile_begin()
     pl.grad_into(g_wino, scale=1.0)
+    assert len(wino3(cv.profile_end())) == 4                       # one expand-3x3 data gradient per Fire module that carries planes
     feat = pl._features(n, size, size)
-    assert sorted(feat.gpw) == [6, 7, 11, 12]                      # Fire modules with 32 / 64 squeeze channels
-    feat.gpw.clear()
+    e3T = {idx: t[2] for idx, t in feat.gp.items() if idx != "c0"}  # the expand-3x3 data-gradient layers (conv.Conv3x3)
+    assert sorted(idx for idx, layer in e3T.items() if layer.u is not None) == [6, 7, 11, 12]      # Fire modules with 32 / 64 squeeze channels
+    for layer in e3T.values():
+        layer.u = None
+    cv.profile_begin()
     pl.grad_into(g_taps, scale=1.0)
+    assert wino3(cv.profile_end()) == []
     assert float(g_taps.abs().max()) > 0 and rel(g_wino, g_taps) < 1e-5
 
 

@@ -665,6 +665,70 @@ def test_winograd3_half_resolution_residual(n, cin, cout, h, w):
     assert rel_err(out, two) < 2e-6
 
 
+@pytest.mark.parametrize("case", ["form1", "form3", "odd_slice", "small_map", "residual_low"])
+def test_conv3x3_entry_lands_on_each_leaf(case):
+    """conv.conv3x3_forward at the smallest shapes that reach each of its leaves, nothing patched: the launches it makes (read through the
+    conv profile) and its result, bit for bit, against the direct wrapper call it has to be -- the same kernel on the same arguments."""
+    from morphganformer_amd import _lib, conv as cv
+    planes, n, cin, cout, h, w, ctotal, choff = {"form1": (3, 64, 8, 512, 16, 16, 512, 0),        # 64 * 1 * 8 = 512 workgroups
+                                                 "form3": (4, 26, 4, 32, 18, 18, 32, 0),          # 26 * 5 * 1 * 1 = 130 >= WINOGRAD3_MIN_WGS
+                                                 "odd_slice": (4, 26, 4, 32, 17, 19, 96, 32),
+                                                 "small_map": (4, 26, 4, 32, 16, 16, 32, 0),
+                                                 "residual_low": (4, 26, 4, 32, 18, 18, 32, 0)}[case]
+    assert cv.WINOGRAD_FORM == 3 and cv.WINOGRAD3_MIN_WGS == 128
+    torch.manual_seed(h * w + cout)
+    r = lambda *s: torch.randn(*s, device="cuda")
+    x, wt, bias = r(n, cin, h, w), r(cout, cin, 3, 3) / (3 * cin ** 0.5), r(cout)
+    s, d = 1 + 0.3 * r(n, cin), 0.5 + torch.rand(n, cout, device="cuda")
+    low = r(n, cout, h // 2, w // 2) if case == "residual_low" else None
+    layer = cv.pack_conv3x3(wt, winograd=True, res=h if planes == 3 else None)
+    assert layer.u.ndim == planes and (layer.cin, layer.cout) == (cin, cout)
+    ep = _lib.make_epilogue(bias=bias, act="lrelu", alpha=0.2, gain=1.3)
+
+    def run(xx, lay, direct=None):
+        """-> (channels the call wrote, kernel names); the rest of the buffer must keep its canary."""
+        m = xx.shape[0]
+        out = torch.full((m, ctotal, h, w), 7.0, device="cuda")
+        kw = dict(in_scale=s[:m], out_scale=d[:m], epilogue=ep, out=out)
+        cv.profile_begin()
+        try:
+            if direct is None:
+                cv.conv3x3_forward(xx, lay, out_choff=choff, residual_low=None if low is None else low[:m], **kw)
+            else:
+                direct(xx, kw)
+        finally:
+            names = [rec[0] for rec in cv.profile_end()]
+        mask = torch.ones(ctotal, dtype=torch.bool, device="cuda")
+        mask[choff:choff + cout] = False
+        assert bool((out[:, mask] == 7.0).all())
+        return out[:, choff:choff + cout], names
+
+    taps = lambda xx, kw: cv.conv_forward(xx, layer.pc, pad=(1, 1), out_choff=choff, **kw)
+    if case == "form1":
+        wino = lambda xx, kw: cv.winograd_forward(xx, layer.u, **kw)
+    else:
+        wino = lambda xx, kw: cv.winograd2_forward(xx, layer.u, out_choff=choff, residual_low=None if low is None else low[:xx.shape[0]], **kw)
+    got, names = run(x, layer)
+    want, want_names = run(x, layer, taps if case == "small_map" else wino)
+    prefix = {"form1": "wino_conv_kernel", "small_map": "conv_taps_kernel"}.get(case, "wino3")
+    assert names[0].startswith(prefix) and names == want_names, (names, want_names)
+    assert torch.equal(got, want)
+    ref = torch.nn.functional.conv2d((x * s[:, :, None, None]).double(), wt.double(), padding=1) * d[:, :, None, None].double()
+    if low is None:                                                    # (the up-sampled skip has its own oracle test above)
+        ref = torch.nn.functional.leaky_relu(ref + bias.double()[None, :, None, None], 0.2) * 1.3
+        assert rel_err(got, ref) < 2e-5
+    if case in ("form1", "form3"):
+        # the same planes at one sample do not fill the chip: the tap list
+        got1, names1 = run(x[:1].contiguous(), layer)
+        want1, want_names1 = run(x[:1].contiguous(), layer, taps)
+        assert names1[0].startswith("conv_taps_kernel") and names1 == want_names1, (names1, want_names1)
+        assert torch.equal(got1, want1)
+    if case == "residual_low":
+        # without planes there is no launch that up-samples the skip: an error, not a result without it
+        with pytest.raises(AssertionError):
+            cv.conv3x3_forward(x, cv.Conv3x3(layer.pc), in_scale=s, out_scale=d, epilogue=ep, residual_low=low)
+
+
 @pytest.mark.parametrize("n,c,h,with_ep", [(8, 64, 128, True), (2, 32, 512, True), (4, 64, 256, False)])
 def test_fir_streaming_kernel_vs_float64(n, c, h, with_ep):
     """fir_up1_stream (csrc/upfirdn2d.hip): the blur after the transposed conv on wide maps -- upfirdn2d(t, f, padding 1, gain 4) of the
