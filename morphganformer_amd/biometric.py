@@ -5,7 +5,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, misc
 
 
 class BiometricLoss:
@@ -124,7 +124,7 @@ class BiometricLoss:
         if tuple(target_a.shape) != tuple(target_b.shape):
             raise ValueError(f"set_target_pair: the two targets differ in shape: {tuple(target_a.shape)} vs {tuple(target_b.shape)}")
         nt = int(target_a.shape[0])
-        al = np.asarray(alpha.detach().cpu() if isinstance(alpha, torch.Tensor) else alpha, dtype=np.float64).reshape(-1)
+        al = misc.as_numpy(alpha, np.float64).reshape(-1)
         if al.size not in (1, nt) or not np.all((al >= 0.0) & (al <= 1.0)):
             raise ValueError(f"set_target_pair: alpha must be one value or {nt} values in [0, 1] (got {alpha!r})")
         al = np.array(np.broadcast_to(al, (nt,)))

@@ -10,7 +10,7 @@
   lpips_map / save_lpips_map    the spatial LPIPS map of an image against a target (PNetLin(spatial=True), lpips/networks_basic.py:75-76) and its
                     .npy / gray .png files
   second_stage      a projection initialised from an earlier result (edit_MSE.py pattern, BASELINE config 5)
-  warp_morph        landmark-Delaunay warp of a morph onto the averaged landmarks (1024_warp_morphs.py:78-113,163-210)
+  warp_morphs       the 0.5 / 0.5 morph warped onto the averaged landmarks (1024_warp_morphs.py:128-210; the warp itself is `warp.py`, re-exported here)
 
 Every image is produced by the HIP generator (`engine.Generator`); there is no CPU path here.  Landmark detection (dlib) is a
 closed third-party CPU dependency: landmarks are passed in by the caller (projection.synthetic_landmarks stands in offline).
@@ -23,7 +23,10 @@ import numpy as np
 import torch
 
 from . import _lib, misc
-from .projection import GradientProjectionEngine, ProjectionArgs, ProjectionEngine, seeded_generator, seeded_latent_stats, seeded_randn
+from .projection import (GradientProjectionEngine, ProjectionArgs, ProjectionEngine, save_best_png, seeded_generator, seeded_latent_stats,
+                         seeded_randn)
+from .warp import (WARP_EXTRA_POINTS, _cv_affine_inverse, _cv_bounding_rect, _cv_fill_convex_poly, _cv_line8, _pack_warp_records,      # noqa: F401
+                   frame_points, gray_u8_device, warp_morph, warp_morph_u8, warp_plan)
 
 
 # ----------------------------------------------------------------------------------------------------------------- image I/O
@@ -69,9 +72,6 @@ def to_uint8_image(G, img):
     return misc.to_uint8(img)
 
 
-_crop_max_rectangle = misc.crop_max_rectangle        # (the reference's name lives in morphganformer_amd.misc)
-
-
 def save_image(G, img, path, ratio=1.0):
     """`crop(misc.to_pil(img[0]), ratio).save(path)` of the drivers (...sqz_MSE.py:190-195)."""
     im = misc.crop_max_rectangle(misc.to_pil(img), ratio)
@@ -89,11 +89,11 @@ def save_latent_mat(path, w, noises=None):
     """`{'w': float32 [1,k,D]}` in MATLAB v5 format, like sio.savemat in the drivers (:201-206).  noises: {layer name: map} of a
     projection that optimised the noise maps -- stored as [res, res] float32 arrays under noise_mat_key(name) beside 'w'."""
     import scipy.io as sio
-    w = np.asarray(w.detach().cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float32)
+    w = misc.as_numpy(w, np.float32)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     out = {"w": w}
     for name, t in (noises or {}).items():
-        m = np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t, dtype=np.float32)
+        m = misc.as_numpy(t, np.float32)
         out[noise_mat_key(name)] = m.reshape(m.shape[-2], m.shape[-1])
     sio.savemat(path, out)
     return path
@@ -138,11 +138,7 @@ def merge_morph(G, w1, w2, alphas=(0.5,), truncation_psi=0.7, noise_mode="random
     The blend is done in numpy float32 exactly like the reference (`0.5 * w1 + 0.5 * w2` on loadmat arrays).
     batched=True renders the whole sweep with ONE generator forward of len(alphas) images (BASELINE config 4's 11-alpha sweep as one
     batch-11 forward) instead of one forward per alpha like the script; the images agree to float32 rounding (other kernel shapes)."""
-    a1 = np.asarray(w1.detach().cpu() if isinstance(w1, torch.Tensor) else w1, dtype=np.float32)
-    a2 = np.asarray(w2.detach().cpu() if isinstance(w2, torch.Tensor) else w2, dtype=np.float32)
-    if a1.shape != a2.shape:
-        raise ValueError(f"merge_morph: the two latents differ in shape: {a1.shape} vs {a2.shape}")
-    blend = lambda a: _blend_latents(a1, a2, a)
+    _, blend = _latent_pair(w1, w2, "merge_morph")
     lat, imgs = [], []
     sweep = render_latent(G, np.concatenate([blend(a) for a in alphas]), truncation_psi, noise_mode) if batched and len(alphas) > 1 else None
     for j, a in enumerate(alphas):
@@ -160,6 +156,14 @@ def merge_morph(G, w1, w2, alphas=(0.5,), truncation_psi=0.7, noise_mode="random
 def _blend_latents(a1, a2, a):
     """merge_morph's latent blend in its float32 numpy arithmetic (`0.5 * w1 + 0.5 * w2` on loadmat arrays, 1024_merge_morph_2.py:83)."""
     return (0.5 * a1 + 0.5 * a2) if a == 0.5 else (np.float32(1.0 - a) * a1 + np.float32(a) * a2)
+
+
+def _latent_pair(w1, w2, who):
+    """The two latents of a morph (numpy or tensors) as float32 arrays of one shape -> (the first, alpha -> their blend)."""
+    a1, a2 = misc.as_numpy(w1, np.float32), misc.as_numpy(w2, np.float32)
+    if a1.shape != a2.shape:
+        raise ValueError(f"{who}: the two latents differ in shape: {a1.shape} vs {a2.shape}")
+    return a1, lambda a: _blend_latents(a1, a2, a)
 
 
 def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, args: ProjectionArgs = None, percept=None, biometric=None,
@@ -183,10 +187,7 @@ def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, ar
     similarities is one).  face_crop_filter: "area" or "bilinear"."""
     if mode != "gradient":
         raise ValueError(f"refine_morph descends the objective: mode must be 'gradient' (got {mode!r}; the literal loop never moves the latent)")
-    a1 = np.asarray(w1.detach().cpu() if isinstance(w1, torch.Tensor) else w1, dtype=np.float32)
-    a2 = np.asarray(w2.detach().cpu() if isinstance(w2, torch.Tensor) else w2, dtype=np.float32)
-    if a1.shape != a2.shape:
-        raise ValueError(f"refine_morph: the two latents differ in shape: {a1.shape} vs {a2.shape}")
+    a1, blend = _latent_pair(w1, w2, "refine_morph")
     if a1.ndim not in (3, 4) or a1.shape[0] != 1:
         raise ValueError(f"refine_morph: latents must be [1,k,D] or [1,k,num_ws,D] (got {a1.shape})")
     alphas = [float(a) for a in alphas]
@@ -194,10 +195,9 @@ def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, ar
         raise ValueError(f"refine_morph: alphas must lie in [0, 1] (got {alphas})")
     if tuple(target_a.shape) != tuple(target_b.shape) or target_a.shape[0] != 1:
         raise ValueError(f"refine_morph: target_a and target_b must both be [1,3,S,S] (got {tuple(target_a.shape)} and {tuple(target_b.shape)})")
-    from .projection import save_best_png
     args = args or ProjectionArgs()
     space = "w+" if a1.ndim == 4 else "z"
-    starts = [_blend_latents(a1, a2, a) for a in alphas]
+    starts = [blend(a) for a in alphas]
     B = len(alphas)
     dev = G.device
     if latent_std is None:
@@ -318,7 +318,7 @@ def arcface_crop(landmarks, size=112):
     points.  landmarks: [5,2] (x, y) -- left eye, right eye, nose tip, left and right mouth corner as the image shows them -- or the [68,2]
     set of the Wing term, of which the eye centres mean(36:42) and mean(42:48), the nose tip 30 and the mouth corners 48 and 54 are taken.
     Host only."""
-    pts = np.asarray(landmarks.detach().cpu().numpy() if isinstance(landmarks, torch.Tensor) else landmarks, dtype=np.float64)
+    pts = misc.as_numpy(landmarks, np.float64)
     if pts.shape == (68, 2):
         pts = np.stack([pts[36:42].mean(0), pts[42:48].mean(0), pts[30], pts[48], pts[54]])
     if pts.shape != (5, 2) or not np.all(np.isfinite(pts)):
@@ -336,7 +336,7 @@ def arcface_crop(landmarks, size=112):
 def scale_crop(M, f):
     """M re-expressed for the image block-averaged by f (ProjectionArgs.pool_above): pixel index x of the image is index x' = (x + 1/2) / f - 1/2
     of the pooled one (pixel centres; a block's mean sits at the block's centre).  M [2,3] or [n,2,3] -> float64 of the same shape."""
-    M = np.array(M.detach().cpu().numpy() if isinstance(M, torch.Tensor) else M, dtype=np.float64)
+    M = np.array(misc.as_numpy(M), dtype=np.float64)         # (a copy: the caller's matrix stays as it is)
     M[..., :, :2] /= float(f)
     M[..., :, 2] = (M[..., :, 2] + 0.5) / float(f) - 0.5
     return M
@@ -349,9 +349,9 @@ def _resolve_crop(face_crop, landmarks, what):
             raise ValueError(f"{what} must be a [2,3] matrix or 'landmarks' (got {face_crop!r})")
         if landmarks is None:
             raise ValueError(f"{what}='landmarks' needs the landmarks it is derived from")
-        lm = np.asarray(landmarks.detach().cpu().numpy() if isinstance(landmarks, torch.Tensor) else landmarks, dtype=np.float64)
+        lm = misc.as_numpy(landmarks, np.float64)
         return arcface_crop(lm) if lm.ndim == 2 else np.stack([arcface_crop(l) for l in lm])
-    return np.asarray(face_crop.detach().cpu().numpy() if isinstance(face_crop, torch.Tensor) else face_crop, dtype=np.float64)
+    return misc.as_numpy(face_crop, np.float64)
 
 
 def face_region_weight(landmarks, size, inside=1.0, outside=0.0, feather=0.0):
@@ -400,7 +400,7 @@ def save_lpips_map(map, path, vmax=None):
     """`path + '.npy'`: the map as float32 [H,W]; `path + '.png'`: gray uint8 round(255 * min(map / vmax, 1)), vmax = the map's maximum
     unless given (an all-zero map gives an all-zero PNG).  map: [1,1,H,W] / [H,W], tensor or array.  Returns the two paths."""
     from PIL import Image
-    m = np.asarray(map.detach().cpu() if isinstance(map, torch.Tensor) else map, dtype=np.float32)
+    m = misc.as_numpy(map, np.float32)
     m = m.reshape(m.shape[-2], m.shape[-1])
     top = float(m.max()) if vmax is None else float(vmax)
     scaled = np.minimum(m.astype(np.float64) / top, 1.0) if top > 0 else np.zeros(m.shape)
@@ -499,9 +499,9 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
         if biometric is None:
             raise ValueError("face_crop is the crop of the biometric term: pass biometric= with it")
         crop = _resolve_crop(face_crop, lm_target, "face_crop")
-        r, pa = G.img_resolution, args.pool_above
-        if pa and r > pa and r // pa > 1:
-            crop = scale_crop(crop, r // pa)
+        f = args.pool_factor(G.img_resolution)
+        if f > 1:
+            crop = scale_crop(crop, f)
     if latent_mean is None or latent_std is None:
         latent_mean, latent_std = seeded_latent_stats(G, args, latent_space, seed)
     if pipeline is None:
@@ -545,13 +545,11 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     if out_prefix is not None:
         save_latent_mat(f"{out_prefix}.mat", w, noises=best_noises)
         if path_to_gen is None:                      # no improvement trail asked for: still leave an image of the result beside the latent
-            from .projection import save_best_png
             out["image"] = save_best_png(G, w, f"{out_prefix}.png", args.ratio, noises=best_noises)
     if path_to_gen is not None:
         if mode == "literal":
             out["images"] = eng.save_improvements(path_to_gen, args.ratio)
         else:
-            from .projection import save_best_png
             out["images"] = [save_best_png(G, w, os.path.join(path_to_gen, "{:06d}_{:04f}.png".format(step, loss)), args.ratio, noises=best_noises)]
     if lpips_map:
         out["lpips_map"] = _best_lpips_map(G, percept, w, target, best_noises)
@@ -586,8 +584,7 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_w
     on = dist.is_available() and dist.is_initialized()
     rank, world = (dist.get_rank(), dist.get_world_size()) if on else (0, 1)
     # an item is a device tensor, an image path, or a callable that produces the tensor when the item is taken (a rank only ever touches its own)
-    pa = getattr(kw.get("args"), "pool_above", 0) or 0           # (projection_example_v1.py: the target at the size the losses see)
-    tsize = G.img_resolution // (G.img_resolution // pa) if (pa and G.img_resolution > pa) else G.img_resolution
+    tsize = G.img_resolution // (kw.get("args") or ProjectionArgs()).pool_factor(G.img_resolution)       # (projection_example_v1.py: the losses' size)
     load = lambda t: t if isinstance(t, torch.Tensor) else (t() if callable(t) else image_transform(t, size=tsize, device=G.device))
     w_plus = kw.get("latent_space", "z") == "w+"
     lshape = (G.cfg.k, G.cfg.num_ws, G.cfg.w_dim) if w_plus else (G.cfg.k, G.cfg.z_dim)      # a W+ result is [k, num_ws, D] per item
@@ -699,7 +696,7 @@ def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=N
         latent_mean, latent_std = seeded_latent_stats(G, args, latent_space, seed)
     tg = torch.cat([t.reshape(1, *t.shape[-3:]) for t in targets]).contiguous()
     if region_weight is not None:                   # one map per target of the group
-        region_weight = torch.stack([torch.as_tensor(np.asarray(w.detach().cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float64)).reshape(
+        region_weight = torch.stack([torch.as_tensor(misc.as_numpy(w, np.float64)).reshape(
             tg.shape[-2], tg.shape[-1]) for w in region_weight])[:, None]
     lm_t = lm_s = None
     if landmarks is not None:
@@ -720,216 +717,6 @@ def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=N
     return {"w": w, "step": step, "loss": loss, "losses": losses}
 
 
-# the 12 frame points the reference adds to the 68 landmarks before triangulating (1024_warp_morphs.py:130-132)
-WARP_EXTRA_POINTS = [[0, 0], [0, 341], [0, 682], [0, 1023], [341, 0], [682, 0], [1023, 0], [1023, 341], [1023, 682], [1023, 1023],
-                     [341, 1023], [682, 1023]]
-
-
-# ---- host set-up of the warp: the OpenCV calls of morphTriangle that are integer / 6x6 control work, restated from OpenCV's published sources
-# (4.x: imgproc/src/shapedescr.cpp pointSetBoundingRect, imgwarp.cpp getAffineTransform / warpAffine, core LUImpl, drawing.cpp fillConvexPoly /
-# FillConvexPoly / Line / LineIterator) in closed form; the per-pixel work is the device kernel's (csrc/warp.hip)
-_XY_SHIFT = 16
-
-
-def _cv_bounding_rect(tri):
-    """cv2.boundingRect(np.float32([tri])): floor of the float32 extremes, both ends included."""
-    p = np.asarray(tri, np.float32)
-    lo, hi = np.floor(p.min(0)).astype(np.int64), np.floor(p.max(0)).astype(np.int64)
-    return int(lo[0]), int(lo[1]), int(hi[0] - lo[0] + 1), int(hi[1] - lo[1] + 1)
-
-
-def _cv_affine_inverse(src_tri, dst_tri):
-    """cv2.getAffineTransform(np.float32(src), np.float32(dst)) -- the 6x6 system solved by Gaussian elimination with partial pivoting in
-    double (core LUImpl), whole rows at a time -- followed by warpAffine's inversion of the matrix (no WARP_INVERSE_MAP).  -> iM [6]."""
-    s, d = np.asarray(src_tri, np.float32).astype(np.float64), np.asarray(dst_tri, np.float32).astype(np.float64)
-    a = np.zeros((6, 7))
-    a[0::2, 0:2], a[0::2, 2], a[1::2, 3:5], a[1::2, 5] = s, 1.0, s, 1.0
-    a[0::2, 6], a[1::2, 6] = d[:, 0], d[:, 1]
-    singular = False
-    for i in range(6):
-        k = i + int(np.argmax(np.abs(a[i:, i])))              # first maximum, like the `>` scan
-        if abs(a[k, i]) < np.finfo(np.float64).eps * 100:     # LU64f's threshold: cv::solve then returns false and zeroes X,
-            singular = True                                   # getAffineTransform does not look at the result -- a collinear source
-            break                                             # triangle gets the all-zero matrix, and warpAffine's inverse of it is zero
-        if k != i:
-            a[[i, k], i:] = a[[k, i], i:]
-        alpha = a[i + 1:, i] * (-1.0 / a[i, i])
-        a[i + 1:, i + 1:] += alpha[:, None] * a[i, i + 1:][None, :]
-    x = np.zeros(6)
-    for i in range(5, -1, -1):
-        if singular:
-            break
-        acc = a[i, 6]
-        for k in range(i + 1, 6):
-            acc -= a[i, k] * x[k]
-        x[i] = acc / a[i, i]
-    m = x.copy()
-    det = m[0] * m[4] - m[1] * m[3]
-    det = 1.0 / det if det != 0 else 0.0
-    a11, a22 = m[4] * det, m[0] * det
-    m[0], m[1], m[3], m[4] = a11, m[1] * -det, m[3] * -det, a22
-    b1 = -m[0] * m[2] - m[1] * m[5]
-    b2 = -m[3] * m[2] - m[4] * m[5]
-    m[2], m[5] = b1, b2
-    return m
-
-
-def _cv_line8(p, q):
-    """Pixels of Line(img, p, q, color, 8): LineIterator(connectivity 8, left_to_right) in closed form -- step k of the major axis has made
-    (2 dy k + dx - 1) // (2 dx) minor steps (the iterator's error term steps when the ideal minor coordinate exceeds the current one by MORE
-    than one half)."""
-    (x1, y1), (x2, y2) = (int(p[0]), int(p[1])), (int(q[0]), int(q[1]))
-    if x2 < x1:
-        x1, y1, x2, y2 = x2, y2, x1, y1
-    dx, dy = x2 - x1, y2 - y1
-    ys = -1 if dy < 0 else 1
-    dy = abs(dy)
-    steep = dy > dx
-    major, minor = (dy, dx) if steep else (dx, dy)
-    k = np.arange(major + 1, dtype=np.int64)
-    m = (2 * minor * k + major - 1) // (2 * major) if major > 0 else np.zeros(1, np.int64)
-    return (x1 + m, y1 + ys * k) if steep else (x1 + k, y1 + ys * m)
-
-
-def _cv_fill_convex_poly(height, width, pts):
-    """bool mask [height, width] of the pixels cv2.fillConvexPoly(mask, np.int32(pts), color, lineType=16, shift=0) writes on a non-8U image
-    (LINE_AA falls back to 8-connected there): the Bresenham outline plus FillConvexPoly's scanline spans.  The two edge walkers advance by a
-    constant 16.16 step between vertex rows, so every run of rows between two vertex events is filled at once."""
-    v = [(int(a), int(b)) for a, b in pts]
-    n = len(v)
-    mask = np.zeros((height, width), bool)
-    for i in range(n):
-        xs, ys = _cv_line8(v[i - 1], v[i])
-        mask[ys, xs] = True
-    ymin, ymax = min(p[1] for p in v), max(p[1] for p in v)
-    imin = min(range(n), key=lambda i: (v[i][1], i))
-    if n < 3 or max(p[0] for p in v) < 0 or ymax < 0 or min(p[0] for p in v) >= width or ymin >= height:
-        return mask
-    ymax = min(ymax, height - 1)
-    ed = [[imin, 1, -(1 << _XY_SHIFT), 0, ymin], [imin, n - 1, -(1 << _XY_SHIFT), 0, ymin]]         # idx, di, x, dx, ye
-    edges, y = n, ymin
-    cols = np.arange(width)
-    while y <= ymax:
-        for e in ed:
-            if y >= e[4]:
-                idx0, idx = e[0], (e[0] + e[1]) % n
-                while True:
-                    edges -= 1
-                    if edges < 0:
-                        break
-                    ty = v[idx][1]
-                    if ty > y:
-                        xs, xe = v[idx0][0] << _XY_SHIFT, v[idx][0] << _XY_SHIFT
-                        num, den = (xe - xs) * 2 + (ty - y), 2 * (ty - y)
-                        e[0], e[2], e[3], e[4] = idx, xs, (abs(num) // den) * (1 if num >= 0 else -1), ty      # C division: toward zero
-                        break
-                    idx0, idx = idx, (idx + e[1]) % n
-        if edges < 0:
-            break
-        y_next = min(ed[0][4], ed[1][4], ymax + 1)              # rows [y, y_next): both walkers keep their step
-        y_next = max(y_next, y + 1)
-        k = np.arange(y_next - y, dtype=np.int64)
-        xa, xb = ed[0][2] + k * ed[0][3], ed[1][2] + k * ed[1][3]
-        lo, hi = np.minimum(xa, xb), np.maximum(xa, xb)
-        xx1, xx2 = (lo + (1 << 15)) >> _XY_SHIFT, (hi + (1 << 15)) >> _XY_SHIFT
-        rows = np.arange(y, y_next)
-        ok = (rows >= 0) & (xx2 >= 0) & (xx1 < width)
-        span = (cols[None, :] >= np.maximum(xx1, 0)[:, None]) & (cols[None, :] <= np.minimum(xx2, width - 1)[:, None]) & ok[:, None]
-        mask[rows[ok]] |= span[ok]
-        steps = y_next - y
-        ed[0][2] += steps * ed[0][3]
-        ed[1][2] += steps * ed[1][3]
-        y = y_next
-    return mask
-
-
-def warp_plan(points_src, points_dst, height, width):
-    """Host side of the Delaunay warp (1024_warp_morphs.py:163-203): triangulate the DESTINATION points with scipy (as the script does) and,
-    per triangle in list order, do what morphTriangle does before any pixel is touched -- the two bounding rectangles, the fillConvexPoly
-    mask of np.int32(tRect), cv2.getAffineTransform(np.float32(t1Rect), np.float32(tRect)) inverted as warpAffine inverts it.
-    Returns (label int32 [height, width]: the triangle that writes each pixel LAST, -1 = none; records: one per triangle -- iM [6] float64,
-    destination patch origin, source patch origin and size; simplices)."""
-    from scipy.spatial import Delaunay
-    ps, pd = np.asarray(points_src, np.float64), np.asarray(points_dst, np.float64)
-    simplices = Delaunay(pd).simplices
-    label = np.full((height, width), -1, np.int32)
-    recs = []
-    for t, idx in enumerate(simplices):
-        tg, ta = ps[idx], pd[idx]
-        r1, r = _cv_bounding_rect(tg), _cv_bounding_rect(ta)
-        if r[0] < 0 or r[1] < 0 or r[0] + r[2] > width or r[1] + r[3] > height or r1[0] < 0 or r1[1] < 0:
-            raise ValueError("warp: mesh points must lie inside the image (the script's numpy slices would not line up otherwise)")
-        t_rect, t1_rect = ta - np.array(r[:2], np.float64), tg - np.array(r1[:2], np.float64)
-        sw, sh = min(r1[0] + r1[2], width) - r1[0], min(r1[1] + r1[3], height) - r1[1]       # img_G[r1.y : r1.y + r1.h, ...]: numpy clips the slice
-        if sw < 1 or sh < 1:
-            raise ValueError("warp: a source triangle lies outside the image")
-        m = _cv_fill_convex_poly(r[3], r[2], np.int32(t_rect))
-        view = label[r[1]:r[1] + r[3], r[0]:r[0] + r[2]]
-        view[m] = t
-        recs.append((_cv_affine_inverse(np.float32(t1_rect), np.float32(t_rect)), r[0], r[1], r1[0], r1[1], sw, sh))
-    return label, recs, simplices
-
-
-def _pack_warp_records(recs):
-    """The device records of mgf_cv_warp_triangles_f32: { double im[6]; int32 dx, dy, sx, sy, sw, sh }."""
-    size = int(_lib.lib().mgf_cv_warp_triangle_bytes())
-    dt = np.dtype([("im", np.float64, 6), ("geo", np.int32, 6)])
-    assert dt.itemsize == size, (dt.itemsize, size)
-    arr = np.zeros(len(recs), dt)
-    for i, (im, *geo) in enumerate(recs):
-        arr["im"][i], arr["geo"][i] = im, geo
-    return arr
-
-
-def warp_morph(img, points_G, points_avg, background=0.0):
-    """Warp the generated morph so that its landmarks `points_G` land on the averaged landmarks `points_avg` (both [P,2] in pixel
-    coordinates, frame points included): the post-process of 1024_warp_morphs.py:163-210, every pixel computed as OpenCV computes it
-    (fixed-point 1/32-pixel coordinates, float weight table, BORDER_REFLECT_101 at the triangle's source patch, fillConvexPoly's pixel set).
-    img: [1,C,H,W] or [C,H,W] float32 device tensor in ANY value range -- the script works on the 0..255 float BGR image it reads back from
-    the PNG, for which every step is exact; returns imgMorph, a tensor of the same shape (`warp_morph_u8` gives the bytes the script writes)."""
-    _lib.require_gpu(img)
-    x = img.reshape(-1, *img.shape[-2:]).contiguous().float()
-    c, h, w = x.shape
-    label, recs, _ = warp_plan(points_G, points_avg, h, w)
-    dev = x.device
-    lab_d = torch.as_tensor(label, device=dev).contiguous()
-    rec_d = torch.as_tensor(_pack_warp_records(recs).view(np.uint8).reshape(-1), device=dev).contiguous()
-    out = torch.empty_like(x)
-    _lib.check(_lib.lib().mgf_cv_warp_triangles_f32(out.data_ptr(), x.data_ptr(), lab_d.data_ptr(), rec_d.data_ptr(), len(recs), c, h, w,
-                                                    float(background), _lib.stream_ptr()), "cv_warp_triangles")
-    return out.reshape(img.shape)
-
-
-def warp_morph_u8(img_u8_hwc, points_G, points_avg):
-    """uint8 [H,W,C] in -> uint8 [H,W,C] out, what the script does between cv2.imread and cv2.imwrite (:186-207): np.float32(image), the
-    triangle loop, np.uint8(imgMorph) (truncation)."""
-    a = np.asarray(img_u8_hwc)
-    assert a.dtype == np.uint8 and a.ndim == 3
-    x = torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1))).to("cuda").float()
-    out = warp_morph(x, points_G, points_avg)
-    return out.to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()           # values in [0, 255]: the cast truncates like np.uint8
-
-
-def frame_points(size: int):
-    """The 12 frame points of 1024_warp_morphs.py:130-132 for a `size` x `size` image (0, 341, 682, 1023 at 1024)."""
-    q = [(size - 1) * i // 3 for i in range(4)]
-    return [[q[0], q[0]], [q[0], q[1]], [q[0], q[2]], [q[0], q[3]], [q[1], q[0]], [q[2], q[0]], [q[3], q[0]], [q[3], q[1]], [q[3], q[2]],
-            [q[3], q[3]], [q[1], q[3]], [q[2], q[3]]]
-
-
-def gray_u8_device(img):
-    """[n,3,H,W] float32 device images -> [n,H,W] uint8 numpy: the gray image `get_landmarks_G` hands to dlib (1024_warp_morphs.py:61-66,
-    the same two cv2 calls as the projection drivers), made on the device (mgf_reference_gray_u8)."""
-    _lib.require_gpu(img)
-    x = img.contiguous().float()
-    n, c, h, w = x.shape
-    assert c == 3
-    out = torch.empty(n, h, w, dtype=torch.uint8, device=x.device)
-    scratch = torch.empty(n * int(_lib.lib().mgf_reference_gray_scratch_floats()), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().mgf_reference_gray_u8(out.data_ptr(), x.data_ptr(), n, h, w, scratch.data_ptr(), _lib.stream_ptr()), "reference_gray_u8")
-    return out.cpu().numpy()
-
-
 def warp_morphs(G, w1, w2, landmark1, landmark2, landmark_G=None, landmark_fn=None, out_dir=None, truncation_psi=0.7, noise_mode="random"):
     """The whole of 1024_warp_morphs.py's main (:128-210): the 0.5 / 0.5 latent morph rendered with `G(W, truncation_psi)` (:153-156),
     the averaged landmarks of the two bona fide images + the 12 frame points triangulated (scipy Delaunay, :160-164), the morph's own
@@ -948,7 +735,7 @@ def warp_morphs(G, w1, w2, landmark1, landmark2, landmark_G=None, landmark_fn=No
         landmark_G = landmark_fn(gray_u8_device(img)[0])
         if landmark_G is None:                              # (the script would fail on `None.detach()` two lines later)
             raise _lib.MgfError("warp_morphs: the detector found no face in the morph")
-    l1, l2, lg = (np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64).reshape(-1, 2) for v in (landmark1, landmark2, landmark_G))
+    l1, l2, lg = (misc.as_numpy(v, np.float64).reshape(-1, 2) for v in (landmark1, landmark2, landmark_G))
     if not (l1.shape == l2.shape == lg.shape):
         raise ValueError(f"warp_morphs: landmark sets differ in shape: {l1.shape}, {l2.shape}, {lg.shape}")
     extra = np.asarray(frame_points(size), dtype=np.float64)
@@ -995,6 +782,6 @@ def facenet_feature(image_u8_hwc, embedder):
 def second_stage(G, target, w_init, latent_std, lm_target, lm_steps, **kw):
     """A second projection whose noisy candidates are drawn around an earlier result instead of the latent mean
     (edit_MSE.py: `latent_in = w1` pattern; BASELINE config 5)."""
-    w0 = torch.as_tensor(np.asarray(w_init.detach().cpu() if isinstance(w_init, torch.Tensor) else w_init, dtype=np.float32))
+    w0 = torch.as_tensor(misc.as_numpy(w_init, np.float32))
     return project_image(G, target, lm_target, lm_steps, latent_mean=w0.reshape(w0.shape[-2:]).to(G.device),
                          latent_std=latent_std, **kw)

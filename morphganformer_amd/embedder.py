@@ -6,11 +6,11 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, misc
 
 
 def np64(v):
-    return (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float64)
+    return misc.as_numpy(v).astype(np.float64)
 
 
 def bn_affine(sd, name, eps):

@@ -5,7 +5,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, misc
 from .projection import ProjectionArgs, ProjectionEngine, _wing_into, get_lr, seeded_randn
 from .trail import ImprovementSlot
 
@@ -139,7 +139,7 @@ class GradientProjectionEngine(ProjectionEngine):
         if tuple(target_b.shape) != tuple(target.shape):
             raise ValueError(f"GradientProjectionEngine: target and target_b do not pair up: {tuple(target.shape)} vs {tuple(target_b.shape)}")
         B = int(target.shape[0])
-        al = np.asarray(morph_alpha.detach().cpu() if isinstance(morph_alpha, torch.Tensor) else morph_alpha, dtype=np.float64).reshape(-1)
+        al = misc.as_numpy(morph_alpha, np.float64).reshape(-1)
         if al.size not in (1, B):
             raise ValueError(f"GradientProjectionEngine: morph_alpha must be one value or one per pair ({B}), got {al.size}")
         if not np.all((al >= 0.0) & (al <= 1.0)):

@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, misc
 from . import lpips_backbones as backbones          # the switches are read through the module (tests and tools set them there)
 from .lpips_backbones import (ALEX_SPEC, CHNS, FIRES, NET_CHNS, POOLS, SCALE, SHIFT, SPECS, TAPS_AFTER, VGG_SPEC,  # noqa: F401 (re-exported)
                               SequentialFeatures, SqueezeFeatures, _pool_out, load_backbone_state, random_backbone, random_squeeze_backbone)
@@ -219,7 +219,7 @@ class PerceptualLoss(torch.nn.Module):
         if tuple(target_a.shape) != tuple(target_b.shape):
             raise ValueError(f"set_target_pair: the two targets differ in shape: {tuple(target_a.shape)} vs {tuple(target_b.shape)}")
         n = int(target_a.shape[0])
-        al = np.asarray(alpha.detach().cpu() if isinstance(alpha, torch.Tensor) else alpha, dtype=np.float64).reshape(-1)
+        al = misc.as_numpy(alpha, np.float64).reshape(-1)
         if al.size not in (1, n) or not np.all((al >= 0.0) & (al <= 1.0)):
             raise ValueError(f"set_target_pair: alpha must be one value or {n} values in [0, 1] (got {alpha!r})")
         al = np.array(np.broadcast_to(al, (n,)))

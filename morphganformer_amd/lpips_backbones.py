@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, misc
 from . import conv as cv
 
 FIRES = {3: (64, 16, 64), 4: (128, 16, 64), 6: (128, 32, 128), 7: (256, 32, 128),
@@ -93,8 +93,7 @@ def load_backbone_state(path):
         raw = torch.load(path, map_location="cpu", weights_only=True)
         if "state_dict" in raw and not any(k.startswith("features.") for k in raw):
             raw = raw["state_dict"]
-    out = {k: np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float32)
-           for k, v in raw.items() if k.startswith("features.")}
+    out = {k: misc.as_numpy(v, np.float32) for k, v in raw.items() if k.startswith("features.")}
     if not out:
         raise _lib.MgfError(f"{path}: no `features.*` entries (expected a torchvision squeezenet1_1 / vgg16 / alexnet state dict)")
     return out

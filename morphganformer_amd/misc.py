@@ -14,6 +14,12 @@ import torch
 from . import _lib
 
 
+def as_numpy(x, dtype=None):
+    """A tensor (any device, with or without grad) or anything array-like -> numpy array of `dtype` (None: its own).  `np.asarray` semantics:
+    no copy where none is needed -- a CPU tensor or an array that already has the dtype comes back as a view of the same memory."""
+    return np.asarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=dtype)
+
+
 def crop_center(img, cw, ch):
     """misc.py:88-90."""
     w, h = img.size

@@ -92,6 +92,10 @@ class ProjectionArgs:
         if self.pixel_term == "msssim" and not (isinstance(self.msssim_levels, int) and 1 <= self.msssim_levels <= len(MSSSIM_WEIGHTS)):
             raise _lib.MgfError(f"projection: msssim_levels must be an integer in 1..{len(MSSSIM_WEIGHTS)} (got {self.msssim_levels!r})")
 
+    def pool_factor(self, resolution):
+        """The block side `pool_above` averages a resolution x resolution image by (1 = not pooled): the losses see resolution // factor pixels."""
+        return resolution // self.pool_above if self.pool_above and resolution > self.pool_above else 1
+
 
 def get_lr(t, initial_lr, rampdown=0.25, rampup=0.05):
     """Learning-rate schedule of the drivers (:63-68).  Inert in literal mode (the optimizer never sees a gradient)."""
@@ -420,7 +424,7 @@ class ProjectionEngine:
         image-space losses; the target comes at the pooled size."""
         a, G = self.args, self.G
         r = G.cfg.img_resolution
-        self.pool_factor = r // a.pool_above if (a.pool_above and r > a.pool_above) else 1
+        self.pool_factor = a.pool_factor(r)
         want = r // self.pool_factor
         if tuple(self.target.shape[-2:]) != (want, want):
             raise _lib.MgfError(f"projection: the target is {tuple(self.target.shape[-2:])}, the image-space losses see {want}x{want} "
