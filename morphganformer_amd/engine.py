@@ -36,6 +36,21 @@ WINOGRAD_MAX_RES = int(os.environ.get("MGF_WINOGRAD_MAX_RES", "1024"))
 # -231 us, 128^2 -175, 256^2 -156 against the tap-list launch; 512^2 at parity (-12), 1024^2 +524 -- the shallow-K layers keep the tap list)
 TCONV_WINO_MAX_RES = int(os.environ.get("MGF_TCONV_WINO_MAX_RES", "256"))
 BF_DIRECT_MAX_RES = int(os.environ.get("MGF_BF_DIRECT_MAX_RES", "128"))     # arith="bf16x3": largest map whose 3x3 layers leave Winograd (tuning hook)
+MAX_LOCAL_LATENTS = 16        # TMAX of csrc/attention.hip and csrc/backward.hip: the attention kernels keep one score per latent in 16 registers
+LATENT_WIDTH = 32             # MD of csrc/latent_prep.hip: the mapping kernel is built for this latent width
+
+
+def check_supported(cfg: GeneratorConfig) -> None:
+    """Refuse a configuration the kernels do not take, naming the limit.  The C entries refuse it too, but only in the middle of the first
+    forward, after the plan has been uploaded and the workspaces sized."""
+    if cfg.k < 2:
+        raise _lib.MgfError(f"Generator: k must be at least 2, one local latent component and the global one (got k={cfg.k})")
+    if cfg.w_dim != LATENT_WIDTH or cfg.z_dim != LATENT_WIDTH:
+        raise _lib.MgfError(f"Generator: the mapping kernel is built for a latent width of {LATENT_WIDTH} "
+                            f"(got z_dim={cfg.z_dim}, w_dim={cfg.w_dim})")
+    if cfg.k - 1 > MAX_LOCAL_LATENTS and any(cfg.has_attention(res) for res in cfg.block_resolutions):
+        raise _lib.MgfError(f"Generator: the attention kernels take at most {MAX_LOCAL_LATENTS} local latent components, "
+                            f"k <= {MAX_LOCAL_LATENTS + 1} (got k={cfg.k})")
 
 
 def pack_mapping_params(sd, cfg: GeneratorConfig) -> np.ndarray:
@@ -244,6 +259,7 @@ class Generator:
         error 4 - 5e-6 of the output's range instead of 1e-6, ~2x the matrix rate).  Everything else is unchanged."""
         if arith not in ("f32", "bf16x3"):
             raise ValueError(f"arith must be 'f32' or 'bf16x3' (got {arith!r})")
+        check_supported(cfg)                                       # before the plan is uploaded and any workspace is sized
         self.cfg = cfg
         self.arith = arith
         self.tpitch_align = 32 if arith == "bf16x3" else 4         # transposed-conv workspace rows on 128-byte lines in the bf16x3 mode (conv.tconv_pitch)
