@@ -282,6 +282,9 @@ int mgf_pack_conv_weights(float* wp, float* wsq, const float* w, int32_t cout, i
  *   d[n, co] = rsqrt( sum_ci wsq[co, ci] * s[n, ci]^2 + 1e-8 )                   (if wsq and d are non-NULL)
  * wsq comes from mgf_pack_conv_weights.  The _multi form takes a DEVICE array of jobs (one launch for all layers); max_cin = the
  * largest job cin if the caller knows it (lets one workgroup serve all n <= 32 samples and read each wsq table once), else 0.
+ * A job's styles are staged in 2048 floats of LDS: mgf_style_demod refuses cin > 2048 and the _multi form max_cin > 2048, but the job
+ * table is device memory the entry cannot read -- with max_cin = 0 (or a max_cin below a job's cin) keeping every job's cin <= 2048 is
+ * left to the caller.
  */
 typedef struct mgf_style_job {
     const float* aff_w;   /* [cin, wdim] */
@@ -660,7 +663,10 @@ int mgf_attn_values_grad_ws(float* dvwb, const float* dg, const float* probs, in
  *   ds[i]  = sum_chunks ds_part[n,i,:] - s[n,i] * sum_o (sum_chunks dc_part[n,o,:]) d[n,o]^2 wsq[o,i]      (second term only with demod)
  *   dwg[n, job, k] = aff_gain * style_gain * sum_i ds[i] * aff_w[i, k]          gradient wrt the global latent component
  * attn_values_bwd_multi: dyc[n, job, t, k] = sum_c dvwb[n,c,t] * wmv[c,k]       gradient wrt the local latent components
- * latent_grad_gather:    dw[n, t < k-1, :] = scale * sum_jobs dyc,  dw[n, k-1, :] = scale * sum_jobs dwg      (w layout [n, k, wdim]) */
+ * latent_grad_gather:    dw[n, t < k-1, :] = scale * sum_jobs dyc,  dw[n, k-1, :] = scale * sum_jobs dwg      (w layout [n, k, wdim])
+ * mgf_style_bwd_job.wsq is read 16 bytes at a time when cin % 4 == 0 and cin / 4 divides 256 (cin = 4, 8, ..., 1024) and must then be
+ * 16-byte aligned -- what mgf_pack_conv_weights writes into a 16-byte aligned buffer is; the entries do not check it (the job table is
+ * device memory).  Demodulation is off for a job in which any of wsq, d, dc_part is NULL. */
 typedef struct mgf_style_bwd_job {
     const float* aff_w;    /* [cin, wdim] */
     const float* wsq;      /* [cout, cin] or NULL */

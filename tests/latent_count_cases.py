@@ -85,7 +85,8 @@ LATENT_WDIM, LATENT_N = 32, 2
 
 
 def latent_side_inputs(T, cs, wdim=LATENT_WDIM, n=LATENT_N):
-    """Two attention jobs (channels cs) and two style jobs (no demodulation) of one latent-side launch, float64."""
+    """Two attention jobs (channels cs) and two style jobs (no demodulation: tests/style_demod_cases.py has the demodulated ones) of one
+    latent-side launch, float64."""
     torch.manual_seed(500 + 10 * T + sum(cs))
     d = torch.float64
     k = T + 1

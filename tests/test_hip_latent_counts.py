@@ -5,7 +5,7 @@ latent and take the register-resident / MFMA forms.  T < 16 is another path thro
 csrc/latent_prep.hip) and other strides in every buffer engine.py / grad.py derive from cfg.k.  Part 1 calls the C entries directly
 against the float64 formulas of tests/latent_count_cases.py; part 2 runs whole generators against the CPU oracle.
 
-Direct calls hand the kernels GUARDED buffers: an operand lies at the head of a larger NaN-filled allocation (a read with a wrong stride
+Direct calls hand the kernels GUARDED buffers (tests/guarded_buffers.py): an operand lies at the head of a larger NaN-filled allocation (a read with a wrong stride
 pulls NaN into the result instead of a neighbour's plausible numbers, and stays inside the allocation), an output is NaN before the call and
 is followed by a NaN guard that must still be NaN after it (a write with a wrong stride either leaves NaN inside or lands in the guard).
 
@@ -19,49 +19,13 @@ import pytest
 import torch
 
 import latent_count_cases as lc
+from guarded_buffers import NAN, Guarded, device_table as _device_table, g_in, g_out, rel
 
 pytestmark = pytest.mark.gpu
 
 GRAD_TOL = 1e-3                       # the gradient gate of tests/test_hip_gradient.py
 PIX_TOL = 1e-3                        # the pixel gate of tests/test_hip_generator.py
 DOT_TOL = 1e-5                        # float32 dot-product kernels (channel_dot, style_grad): relative to the largest element
-NAN = float("nan")
-
-
-def rel(a, b):
-    a = a.detach().double().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, np.float64)
-    b = b.detach().double().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-class Guarded:
-    """A float32 device tensor `t` at the head of a NaN-filled buffer.  span = 16: room for a [rows][T] table read or written with row
-    stride 16 (the padded width of the kernels' tables); span = 1: 64 floats behind the end."""
-
-    def __init__(self, shape, data=None, span=1, offset=0):
-        numel = int(np.prod(shape))
-        self.buf = torch.full((offset + numel * span + 64,), NAN, dtype=torch.float32, device="cuda")
-        self.t = self.buf[offset:offset + numel].view(*shape)
-        self.end = offset + numel
-        if data is not None:
-            self.t.copy_(data.detach().to(torch.float32))
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def guard_intact(self):
-        return bool(torch.isnan(self.buf[self.end:]).all())
-
-    def written(self):
-        return not bool(torch.isnan(self.t).any())
-
-
-def g_in(t64, span=1):
-    return Guarded(tuple(t64.shape), t64, span)
-
-
-def g_out(*shape, span=1):
-    return Guarded(shape, None, span)
 
 
 def _lib_():
@@ -136,11 +100,6 @@ def test_duplex_attention_bwd_latent_counts_match_autograd(n, c, res, T):
         _lib.check(L.mgf_attn_values_grad_ws(o.ptr(), dg.ptr(), probs.ptr(), n, c, f, T, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
         assert o.written() and o.guard_intact()
     assert torch.equal(dv2.t, dv.t) and torch.equal(dv2.t, dv3.t)
-
-
-def _device_table(jobs, kind):
-    arr = (kind * len(jobs))(*jobs)
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).cuda()
 
 
 @pytest.mark.parametrize("cs", lc.LATENT_CHANNELS)
