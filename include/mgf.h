@@ -874,6 +874,30 @@ int mgf_adam_elementwise_f32(float* param, float* exp_avg, float* exp_avg_sq, in
                              float eps, float weight_decay, mgf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Latent de-morphing (gradient mode, demorph.py): the generator's rows are linear mixes of latent parameters, `rows = coef params`, so that a
+ * morph's row (1 - a) p_A + a p_B and the trusted reference's row p_A descend together.  At most 8 rows and 8 parameters of numel >= 1 floats
+ * each; no atomics, a fixed summation order and NO fused multiply-adds: every product and every sum below is rounded on its own.  A call
+ * with a NULL pointer (where none is allowed), n_rows / n_params outside 1..8, numel < 1 or an output that overlaps an input is refused.
+ *
+ * latent_mix:      rows[b, i] = sum_p coef[b, p] * params[p, i] in float32, in p order starting from the first product (coef: device
+ *                  [n_rows, n_params] float32).  coef = [[f32(1 - a), f32(a)], [1, 0]] gives merge_morph's blend and params[0], bit for bit.
+ * latent_mix_bwd:  dparams[p, i] = f32( sum_b (f64(row_weight[b]) * f64(coef[b, p])) * f64(drows[b, i]) ): float64 in b order starting from the
+ *                  first product, one rounding at the end (row_weight: device [n_rows] float32, NULL = ones).
+ * joint_losses:    the one-candidate loss slots mgf_select_best takes, as row-weighted sums of the per-row slots: slot_joint =
+ *                  sum_b f64(row_weight[b]) * f64(slot[b]) in b order, p_joint and mse_joint rounded once to float32, w_joint float64 (a joint
+ *                  slot and its per-row slot are both given or both NULL).  row_totals [n_rows, steps_total] (NULL: skipped) takes, at column
+ *                  *step, select_best's own total of each row alone, unweighted: f64(p_loss[b]) + lamda * w_loss[b] + f64(beta * mse_loss[b]),
+ *                  NaN when valid[*step] == 0 (the joint slots are written all the same).  Nothing is written when *step >= steps_total;
+ *                  the step counter is read, never advanced. */
+int mgf_latent_mix_f32(float* rows, const float* params, const float* coef, int32_t n_rows, int32_t n_params, int64_t numel,
+                       mgf_stream_t stream);
+int mgf_latent_mix_bwd_f32(float* dparams, const float* drows, const float* coef, const float* row_weight, int32_t n_rows, int32_t n_params,
+                           int64_t numel, mgf_stream_t stream);
+int mgf_joint_losses_f32(float* p_joint, double* w_joint, float* mse_joint, double* row_totals, const float* p_loss, const double* w_loss,
+                         const float* mse_loss, const float* row_weight, double lamda, float beta, const int32_t* step, const int32_t* valid,
+                         int32_t n_rows, int32_t steps_total, mgf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Noise-map optimisation (gradient mode): the generator's per-layer noise inputs as parameters next to the latent, with the
  * regulariser and the normalisation the drivers still carry (1024_example_wing_loss_perceptual_sqz_MSE.py:32-60).  float32 in and out,
  * float64 accumulation, fixed summation order, no atomics; scratch is the caller's (8-byte aligned, sizes from the *_scratch_bytes queries).

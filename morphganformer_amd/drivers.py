@@ -6,6 +6,8 @@
   merge_morph       (1-a) w1 + a w2 -> G(., psi) -> JPG+.mat (1024_merge_morph_2.py:83-92; the reference hard-codes a = 0.5,
                     BASELINE config 4 sweeps 11 values)
   refine_morph      the blend descended against BOTH contributing subjects (gradient mode with a target pair; no reference script)
+  demorph_latent / demorph    the other contributor of a morph from one trusted image: the closed form on two projections, and the coupled
+                    descent (demorph.DemorphEngine; no reference script)
   project_image     latent statistics + one ProjectionEngine run + best-of PNG / .mat   (:135-208, :246-268)
   lpips_map / save_lpips_map    the spatial LPIPS map of an image against a target (PNetLin(spatial=True), lpips/networks_basic.py:75-76) and its
                     .npy / gray .png files
@@ -249,6 +251,63 @@ def refine_morph(G, w1, w2, target_a, target_b, alphas=(0.5,), lockstep=True, ar
             save_latent_mat(tag + ".mat", r["w"])
             r["image"] = save_best_png(G, r["w"], tag + ".png", args.ratio if ratio is None else ratio)
     return out
+
+
+def demorph_latent(w_morph, w_ref, alpha=0.5):
+    """The closed-form de-morph of two projections: merge_morph's `w_M = (1 - a) w_A + a w_B` solved for the other contributor,
+    `w_B = (w_M - (1 - a) w_A) / a`, in float32 numpy like the blend it inverts.  w_morph / w_ref: z latents [1,k,D] or W+ latents
+    [1,k,num_ws,D] of one shape.  The errors of both projections come back amplified by 1 / a: alpha must lie in (0, 1]."""
+    alpha = float(alpha)
+    if not 0.0 < alpha <= 1.0:
+        raise ValueError(f"demorph_latent: alpha must lie in (0, 1] (got {alpha}): at alpha = 0 the morph holds nothing of the other contributor")
+    _latent_pair(w_morph, w_ref, "demorph_latent")
+    wm, wa = misc.as_numpy(w_morph, np.float32), misc.as_numpy(w_ref, np.float32)
+    return (wm - np.float32(1.0 - alpha) * wa) / np.float32(alpha)
+
+
+def demorph(G, morph_img, reference_img, w_morph=None, w_ref=None, alpha=0.5, args: ProjectionArgs = None, percept=None, biometric=None,
+            gamma=1.0, use_mse=True, row_weight=(1.0, 1.0), latent_std=None, latent_space=None, eps=None, seed=None, use_graph=True,
+            noise_mode="random", lm_target=None, lm_steps=None, lm_valid=None, region_weight=None, face_crop=None, face_crop_target=None,
+            face_crop_filter="area", weight_decay=0.0, out_prefix=None, ratio=None):
+    """Reference-based de-morphing: restore the second contributor of the suspected morph `morph_img` [1,3,S,S] from `reference_img`, one
+    trusted image of the first, by the coupled descent of demorph.DemorphEngine (G((1 - alpha) p_A + alpha p_B) against the morph, G(p_A)
+    against the reference; the restored face is G(p_B)).  w_morph / w_ref: the latents of earlier projections of the two images (what the
+    `.mat` files hold, z or W+; both or neither) -- the descent then starts at p_A = w_ref, p_B = demorph_latent(w_morph, w_ref, alpha); without
+    them both parameters start at the latent mean (`latent_space`: "z", the default, or "w+").  Returns the engine's result (w_a, w_b, best_step,
+    best_loss, losses, row_losses) plus w_start_b.  out_prefix: `<prefix>_restored.mat / .png` (w_b, rendered like a projection result) and
+    `<prefix>_reference.mat` (w_a)."""
+    from .demorph import DemorphEngine
+    args = args or ProjectionArgs()
+    if (w_morph is None) != (w_ref is None):
+        raise ValueError("demorph: w_morph and w_ref come together (the closed-form start needs both projections)")
+    if w_morph is not None:
+        start_b = demorph_latent(w_morph, w_ref, alpha)
+        start_a = misc.as_numpy(w_ref, np.float32)
+        if start_a.ndim not in (3, 4) or start_a.shape[0] != 1:
+            raise ValueError(f"demorph: latents must be [1,k,D] or [1,k,num_ws,D] (got {start_a.shape})")
+        space = "w+" if start_a.ndim == 4 else "z"
+        if latent_space not in (None, space):
+            raise ValueError(f"demorph: latent_space={latent_space!r} but the latents are {space} latents {start_a.shape}")
+    else:
+        space = latent_space or "z"
+    mean, std = (None, latent_std) if (latent_std is not None and w_morph is not None) else seeded_latent_stats(G, args, space, seed)
+    if latent_std is None:
+        latent_std = std
+    if w_morph is None:
+        start_a = start_b = misc.as_numpy(mean, np.float32)[None]
+    to_dev = lambda w: torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(G.device)
+    eng = DemorphEngine(G, morph_img, reference_img, to_dev(start_a), to_dev(start_b), float(latent_std), args, alpha=alpha, row_weight=row_weight,
+                        percept=percept, biometric=biometric, gamma=gamma, use_mse=use_mse, lm_target=lm_target, lm_steps=lm_steps, lm_valid=lm_valid,
+                        eps=eps, latent_space=space, region_weight=region_weight, face_crop=face_crop, face_crop_target=face_crop_target,
+                        face_crop_filter=face_crop_filter, use_graph=use_graph, weight_decay=weight_decay, noise_mode=noise_mode,
+                        seed=0 if seed is None else seed)
+    res = eng.run().result()
+    res["w_start_b"] = np.asarray(start_b, dtype=np.float32)
+    if out_prefix is not None:
+        save_latent_mat(out_prefix + "_restored.mat", res["w_b"])
+        save_latent_mat(out_prefix + "_reference.mat", res["w_a"])
+        res["image"] = save_best_png(G, res["w_b"], out_prefix + "_restored.png", args.ratio if ratio is None else ratio)
+    return res
 
 
 def merge_morph_tree(G, src_path, dst_path, truncation_psi=0.7, ratio=1.0, noise_mode="random"):

@@ -244,17 +244,42 @@ class GradientProjectionEngine(ProjectionEngine):
                                                        float(a.noise_regularize), 1, int(has_p or i > 0), self.noise_reg_scratch.data_ptr(), st),
                        "noise_regularize_grad")
 
-    def _iteration(self):
-        L, st, a, B = _lib.lib(), _lib.stream_ptr(), self.args, self.targets
+    # The three points at which a subclass couples the rows (demorph.DemorphEngine: rows that are linear mixes of parameters).  Here a row IS
+    # a parameter: the hooks add no launch and reorder none.
+    def _make_rows(self):
+        """Perturb the parameters and return the generator's input rows [B, *latent shape]."""
         # B targets: one flat parameter of B * numel floats, one noise row [B * numel] per step
-        _lib.check(L.mgf_latent_perturb(self.latent_n.data_ptr(), self.latent_in.data_ptr(), self.eps.data_ptr(), self.sigma.data_ptr(),
-                                        self.step_ctr.data_ptr(), 1, self.steps, B * self.numel, st), "latent_perturb")
+        _lib.check(_lib.lib().mgf_latent_perturb(self.latent_n.data_ptr(), self.latent_in.data_ptr(), self.eps.data_ptr(), self.sigma.data_ptr(),
+                                                 self.step_ctr.data_ptr(), 1, self.steps, self.targets * self.numel, _lib.stream_ptr()), "latent_perturb")
+        return self.latent_n
+
+    def _apply_row_gradients(self, drows):
+        """The parameters' gradient [B, *latent shape] from the rows' (the generator backward's output)."""
+        return drows
+
+    def _bookkeeping(self, dz, has_p):
+        """Per-target optimizer step, Wing term and best-of bookkeeping (tiny launches)."""
+        L, st, B = _lib.lib(), _lib.stream_ptr(), self.targets
+        for j in range(B):
+            ctr = self.step_ctr[j:]
+            valid = None if self.valid is None else (self.valid[j] if B > 1 else self.valid)
+            _lib.check(L.mgf_adam_step_f32(self.latent_in[j:].data_ptr(), self.exp_avg[j:].data_ptr(), self.exp_avg_sq[j:].data_ptr(),
+                                           self.adam_t[j:].data_ptr(), dz[j:].data_ptr(), self.lr_table.data_ptr(), ctr.data_ptr(),
+                                           _lib.ptr(valid), self.numel, self.steps, float(self.betas[0]), float(self.betas[1]),
+                                           self.adam_eps, self.weight_decay, st), "adam_step")
+            if self.use_wing:
+                _wing_into(self.wing_kind, self.w_loss[j:], self.lm_tables[j], self.lm_target[j] if B > 1 else self.lm_target, 1, ctr)
+            self._select_best(self.latent_n[j:], 1, self.noise_slot, row=j, valid=valid, has_p=has_p)
+
+    def _iteration(self):
+        a, B = self.args, self.targets
+        rows = self._make_rows()
         opt_noise = self.optimize_noise
         nkw = dict(noise_mode="inject", noises=self.noises) if opt_noise else dict(noise_mode=self.noise_mode)
         if self.latent_space == "w+":
-            img = self.gg.forward(ws=self.latent_n, **nkw)                        # [B, k, num_ws, D]: every layer reads its own slot
+            img = self.gg.forward(ws=rows, **nkw)                                 # [B, k, num_ws, D]: every layer reads its own slot
         else:
-            img = self.gg.forward(self.latent_n, **nkw)                           # psi lands in `c` in the drivers: no truncation
+            img = self.gg.forward(rows, **nkw)                                    # psi lands in `c` in the drivers: no truncation
         if B == 1:
             self._landmarks(img)                                                  # before Adam: a "no face" step must not move the latent
         tstride = img.numel() // B if B > 1 else 0
@@ -278,20 +303,12 @@ class GradientProjectionEngine(ProjectionEngine):
             dz = self.gg.backward_ws(self.dimg, dnoises=self.dnoises) if self.latent_space == "w+" else self.gg.backward(self.dimg, dnoises=self.dnoises)
         else:
             dz = self.gg.backward_ws(self.dimg) if self.latent_space == "w+" else self.gg.backward(self.dimg)
+        dz = self._apply_row_gradients(dz)
         has_p = self.has_p or opt_noise
         if opt_noise:
             self._noise_regularize(self.has_p)
             self.noise_ctr.copy_(self.step_ctr)
-        for j in range(B):                   # per-target optimizer step, Wing term and best-of bookkeeping (tiny launches)
-            ctr = self.step_ctr[j:]
-            valid = None if self.valid is None else (self.valid[j] if B > 1 else self.valid)
-            _lib.check(L.mgf_adam_step_f32(self.latent_in[j:].data_ptr(), self.exp_avg[j:].data_ptr(), self.exp_avg_sq[j:].data_ptr(),
-                                           self.adam_t[j:].data_ptr(), dz[j:].data_ptr(), self.lr_table.data_ptr(), ctr.data_ptr(),
-                                           _lib.ptr(valid), self.numel, self.steps, float(self.betas[0]), float(self.betas[1]),
-                                           self.adam_eps, self.weight_decay, st), "adam_step")
-            if self.use_wing:
-                _wing_into(self.wing_kind, self.w_loss[j:], self.lm_tables[j], self.lm_target[j] if B > 1 else self.lm_target, 1, ctr)
-            self._select_best(self.latent_n[j:], 1, self.noise_slot, row=j, valid=valid, has_p=has_p)
+        self._bookkeeping(dz, has_p)
         if opt_noise:
             self._noise_update()
         return img

@@ -481,18 +481,21 @@ class ProjectionEngine:
             _lib.check(L.mgf_keep_improvements(self.trail.imgs.data_ptr(), full_img.data_ptr(), self.trail.imgs.shape[1],
                                                self.trail.take.data_ptr(), B, st), "keep_improvements")
 
-    def _select_best(self, latent_n, n, slot, row=0, valid=None, has_p=None):
+    def _select_best(self, latent_n, n, slot, row=0, valid=None, has_p=None, numel=None, loss_slots=None):
         """The in-order best-so-far selection over the `n` candidates `latent_n` of target `row`: that target's rows of the loop state and of
         the three loss slots (a slot that no term writes goes in as null), its `valid` table, and `slot`, the ImprovementSlot that learns
-        which candidates improved (None: nobody asks).  The one place that spells mgf_select_best's argument list."""
+        which candidates improved (None: nobody asks).  The one place that spells mgf_select_best's argument list.  numel: the floats of one
+        candidate where that is not one latent (the de-morphing engine's parameter pair); loss_slots: its (p, w, mse) slots in place of row
+        `row` of the engine's."""
         a, j = self.args, row
         has_p = self.has_p if has_p is None else has_p
         take, count, slots, steps, losses = (None, None, 0, None, None) if slot is None else (slot.take, slot.count, slot.slots, slot.steps, slot.losses)
+        p_loss, w_loss, mse_loss = (self.p_loss[j:], self.w_loss[j:], self.mse_loss[j:]) if loss_slots is None else loss_slots
         _lib.check(_lib.lib().mgf_select_best(
             self.min_loss[j:].data_ptr(), self.best_latent[j:].data_ptr(), self.best_step[j:].data_ptr(),
-            self.losses.reshape(self.min_loss.numel(), -1)[j].data_ptr(), latent_n.data_ptr(), self.numel,
-            _lib.ptr(self.p_loss[j:] if has_p else None), _lib.ptr(self.w_loss[j:] if (self.use_wing or self.use_lbp) else None),
-            _lib.ptr(self.mse_loss[j:] if self.use_mse else None), 1.0 if self.use_lbp else float(a.lamda), float(a.beta),
+            self.losses.reshape(self.min_loss.numel(), -1)[j].data_ptr(), latent_n.data_ptr(), self.numel if numel is None else int(numel),
+            _lib.ptr(p_loss if has_p else None), _lib.ptr(w_loss if (self.use_wing or self.use_lbp) else None),
+            _lib.ptr(mse_loss if self.use_mse else None), 1.0 if self.use_lbp else float(a.lamda), float(a.beta),
             self.step_ctr[j:].data_ptr(), _lib.ptr(valid), n, self.steps, _lib.ptr(take), _lib.ptr(count), slots, _lib.ptr(steps), _lib.ptr(losses),
             _lib.stream_ptr()), "select_best")
 
