@@ -898,6 +898,27 @@ int mgf_joint_losses_f32(float* p_joint, double* w_joint, float* mse_joint, doub
                          int32_t n_rows, int32_t steps_total, mgf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Evolution-strategy mode (evolution.py): the (mu/mu_w, lambda) recombination that follows a scored generation of the literal loop.  One
+ * generation = the `batch` candidates of one mgf_latent_perturb / mgf_select_best pair; the launch goes BEHIND mgf_select_best and reads the
+ * totals it wrote.  Deterministic: float64, a fixed order, no atomics and NO fused multiply-adds (every product, quotient and sum below is
+ * rounded on its own); everything is read from device memory (no host synchronisation, capturable).
+ *
+ * es_recombine:  s0 = *step0, the step counter as it stood BEFORE mgf_select_best advanced it (a copy the caller keeps);
+ *                n = min(batch, steps_total - s0); nothing at all is written when n <= 0 (or s0 < 0).
+ *                cand [batch, numel]: the generation's latent_n rows as the generator saw them.  totals [steps_total]: select_best's losses_out.
+ *                Candidate j < n is VALID iff totals[s0 + j] is finite (select_best leaves NaN for a "no face" step; a NaN or infinite loss
+ *                never steers the mean).  The valid candidates are ranked by total ascending, ties to the smaller j: j_0, j_1, ...; with v of
+ *                them, m = min(mu, v).  m == 0: `mean` stays as it is.  Otherwise
+ *                  wsum = sum_{r<m} weights[r]                                   float64, r order  (weights: device [>= mu] float64)
+ *                  S[i] = sum_{r<m} (weights[r] / wsum) * f64(cand[j_r, i])     float64, r order starting from the first product
+ *                  mean[i] = f32( f64(mean[i]) + mean_lr * (S[i] - f64(mean[i])) )
+ *                used (optional, [ceil(steps_total / batch)] int32): used[s0 / batch] = m (also when m == 0).
+ *                Refused with MGF_EINVAL before any launch: a NULL mean / cand / totals / step0 / weights, batch outside 1..1024 (the
+ *                generation is ranked in LDS), mu outside 1..batch, numel < 1, steps_total < 1, `mean` overlapping `cand`. */
+int mgf_es_recombine_f32(float* mean, const float* cand, const double* totals, const int32_t* step0, const double* weights, int32_t mu,
+                         int32_t batch, int32_t steps_total, int64_t numel, double mean_lr, int32_t* used, mgf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Noise-map optimisation (gradient mode): the generator's per-layer noise inputs as parameters next to the latent, with the
  * regulariser and the normalisation the drivers still carry (1024_example_wing_loss_perceptual_sqz_MSE.py:32-60).  float32 in and out,
  * float64 accumulation, fixed summation order, no atomics; scratch is the caller's (8-byte aligned, sizes from the *_scratch_bytes queries).

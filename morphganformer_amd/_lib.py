@@ -197,6 +197,7 @@ _SIGS = {
     "mgf_latent_mix_f32": (C.c_int, [vp, vp, vp, i32, i32, i64, vp]),
     "mgf_latent_mix_bwd_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, vp]),
     "mgf_joint_losses_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, f64, f32, vp, vp, i32, i32, vp]),
+    "mgf_es_recombine_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i64, f64, vp, vp]),
     "mgf_noise_grad_f32": (C.c_int, [vp, vp, vp, i32, i64, i32, vp]),
     "mgf_noise_regularize_scratch_bytes": (i64, [i32]),
     "mgf_noise_regularize_f32": (C.c_int, [vp, vp, i32, f32, i32, vp, vp]),

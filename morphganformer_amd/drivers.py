@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, misc
+from .evolution import EvolutionProjectionEngine, recombination_weights
 from .projection import (GradientProjectionEngine, ProjectionArgs, ProjectionEngine, save_best_png, seeded_generator, seeded_latent_stats,
                          seeded_randn)
 from .warp import (WARP_EXTRA_POINTS, _cv_affine_inverse, _cv_bounding_rect, _cv_fill_convex_poly, _cv_line8, _pack_warp_records,      # noqa: F401
@@ -490,14 +491,17 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                   landmark_fn=None, mode="literal", weight_decay=0.0, path_to_gen=None, keep_images=64, engine=None,
                   return_engine=False, latent_space="z", landmark_input="float", biometric=None, gamma=1.0, lbp_target=None, pipeline=None,
                   mdf=None, optimize_noise=False, noise_init="randn", lpips_map=False, region_weight=None, face_crop=None,
-                  face_crop_filter="area"):
+                  face_crop_filter="area", elite=None, es_weights="log", mean_lr=1.0):
     """One full `projection(...)` call (:135-208).  `target`: [1,3,S,S] from image_transform; `lm_target` [68,2] and either
     `lm_steps` [steps,68,2] (injected landmark detections) or `landmark_fn` (host detector called on every generated image,
     see ProjectionEngine; landmark_input="gray_u8" hands it the drivers' gray uint8 image, built on the device).  mode="literal" is the loop as the reference executes it (best-of-N noisy sampling, `batch` steps per
     forward -- 32 by default, the benchmarked configuration; the result does not depend on it); mode="gradient" back-propagates the
     loss into the latent and lets Adam move it (GradientProjectionEngine; one candidate per step; weight_decay=1e-4 is the
     1024_example_MSE.py:117 optimizer; latent_space="w+" optimises the per-layer intermediate latent [k, num_ws, D] instead of z -- the
-    statistics are then taken in w space, projection.latent_stats_w -- and `w` comes back as [1, k, num_ws, D]).  Returns dict(w, step,
+    statistics are then taken in w space, projection.latent_stats_w -- and `w` comes back as [1, k, num_ws, D]); mode="evolution" is the literal loop with a mean
+    that moves (evolution.EvolutionProjectionEngine: every batch of candidates is a generation, after which the mean becomes the weighted average
+    of its best `elite` candidates -- `es_weights` "log" or "equal", step `mean_lr` -- so terms without a gradient steer the latent too; z only,
+    never pipelined; outputs and engine= re-targeting are literal mode's, and the result gains `mean` [1,k,D] and `elite_used`).  Returns dict(w, step,
     loss, losses).
 
     biometric / gamma: an iresnet.BiometricLoss (embedder "facenet" or "iresnetNN") adds gamma * MSE(embed(img), embed(target)) to the objective
@@ -540,10 +544,14 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     hands it out) -- it is re-targeted in place (`ProjectionEngine.retarget`), which keeps its captured hipGraph and workspaces; this is
     how `project_many` walks a list of targets."""
     args = args or ProjectionArgs()
-    if mode not in ("literal", "gradient"):
-        raise ValueError(f"mode must be 'literal' or 'gradient' (got {mode!r})")
-    if engine is not None and mode != "literal":
-        raise ValueError("engine= (re-targeting) is for literal mode")
+    if mode not in ("literal", "gradient", "evolution"):
+        raise ValueError(f"mode must be 'literal', 'gradient' or 'evolution' (got {mode!r})")
+    sampling = mode in ("literal", "evolution")              # the loops that score `batch` candidates per forward and keep literal mode's outputs
+    if engine is not None and not sampling:
+        raise ValueError("engine= (re-targeting) is for literal and evolution mode")
+    if mode == "evolution" and pipeline:
+        raise _lib.MgfError("project_image: mode='evolution' is never pipelined (the next generation's candidates are drawn around a mean that "
+                            "depends on this generation's losses)")
     if latent_space not in ("z", "w+") or (latent_space == "w+" and mode != "gradient"):
         raise ValueError("latent_space must be 'z', or 'w+' together with mode='gradient'")
     if optimize_noise and mode != "gradient":
@@ -565,7 +573,13 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
         latent_mean, latent_std = seeded_latent_stats(G, args, latent_space, seed)
     if pipeline is None:
         pipeline = mode == "literal" and landmark_fn is None and biometric is None and getattr(percept, "net", None) == "squeeze"
-    keep = max(int(keep_images), int(batch)) if path_to_gen is not None and mode == "literal" else 0
+    keep = max(int(keep_images), int(batch)) if path_to_gen is not None and sampling else 0
+    if engine is not None and (mode == "evolution") != isinstance(engine, EvolutionProjectionEngine):
+        raise ValueError(f"engine= was built for another mode than {mode!r}")
+    if engine is not None and mode == "evolution" and not (
+            engine.elite == (max(1, batch // 4) if elite is None else int(elite)) and engine.mean_lr == float(mean_lr) and
+            np.array_equal(engine.es_weight_table, recombination_weights(engine.elite, es_weights))):
+        raise ValueError("engine= was built with another elite / es_weights / mean_lr")
     if engine is not None:
         if (engine.G is not G or engine.batch != batch or engine.steps != args.step or engine.keep_images != keep or
                 engine.pipeline != (bool(pipeline) and landmark_fn is None)):
@@ -590,13 +604,17 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                                        biometric=biometric, gamma=gamma, mdf=mdf, optimize_noise=optimize_noise, noise_init=noise_init,
                                        region_weight=region_weight, face_crop=crop, face_crop_filter=face_crop_filter)
     else:
-        eng = ProjectionEngine(G, target, latent_mean, float(latent_std), args, percept=percept, lm_target=lm_target,
-                               lm_steps=lm_steps, eps=eps, noise_mode=noise_mode, use_graph=use_graph, batch=batch, use_mse=use_mse,
-                               landmark_fn=landmark_fn, keep_images=keep, seed=0 if seed is None else seed, landmark_input=landmark_input,
-                               biometric=biometric, gamma=gamma, lbp_target=lbp_target, pipeline=pipeline, mdf=mdf, region_weight=region_weight,
-                               face_crop=crop, face_crop_filter=face_crop_filter)
+        es = dict(elite=elite, es_weights=es_weights, mean_lr=mean_lr) if mode == "evolution" else {}
+        eng = (EvolutionProjectionEngine if es else ProjectionEngine)(
+            G, target, latent_mean, float(latent_std), args, percept=percept, lm_target=lm_target,
+            lm_steps=lm_steps, eps=eps, noise_mode=noise_mode, use_graph=use_graph, batch=batch, use_mse=use_mse,
+            landmark_fn=landmark_fn, keep_images=keep, seed=0 if seed is None else seed, landmark_input=landmark_input,
+            biometric=biometric, gamma=gamma, lbp_target=lbp_target, pipeline=pipeline, mdf=mdf, region_weight=region_weight,
+            face_crop=crop, face_crop_filter=face_crop_filter, **es)
     w, step, loss, losses = eng.run().result()
     out = {"w": w, "step": step, "loss": loss, "losses": losses}
+    if mode == "evolution":
+        out["mean"], out["elite_used"] = eng.mean.cpu(), eng.elite_used()
     best_noises = None
     if optimize_noise:
         best_noises = {name: t.clone() for name, t in eng.best_noises.items()}
@@ -606,7 +624,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
         if path_to_gen is None:                      # no improvement trail asked for: still leave an image of the result beside the latent
             out["image"] = save_best_png(G, w, f"{out_prefix}.png", args.ratio, noises=best_noises)
     if path_to_gen is not None:
-        if mode == "literal":
+        if sampling:
             out["images"] = eng.save_improvements(path_to_gen, args.ratio)
         else:
             out["images"] = [save_best_png(G, w, os.path.join(path_to_gen, "{:06d}_{:04f}.png".format(step, loss)), args.ratio, noises=best_noises)]
@@ -665,7 +683,7 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_w
         out = unpack_results(gather_many(rows, -(-len(targets) // world)), lshape)
         out["mine"] = list(mine)
         return out
-    reuse = kw.get("mode", "literal") == "literal" and kw.get("landmark_fn") is None and kw.get("eps") is None
+    reuse = kw.get("mode", "literal") in ("literal", "evolution") and kw.get("landmark_fn") is None and kw.get("eps") is None
     if reuse and (kw.get("latent_mean") is None or kw.get("latent_std") is None):
         kw["latent_mean"], kw["latent_std"] = seeded_latent_stats(G, kw.get("args") or ProjectionArgs(), "z", kw.get("seed"))   # once per rank, not per item
     state = {"eng": None}
