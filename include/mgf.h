@@ -941,6 +941,48 @@ int64_t mgf_noise_normalize_scratch_bytes(void);
 int mgf_noise_normalize_f32(float* x, int64_t numel, const int32_t* step, const int32_t* valid, int32_t steps_total, void* scratch,
                             mgf_stream_t stream);
 
+/* The same over SETS, for lockstep targets with maps of their own: a set is one target's maps, set t starts t * set_stride floats after
+ * set 0, and one MAP TABLE holds for every set: map m is sides[m] x sides[m] (a side noise_regularize takes) and starts offsets[m] floats
+ * into the set.  `sides` and `offsets` are HOST arrays of n_maps <= 32 entries that travel in the kernel arguments: no call copies anything
+ * to the device, every call can be captured.  The launch count depends on neither n_sets nor n_maps, and every (set, map) gets the per-map
+ * entry's arithmetic (the kernels share the bodies; partial counts and fold orders are the per-map ones), i.e. its bits.
+ *
+ * noise_sets_scratch_bytes:  the scratch of noise_sets_regularize_grad for n_sets sets of the table; noise_sets_normalize needs less and
+ *              takes the same buffer.  0 for a table that is refused.
+ * noise_sets_regularize_grad:  for every set t and map m  dx[t, m] (+)= scale * d reg / d x[t, m]  (dx is laid out like x), and, when
+ *              `value` is given,  value[t * value_stride] (+)= the maps' f32(scale * reg) added in float32 in table order -- the sequence
+ *              n_maps calls of noise_regularize_grad with accumulate_value = 1 (from the second on) form.  One forward launch per distinct
+ *              pyramid side over all (set, map) that have that level, one launch with a workgroup per (set, map) for the statistics, one
+ *              backward launch per distinct side (the first of them also adds up the values): 19 launches for the maps of a 1024^2
+ *              generator, whatever n_sets.
+ * noise_sets_normalize:  noise_normalize of every map of every set in two launches; set t is gated by step[t * step_stride] and the row
+ *              valid + t * valid_stride (step NULL: every set is live; valid NULL: no table): a skipped step or one past the end leaves
+ *              that set's maps bit-unchanged while the others move.
+ * noise_sets_grad:  dnoise[j * dnoise_stride + p] (+)= strength[0] * sum_c dpre[j, c, p] for the n samples of dpre [n, c, hw] in one launch,
+ *              with noise_grad's slice form for (c, hw).
+ * noise_sets_pack:  dst, dense and map-major ([map][set][side^2]), = the sets' maps: the generator's layers read n_sets dense maps each
+ *              (mgf_epilogue.noise with noise_n = n_sets), the sets keep a target's maps together.  One launch; dst must not overlap x.
+ * adam_sets (behind adam_elementwise's arithmetic):  n_sets slices of numel floats, slice t at t * set_stride in param / exp_avg /
+ *              exp_avg_sq / grad, with its own adam_t[t], step[t * step_stride] and row valid + t * valid_stride; one update launch and
+ *              one that advances the counts.
+ * Refused with MGF_EINVAL before any launch: a NULL pointer where none is allowed (value, step where stated, valid may be NULL), n_maps
+ * outside 1..32, n_sets < 1 (or n_sets * n_maps > 65535), a side noise_regularize refuses, a negative offset, maps that overlap in the
+ * table, a set_stride smaller than the table's extent, dx's span overlapping x's, a stride smaller than the slice it steps over. */
+int64_t mgf_noise_sets_scratch_bytes(const int32_t* sides, int32_t n_maps, int32_t n_sets);
+int mgf_noise_sets_regularize_grad_f32(float* dx, float* value, int64_t value_stride, const float* x, const int64_t* offsets,
+                                       const int32_t* sides, int32_t n_maps, int32_t n_sets, int64_t set_stride, float scale,
+                                       int32_t accumulate_dx, int32_t accumulate_value, void* scratch, mgf_stream_t stream);
+int mgf_noise_sets_normalize_f32(float* x, const int64_t* offsets, const int32_t* sides, int32_t n_maps, int32_t n_sets, int64_t set_stride,
+                                 const int32_t* step, int64_t step_stride, const int32_t* valid, int64_t valid_stride, int32_t steps_total,
+                                 void* scratch, mgf_stream_t stream);
+int mgf_noise_sets_grad_f32(float* dnoise, int64_t dnoise_stride, const float* dpre, const float* strength, int32_t n, int32_t c, int64_t hw,
+                            int32_t accumulate, mgf_stream_t stream);
+int mgf_noise_sets_pack_f32(float* dst, const float* x, const int64_t* offsets, const int32_t* sides, int32_t n_maps, int32_t n_sets,
+                            int64_t set_stride, mgf_stream_t stream);
+int mgf_adam_sets_f32(float* param, float* exp_avg, float* exp_avg_sq, int32_t* adam_t, const float* grad, const float* lr_table,
+                      const int32_t* step, int64_t step_stride, const int32_t* valid, int64_t valid_stride, int64_t numel, int32_t n_sets,
+                      int64_t set_stride, int32_t steps_total, float beta1, float beta2, float eps, float weight_decay, mgf_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * MDF objective (mdfloss.py:16-47 over the SinGAN WDiscriminators of SinGAN/models.py:7-35; csrc/mdf.hip): per discriminator five
  * VALID 3x3 / stride-1 convolutions, eval-mode BatchNorm folded into weight and bias (w [c][cin][3][3] in torch layout), LeakyReLU

@@ -204,6 +204,13 @@ _SIGS = {
     "mgf_noise_regularize_grad_f32": (C.c_int, [vp, vp, vp, i32, f32, i32, i32, vp, vp]),
     "mgf_noise_normalize_scratch_bytes": (i64, []),
     "mgf_noise_normalize_f32": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
+    # (sides / offsets: HOST arrays, e.g. (i32 * n)(*sides) -- see map_table())
+    "mgf_noise_sets_scratch_bytes": (i64, [vp, i32, i32]),
+    "mgf_noise_sets_regularize_grad_f32": (C.c_int, [vp, vp, i64, vp, vp, vp, i32, i32, i64, f32, i32, i32, vp, vp]),
+    "mgf_noise_sets_normalize_f32": (C.c_int, [vp, vp, vp, i32, i32, i64, vp, i64, vp, i64, i32, vp, vp]),
+    "mgf_noise_sets_grad_f32": (C.c_int, [vp, i64, vp, vp, i32, i32, i64, i32, vp]),
+    "mgf_noise_sets_pack_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, vp]),
+    "mgf_adam_sets_f32":(C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i32, i64, i32, f32, f32, f32, f32, vp]),
     "mgf_mapping_bwd_scratch_floats": (i64, [i32, i32, i32]),
     "mgf_mapping_backward": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "mgf_mapping_forward_save": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
@@ -254,6 +261,13 @@ def stream_ptr() -> int:
 
 def ptr(t):
     return 0 if t is None else t.data_ptr()
+
+
+def map_table(sides, offsets):
+    """The host-side map table of the mgf_noise_sets_* entries: (sides as int32[n], offsets as int64[n], n)."""
+    n = len(sides)
+    assert len(offsets) == n
+    return (i32 * n)(*[int(s) for s in sides]), (i64 * n)(*[int(o) for o in offsets]), n
 
 
 def require_gpu(*tensors):

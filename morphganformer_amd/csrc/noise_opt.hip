@@ -3,6 +3,8 @@
 //   mgf_noise_regularize(_grad)_f32  noise_regularize of the drivers (1024_example_wing_loss_perceptual_sqz_MSE.py:32-52) and its gradient
 //   mgf_noise_normalize_f32        noise_normalize_ (:55-60): x <- (x - mean) / std, std unbiased
 //   mgf_adam_elementwise_f32       mgf_adam_step_f32's arithmetic on any number of workgroups
+//   mgf_noise_sets_* / mgf_adam_sets_f32   the same four over SETS (one target's maps each; a map table that holds for every set) in a
+//                                  launch count that depends on neither the number of sets nor of maps; the per-element bodies are shared
 // float32 in and out, float64 accumulation, fixed summation order (block partials in caller scratch, folded by a fixed tree), no atomics.
 #include "mgf_common.h"
 
@@ -25,8 +27,8 @@ __device__ __forceinline__ double block_sum_256(double v, double* sh) {
 // block = PQ pixel groups x S channel slices (PQ * S = 256); a thread sums its slice's channels in index order for V consecutive pixels,
 // the slices are then added in index order.  S > 1 only where the map is too small to fill the chip with one thread per pixel group.
 template <int V, int S>
-__global__ __launch_bounds__(256) void noise_grad_kernel(float* __restrict__ dnoise, const float* __restrict__ dpre, const float* __restrict__ strength,
-                                                         int c, int64_t hw, int accumulate) {
+__device__ __forceinline__ void noise_grad_body(float* __restrict__ dnoise, const float* __restrict__ dpre, const float* __restrict__ strength,
+                                                int c, int64_t hw, int accumulate) {
     constexpr int PQ = 256 / S;
     __shared__ double part[S > 1 ? S : 1][PQ][V];
     const int pq = threadIdx.x % PQ, sl = threadIdx.x / PQ;
@@ -80,18 +82,49 @@ __global__ __launch_bounds__(256) void noise_grad_kernel(float* __restrict__ dno
 }
 
 template <int V, int S>
-void launch_noise_grad(float* dnoise, const float* dpre, const float* strength, int c, int64_t hw, int accumulate, hipStream_t st) {
+__global__ __launch_bounds__(256) void noise_grad_kernel(float* __restrict__ dnoise, const float* __restrict__ dpre, const float* __restrict__ strength,
+                                                         int c, int64_t hw, int accumulate) {
+    noise_grad_body<V, S>(dnoise, dpre, strength, c, hw, accumulate);
+}
+
+// The same body for sample blockIdx.y of dpre [n, c, hw], into that sample's own map.
+template <int V, int S>
+__global__ __launch_bounds__(256) void noise_sets_grad_kernel(float* __restrict__ dnoise, int64_t dnoise_stride, const float* __restrict__ dpre,
+                                                              const float* __restrict__ strength, int c, int64_t hw, int accumulate) {
+    noise_grad_body<V, S>(dnoise + (int64_t)blockIdx.y * dnoise_stride, dpre + (int64_t)blockIdx.y * c * hw, strength, c, hw, accumulate);
+}
+
+// n == 0: the per-map kernel; n >= 1: the per-sample one over n samples.
+template <int V, int S>
+void launch_noise_grad(float* dnoise, const float* dpre, const float* strength, int c, int64_t hw, int accumulate, hipStream_t st, int n = 0,
+                       int64_t dnoise_stride = 0) {
     const int64_t groups = hw / V;
     const int grid = (int)mgf_cdiv(groups, 256 / S);
-    hipLaunchKernelGGL((noise_grad_kernel<V, S>), dim3(grid), dim3(256), 0, st, dnoise, dpre, strength, c, hw, accumulate);
+    if (n == 0)
+        hipLaunchKernelGGL((noise_grad_kernel<V, S>), dim3(grid), dim3(256), 0, st, dnoise, dpre, strength, c, hw, accumulate);
+    else
+        hipLaunchKernelGGL((noise_sets_grad_kernel<V, S>), dim3(grid, n), dim3(256), 0, st, dnoise, dnoise_stride, dpre, strength, c, hw, accumulate);
+}
+
+// The slice form for a layer of c channels and hw pixels (vec: float4 loads are possible).
+void choose_noise_grad(bool vec, float* dnoise, const float* dpre, const float* strength, int c, int64_t hw, int accumulate, hipStream_t st,
+                       int n = 0, int64_t dnoise_stride = 0) {
+    if (vec) {
+        const int64_t groups = hw / 4;
+        if (groups >= 65536 || c < 16) launch_noise_grad<4, 1>(dnoise, dpre, strength, c, hw, accumulate, st, n, dnoise_stride);
+        else if (groups >= 16384 || c < 64) launch_noise_grad<4, 4>(dnoise, dpre, strength, c, hw, accumulate, st, n, dnoise_stride);
+        else launch_noise_grad<4, 16>(dnoise, dpre, strength, c, hw, accumulate, st, n, dnoise_stride);
+    } else {
+        if (c < 64) launch_noise_grad<1, 1>(dnoise, dpre, strength, c, hw, accumulate, st, n, dnoise_stride);
+        else launch_noise_grad<1, 16>(dnoise, dpre, strength, c, hw, accumulate, st, n, dnoise_stride);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------- regulariser
 // One level of the pyramid, side s: block partials of  a = sum x[y,x] x[y,x-1]  and  b = sum x[y,x] x[y-1,x]  (indices modulo s: the rolls
 // wrap), one thread per 2 x 2 block, and -- when `next` is given -- the block means, the next level's map.
 template <typename T>
-__global__ __launch_bounds__(256) void reg_level_fwd_kernel(double* __restrict__ partials, double* __restrict__ next, const T* __restrict__ x, int s) {
-    __shared__ double sh[4];
+__device__ __forceinline__ void reg_level_fwd_body(double* __restrict__ partials, double* __restrict__ next, const T* __restrict__ x, int s, double* sh) {
     const int half = s >> 1;
     const int64_t blocks = (int64_t)half * half;
     double a = 0.0, b = 0.0;
@@ -113,6 +146,12 @@ __global__ __launch_bounds__(256) void reg_level_fwd_kernel(double* __restrict__
     if (threadIdx.x == 0) { partials[2 * blockIdx.x] = a; partials[2 * blockIdx.x + 1] = b; }
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void reg_level_fwd_kernel(double* __restrict__ partials, double* __restrict__ next, const T* __restrict__ x, int s) {
+    __shared__ double sh[4];
+    reg_level_fwd_body<T>(partials, next, x, s, sh);
+}
+
 struct RegLevels {
     int32_t levels;
     int32_t side[16];
@@ -121,20 +160,24 @@ struct RegLevels {
 
 // One workgroup: fold every level's partials, stats[l] = {mean of the column product, mean of the row product}, and
 // value (+)= scale * sum_l (A_l^2 + B_l^2) when `value` is given.
+// Level l of one map: fold its `nparts` partials, stats[l] = {A, B}; returns A^2 + B^2 (every thread).
+__device__ __forceinline__ double reg_finish_level(double* __restrict__ stats, const double* __restrict__ partials, int l, int nparts, int side,
+                                                   double* sh) {
+    const double* p = partials + (int64_t)l * NO_PARTS * 2;
+    const bool in = (int)threadIdx.x < nparts;
+    const double a = block_sum_256(in ? p[2 * threadIdx.x] : 0.0, sh);
+    const double b = block_sum_256(in ? p[2 * threadIdx.x + 1] : 0.0, sh);
+    const double n = (double)side * (double)side;
+    const double A = a / n, B = b / n;
+    if (threadIdx.x == 0) { stats[2 * l] = A; stats[2 * l + 1] = B; }
+    return A * A + B * B;
+}
+
 __global__ __launch_bounds__(256) void reg_finish_kernel(double* __restrict__ stats, float* value, const double* __restrict__ partials, RegLevels lv,
                                                          double scale, int accumulate) {
     __shared__ double sh[4];
     double reg = 0.0;
-    for (int l = 0; l < lv.levels; ++l) {
-        const double* p = partials + (int64_t)l * NO_PARTS * 2;
-        const bool in = (int)threadIdx.x < lv.nparts[l];
-        const double a = block_sum_256(in ? p[2 * threadIdx.x] : 0.0, sh);
-        const double b = block_sum_256(in ? p[2 * threadIdx.x + 1] : 0.0, sh);
-        const double n = (double)lv.side[l] * (double)lv.side[l];
-        const double A = a / n, B = b / n;
-        if (threadIdx.x == 0) { stats[2 * l] = A; stats[2 * l + 1] = B; }
-        reg += A * A + B * B;
-    }
+    for (int l = 0; l < lv.levels; ++l) reg += reg_finish_level(stats, partials, l, lv.nparts[l], lv.side[l], sh);
     if (value && threadIdx.x == 0) {
         const float v = (float)(scale * reg);
         *value = accumulate ? *value + v : v;
@@ -144,9 +187,9 @@ __global__ __launch_bounds__(256) void reg_finish_kernel(double* __restrict__ st
 // Gradient of one level, one thread per element:  g = 2A/N (left + right) + 2B/N (upper + lower) + 1/4 g_parent[y/2, x/2]  (the block
 // mean's adjoint); inner levels keep g in float64 scratch, the finest level writes dx (+)= scale * g.
 template <typename T>
-__global__ __launch_bounds__(256) void reg_level_bwd_kernel(double* __restrict__ gcur, float* __restrict__ dx, const T* __restrict__ x,
-                                                            const double* __restrict__ gparent, const double* __restrict__ stats, int s,
-                                                            double scale, int accumulate) {
+__device__ __forceinline__ void reg_level_bwd_body(double* __restrict__ gcur, float* __restrict__ dx, const T* __restrict__ x,
+                                                   const double* __restrict__ gparent, const double* __restrict__ stats, int s,
+                                                   double scale, int accumulate) {
     const double n = (double)s * (double)s;
     const double ka = 2.0 * stats[0] / n, kb = 2.0 * stats[1] / n;
     const int64_t total = (int64_t)s * s;
@@ -164,6 +207,13 @@ __global__ __launch_bounds__(256) void reg_level_bwd_kernel(double* __restrict__
             gcur[i] = g;
         }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void reg_level_bwd_kernel(double* __restrict__ gcur, float* __restrict__ dx, const T* __restrict__ x,
+                                                            const double* __restrict__ gparent, const double* __restrict__ stats, int s,
+                                                            double scale, int accumulate) {
+    reg_level_bwd_body<T>(gcur, dx, x, gparent, stats, s, scale, accumulate);
 }
 
 int reg_levels(int32_t side, RegLevels* lv) {
@@ -212,23 +262,22 @@ __device__ __forceinline__ bool step_is_live(const int32_t* step, const int32_t*
     return s < steps_total && !(valid && valid[s] == 0);
 }
 
-__global__ __launch_bounds__(256) void norm_partial_kernel(double* __restrict__ partials, const float* __restrict__ x, int64_t numel) {
-    __shared__ double sh[4];
+// Block bx of gx: its partial sums of x and x^2 (the partial count and a thread's summation order depend on gx).
+__device__ __forceinline__ void norm_partial_body(double* __restrict__ partials, const float* __restrict__ x, int64_t numel, int bx, int gx, double* sh) {
     double s = 0.0, q = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < numel; i += (int64_t)gridDim.x * 256) {
+    for (int64_t i = (int64_t)bx * 256 + threadIdx.x; i < numel; i += (int64_t)gx * 256) {
         const double v = (double)x[i];
         s += v;
         q += v * v;
     }
     s = block_sum_256(s, sh);
     q = block_sum_256(q, sh);
-    if (threadIdx.x == 0) { partials[2 * blockIdx.x] = s; partials[2 * blockIdx.x + 1] = q; }
+    if (threadIdx.x == 0) { partials[2 * bx] = s; partials[2 * bx + 1] = q; }
 }
 
-__global__ __launch_bounds__(256) void norm_apply_kernel(float* __restrict__ x, const double* __restrict__ partials, int nparts, int64_t numel,
-                                                         const int32_t* step, const int32_t* valid, int steps_total) {
-    __shared__ double sh[4];
-    if (!step_is_live(step, valid, steps_total)) return;                     // (uniform over the grid)
+// Block bx of gx: fold the partials and normalise its share of the elements (elementwise: gx changes no bit).
+__device__ __forceinline__ void norm_apply_body(float* __restrict__ x, const double* __restrict__ partials, int nparts, int64_t numel, int bx, int gx,
+                                                double* sh) {
     const bool in = (int)threadIdx.x < nparts;
     const double s = block_sum_256(in ? partials[2 * threadIdx.x] : 0.0, sh);
     const double q = block_sum_256(in ? partials[2 * threadIdx.x + 1] : 0.0, sh);
@@ -236,16 +285,28 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(float* __restrict__ x, 
     const double mean = s / n;
     const double var = (q - s * mean) / (n - 1.0);                            // unbiased, torch's default
     const double inv = 1.0 / sqrt(var);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < numel; i += (int64_t)gridDim.x * 256)
+    for (int64_t i = (int64_t)bx * 256 + threadIdx.x; i < numel; i += (int64_t)gx * 256)
         x[i] = (float)(((double)x[i] - mean) * inv);
+}
+
+__global__ __launch_bounds__(256) void norm_partial_kernel(double* __restrict__ partials, const float* __restrict__ x, int64_t numel) {
+    __shared__ double sh[4];
+    norm_partial_body(partials, x, numel, blockIdx.x, gridDim.x, sh);
+}
+
+__global__ __launch_bounds__(256) void norm_apply_kernel(float* __restrict__ x, const double* __restrict__ partials, int nparts, int64_t numel,
+                                                         const int32_t* step, const int32_t* valid, int steps_total) {
+    __shared__ double sh[4];
+    if (!step_is_live(step, valid, steps_total)) return;                     // (uniform over the grid)
+    norm_apply_body(x, partials, nparts, numel, blockIdx.x, gridDim.x, sh);
 }
 
 // ---------------------------------------------------------------------------------------------- Adam
 // adam_step_kernel of backward.hip, expression for expression, over a grid; the step count is advanced by a launch of its own behind it
 // (no block may see the new count).
-__global__ __launch_bounds__(256) void adam_elementwise_kernel(float* param, float* m, float* v, const int32_t* t_ctr, const float* grad,
-                                                               const float* lr_table, const int32_t* step, const int32_t* valid, int64_t numel,
-                                                               int steps_total, float beta1, float beta2, float eps, float weight_decay) {
+__device__ __forceinline__ void adam_elementwise_body(float* param, float* m, float* v, const int32_t* t_ctr, const float* grad,
+                                                      const float* lr_table, const int32_t* step, const int32_t* valid, int64_t numel,
+                                                      int steps_total, float beta1, float beta2, float eps, float weight_decay) {
     const int s = *step;
     if (s >= steps_total || (valid && valid[s] == 0)) return;
     const int t = *t_ctr + 1;
@@ -263,10 +324,231 @@ __global__ __launch_bounds__(256) void adam_elementwise_kernel(float* param, flo
     }
 }
 
+__global__ __launch_bounds__(256) void adam_elementwise_kernel(float* param, float* m, float* v, const int32_t* t_ctr, const float* grad,
+                                                               const float* lr_table, const int32_t* step, const int32_t* valid, int64_t numel,
+                                                               int steps_total, float beta1, float beta2, float eps, float weight_decay) {
+    adam_elementwise_body(param, m, v, t_ctr, grad, lr_table, step, valid, numel, steps_total, beta1, beta2, eps, weight_decay);
+}
+
 __global__ void adam_advance_kernel(int32_t* t_ctr, const int32_t* step, const int32_t* valid, int steps_total) {
     const int s = *step;
     if (s >= steps_total || (valid && valid[s] == 0)) return;
     *t_ctr = *t_ctr + 1;
+}
+
+// Slice blockIdx.y of n_sets: its own optimizer count, step counter and `valid` row.
+__global__ __launch_bounds__(256) void adam_sets_kernel(float* param, float* m, float* v, const int32_t* t_ctr, const float* grad, const float* lr_table,
+                                                        const int32_t* step, int64_t step_stride, const int32_t* valid, int64_t valid_stride,
+                                                        int64_t numel, int64_t set_stride, int steps_total, float beta1, float beta2, float eps,
+                                                        float weight_decay) {
+    const int64_t t = blockIdx.y, o = t * set_stride;
+    adam_elementwise_body(param + o, m + o, v + o, t_ctr + t, grad + o, lr_table, step + t * step_stride, valid ? valid + t * valid_stride : nullptr,
+                          numel, steps_total, beta1, beta2, eps, weight_decay);
+}
+
+__global__ void adam_sets_advance_kernel(int32_t* t_ctr, const int32_t* step, int64_t step_stride, const int32_t* valid, int64_t valid_stride,
+                                         int n_sets, int steps_total) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_sets) return;
+    const int s = step[t * step_stride];
+    if (s >= steps_total || (valid && valid[t * valid_stride + s] == 0)) return;
+    t_ctr[t] = t_ctr[t] + 1;
+}
+
+// ---------------------------------------------------------------------------------------------- sets
+// A set is one target's maps: map m has side tab.side[m] and starts tab.off[m] floats into the set, set t starts t * set_stride floats after
+// set 0.  The table travels by value in the kernel arguments (nothing is copied to the device).  A JOB is one (set, map); its scratch has
+// the per-map entry's layout (partials | stats | map pyramid | gradient pyramid) and starts tab.sc[m] doubles into the set's scratch.
+constexpr int SETS_MAX_MAPS = 32;
+
+struct SetTable {
+    int32_t n_maps;
+    int32_t side[SETS_MAX_MAPS];
+    int64_t off[SETS_MAX_MAPS];
+    int64_t sc[SETS_MAX_MAPS];
+};
+
+// The maps that have a pyramid level of the launch's side.
+struct LevelJobs {
+    int32_t n;
+    uint8_t map[SETS_MAX_MAPS];
+};
+
+__host__ __device__ __forceinline__ int map_levels(int side) {
+    int l = 1;
+    for (int s = side; s > 8; s >>= 1) ++l;
+    return l;
+}
+
+// Offset of level l >= 1 inside a map's pyramid (levels 1.. back to back).
+__host__ __device__ __forceinline__ int64_t pyramid_offset(int side, int l) {
+    int64_t o = 0;
+    for (int k = 1; k < l; ++k) o += (int64_t)(side >> k) * (side >> k);
+    return o;
+}
+
+__host__ __device__ __forceinline__ int level_parts(int s) {
+    const int64_t g = ((int64_t)(s / 2) * (s / 2) + 255) / 256;
+    return (int)(g > NO_PARTS ? NO_PARTS : g);
+}
+
+struct JobScratch {
+    double* partials;
+    double* stats;
+    double* xpyr;
+    double* gpyr;
+};
+
+__device__ __forceinline__ JobScratch job_scratch(double* sc, int side) {
+    const int levels = map_levels(side);
+    JobScratch j;
+    j.partials = sc;
+    j.stats = sc + (int64_t)levels * NO_PARTS * 2;
+    j.xpyr = j.stats + (int64_t)levels * 2;
+    j.gpyr = j.xpyr + pyramid_offset(side, levels);
+    return j;
+}
+
+// grid (partials of side s, sets x jobs.n): level `s` of every job that has one, each with the per-map kernel's grid.
+__global__ __launch_bounds__(256) void reg_sets_fwd_kernel(double* __restrict__ scratch, const float* __restrict__ x, SetTable tab, LevelJobs jobs,
+                                                           int64_t set_stride, int64_t set_doubles, int s) {
+    __shared__ double sh[4];
+    const int t = blockIdx.y / jobs.n, m = jobs.map[blockIdx.y % jobs.n];
+    const int side = tab.side[m], levels = map_levels(side);
+    int l = 0;
+    for (int q = side; q > s; q >>= 1) ++l;
+    const JobScratch js = job_scratch(scratch + (int64_t)t * set_doubles + tab.sc[m], side);
+    double* partials = js.partials + (int64_t)l * NO_PARTS * 2;
+    double* next = l + 1 < levels ? js.xpyr + pyramid_offset(side, l + 1) : nullptr;
+    if (l == 0)
+        reg_level_fwd_body<float>(partials, next, x + (int64_t)t * set_stride + tab.off[m], s, sh);
+    else
+        reg_level_fwd_body<double>(partials, next, js.xpyr + pyramid_offset(side, l), s, sh);
+}
+
+// One workgroup per job: its levels' statistics, and f32(scale * reg) of the map into the set's value row (vals[m], behind the jobs' scratch).
+__global__ __launch_bounds__(256) void reg_sets_finish_kernel(double* __restrict__ scratch, SetTable tab, int64_t set_doubles, int64_t vals_off,
+                                                              double scale) {
+    __shared__ double sh[4];
+    const int t = blockIdx.x / tab.n_maps, m = blockIdx.x % tab.n_maps;
+    const int side = tab.side[m], levels = map_levels(side);
+    double* set_sc = scratch + (int64_t)t * set_doubles;
+    const JobScratch js = job_scratch(set_sc + tab.sc[m], side);
+    double reg = 0.0;
+    for (int l = 0; l < levels; ++l) reg += reg_finish_level(js.stats, js.partials, l, level_parts(side >> l), side >> l, sh);
+    if (threadIdx.x == 0) set_sc[vals_off + m] = (double)(float)(scale * reg);
+}
+
+// grid (blocks of side s, sets x jobs.n): the gradient of level `s` of every job that has one.  With fold_value (the first of the backward
+// launches) one thread per set also adds the set's value row to value[t * value_stride], in float32 in table order.
+__global__ __launch_bounds__(256) void reg_sets_bwd_kernel(float* __restrict__ dx, float* value, int64_t value_stride, double* __restrict__ scratch,
+                                                           const float* __restrict__ x, SetTable tab, LevelJobs jobs, int64_t set_stride,
+                                                           int64_t set_doubles, int64_t vals_off, int s, double scale, int accumulate_dx,
+                                                           int accumulate_value, int fold_value) {
+    const int t = blockIdx.y / jobs.n, k = blockIdx.y % jobs.n, m = jobs.map[k];
+    const int side = tab.side[m], levels = map_levels(side);
+    double* set_sc = scratch + (int64_t)t * set_doubles;
+    if (fold_value && value && k == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+        float* dst = value + (int64_t)t * value_stride;
+        float acc = accumulate_value ? *dst : 0.f;
+        for (int i = 0; i < tab.n_maps; ++i) {
+            const float v = (float)set_sc[vals_off + i];
+            acc = (accumulate_value || i > 0) ? acc + v : v;
+        }
+        *dst = acc;
+    }
+    int l = 0;
+    for (int q = side; q > s; q >>= 1) ++l;
+    const JobScratch js = job_scratch(set_sc + tab.sc[m], side);
+    const double* gparent = l + 1 < levels ? js.gpyr + pyramid_offset(side, l + 1) : nullptr;
+    const int64_t o = (int64_t)t * set_stride + tab.off[m];
+    if (l == 0)
+        reg_level_bwd_body<float>((double*)nullptr, dx + o, x + o, gparent, js.stats, s, scale, accumulate_dx);
+    else
+        reg_level_bwd_body<double>(js.gpyr + pyramid_offset(side, l), (float*)nullptr, (const double*)(js.xpyr + pyramid_offset(side, l)), gparent,
+                                   js.stats + 2 * l, s, 1.0, 0);
+}
+
+__host__ __device__ __forceinline__ int norm_parts(int side) {
+    const int64_t g = ((int64_t)side * side + 1023) / 1024;
+    return (int)(g > NO_PARTS ? NO_PARTS : g);
+}
+
+// Block b of a set's row of blocks -> (map, block inside the map's norm_parts blocks).
+__device__ __forceinline__ int norm_job(const SetTable& tab, int b, int* bx) {
+    int m = 0;
+    for (; m + 1 < tab.n_maps; ++m) {
+        const int np = norm_parts(tab.side[m]);
+        if (b < np) break;
+        b -= np;
+    }
+    *bx = b;
+    return m;
+}
+
+// grid (sum of the maps' partial counts, sets); partials of job (t, m) at scratch[(t * n_maps + m) * NO_PARTS * 2].
+__global__ __launch_bounds__(256) void norm_sets_partial_kernel(double* __restrict__ scratch, const float* __restrict__ x, SetTable tab, int64_t set_stride) {
+    __shared__ double sh[4];
+    int bx;
+    const int t = blockIdx.y, m = norm_job(tab, blockIdx.x, &bx);
+    const int side = tab.side[m];
+    norm_partial_body(scratch + ((int64_t)t * tab.n_maps + m) * NO_PARTS * 2, x + (int64_t)t * set_stride + tab.off[m], (int64_t)side * side, bx,
+                      norm_parts(side), sh);
+}
+
+__global__ __launch_bounds__(256) void norm_sets_apply_kernel(float* __restrict__ x, const double* __restrict__ scratch, SetTable tab, int64_t set_stride,
+                                                              const int32_t* step, int64_t step_stride, const int32_t* valid, int64_t valid_stride,
+                                                              int steps_total) {
+    __shared__ double sh[4];
+    const int t = blockIdx.y;
+    if (!step_is_live(step ? step + t * step_stride : nullptr, valid ? valid + t * valid_stride : nullptr, steps_total)) return;   // (uniform over the block)
+    int bx;
+    const int m = norm_job(tab, blockIdx.x, &bx);
+    const int side = tab.side[m];
+    norm_apply_body(x + (int64_t)t * set_stride + tab.off[m], scratch + ((int64_t)t * tab.n_maps + m) * NO_PARTS * 2, norm_parts(side),
+                    (int64_t)side * side, bx, norm_parts(side), sh);
+}
+
+// dst, map-major and dense ([map][set][side^2]: what the generator's layers read, n_sets maps each), from the sets; tab.sc[m] = the floats
+// of the maps in front of m.  grid as norm_sets_partial_kernel.
+__global__ __launch_bounds__(256) void sets_pack_kernel(float* __restrict__ dst, const float* __restrict__ x, SetTable tab, int64_t set_stride) {
+    int bx;
+    const int t = blockIdx.y, m = norm_job(tab, blockIdx.x, &bx);
+    const int side = tab.side[m], gx = norm_parts(side);
+    const int64_t numel = (int64_t)side * side;
+    const float* src = x + (int64_t)t * set_stride + tab.off[m];
+    float* out = dst + (int64_t)gridDim.y * tab.sc[m] + (int64_t)t * numel;
+    for (int64_t i = (int64_t)bx * 256 + threadIdx.x; i < numel; i += (int64_t)gx * 256) out[i] = src[i];
+}
+
+// Check a map table and fill the kernels' copy.  0 with the error set, else 1.
+int sets_table(const char* who, const int64_t* offsets, const int32_t* sides, int32_t n_maps, int32_t n_sets, int64_t set_stride, SetTable* tab,
+               int64_t* jobs_doubles, int64_t* span = nullptr) {
+#define SETS_REQUIRE(cond, ...) do { if (!(cond)) { mgf_set_error(__VA_ARGS__); return 0; } } while (0)
+    SETS_REQUIRE(offsets && sides, "%s: null map table", who);
+    SETS_REQUIRE(n_maps >= 1 && n_maps <= SETS_MAX_MAPS, "%s: n_maps must lie in 1..%d (got %d)", who, SETS_MAX_MAPS, n_maps);
+    SETS_REQUIRE(n_sets >= 1 && (int64_t)n_sets * n_maps <= 65535, "%s: n_sets must be >= 1 and n_sets * n_maps <= 65535 (got %d sets)", who, n_sets);
+    int64_t extent = 0, sc = 0;
+    tab->n_maps = n_maps;
+    for (int m = 0; m < n_maps; ++m) {
+        RegLevels lv;
+        SETS_REQUIRE(reg_levels(sides[m], &lv), "%s: map %d: the side must be a power of two in 2..32768 (got %d)", who, m, sides[m]);
+        SETS_REQUIRE(offsets[m] >= 0, "%s: map %d: negative offset", who, m);
+        const int64_t end = offsets[m] + (int64_t)sides[m] * sides[m];
+        for (int k = 0; k < m; ++k)
+            SETS_REQUIRE(end <= offsets[k] || offsets[k] + (int64_t)sides[k] * sides[k] <= offsets[m], "%s: maps %d and %d overlap", who, k, m);
+        if (end > extent) extent = end;
+        tab->side[m] = sides[m];
+        tab->off[m] = offsets[m];
+        tab->sc[m] = sc;
+        sc += mgf_noise_regularize_scratch_bytes(sides[m]) / 8;
+    }
+    for (int m = n_maps; m < SETS_MAX_MAPS; ++m) { tab->side[m] = 0; tab->off[m] = 0; tab->sc[m] = 0; }
+    SETS_REQUIRE(set_stride >= extent, "%s: set_stride %lld is smaller than the table's extent %lld", who, (long long)set_stride, (long long)extent);
+#undef SETS_REQUIRE
+    *jobs_doubles = sc;
+    if (span) *span = (int64_t)(n_sets - 1) * set_stride + extent;          // floats from set 0's start to the end of the last set's maps
+    return 1;
 }
 
 }  // namespace
@@ -278,15 +560,7 @@ extern "C" int mgf_noise_grad_f32(float* dnoise, const float* dpre, const float*
     MGF_REQUIRE(hw <= ((int64_t)1 << 30), MGF_ETOOBIG, "noise_grad: map too large (%lld pixels)", (long long)hw);
     hipStream_t st = (hipStream_t)stream;
     const bool vec = hw % 4 == 0 && ((uintptr_t)dpre % 16) == 0 && ((uintptr_t)dnoise % 16) == 0;
-    if (vec) {
-        const int64_t groups = hw / 4;
-        if (groups >= 65536 || c < 16) launch_noise_grad<4, 1>(dnoise, dpre, strength, c, hw, accumulate, st);
-        else if (groups >= 16384 || c < 64) launch_noise_grad<4, 4>(dnoise, dpre, strength, c, hw, accumulate, st);
-        else launch_noise_grad<4, 16>(dnoise, dpre, strength, c, hw, accumulate, st);
-    } else {
-        if (c < 64) launch_noise_grad<1, 1>(dnoise, dpre, strength, c, hw, accumulate, st);
-        else launch_noise_grad<1, 16>(dnoise, dpre, strength, c, hw, accumulate, st);
-    }
+    choose_noise_grad(vec, dnoise, dpre, strength, c, hw, accumulate, st);
     MGF_CHECK_LAUNCH("noise_grad");
     return MGF_OK;
 }
@@ -372,5 +646,127 @@ extern "C" int mgf_adam_elementwise_f32(float* param, float* exp_avg, float* exp
                        (const int32_t*)adam_t, grad, lr_table, step, valid, numel, steps_total, beta1, beta2, eps, weight_decay);
     hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, st, adam_t, step, valid, steps_total);
     MGF_CHECK_LAUNCH("adam_elementwise");
+    return MGF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- sets: entries
+extern "C" int64_t mgf_noise_sets_scratch_bytes(const int32_t* sides, int32_t n_maps, int32_t n_sets) {
+    if (!sides || n_maps < 1 || n_maps > SETS_MAX_MAPS || n_sets < 1) return 0;
+    int64_t d = n_maps;                                     // the set's value row
+    for (int m = 0; m < n_maps; ++m) {
+        const int64_t b = mgf_noise_regularize_scratch_bytes(sides[m]);
+        if (!b) return 0;
+        d += b / 8;
+    }
+    return 8 * d * n_sets;                                  // (the normalisation's [sets][maps][NO_PARTS][2] partials fit: every job holds more)
+}
+
+extern "C" int mgf_noise_sets_regularize_grad_f32(float* dx, float* value, int64_t value_stride, const float* x, const int64_t* offsets,
+                                                  const int32_t* sides, int32_t n_maps, int32_t n_sets, int64_t set_stride, float scale,
+                                                  int32_t accumulate_dx, int32_t accumulate_value, void* scratch, mgf_stream_t stream) {
+    SetTable tab;
+    int64_t jobs_doubles = 0, span = 0;
+    MGF_REQUIRE(dx && x && scratch, MGF_EINVAL, "noise_sets_regularize_grad: null pointer");
+    MGF_REQUIRE(((uintptr_t)scratch % 8) == 0, MGF_EINVAL, "noise_sets_regularize_grad: scratch must be 8-byte aligned");
+    if (!sets_table("noise_sets_regularize_grad", offsets, sides, n_maps, n_sets, set_stride, &tab, &jobs_doubles, &span)) return MGF_EINVAL;
+    MGF_REQUIRE(dx + span <= x || x + span <= dx, MGF_EINVAL, "noise_sets_regularize_grad: dx must not alias x");
+    MGF_REQUIRE(!value || n_sets == 1 || value_stride >= 1, MGF_EINVAL, "noise_sets_regularize_grad: bad value_stride");
+    hipStream_t st = (hipStream_t)stream;
+    double* sc = (double*)scratch;
+    const int64_t set_doubles = jobs_doubles + n_maps, vals_off = jobs_doubles;
+    // the distinct pyramid sides, largest first, and the maps that have each
+    int32_t level_side[16];
+    LevelJobs jobs[16];
+    int nlev = 0;
+    for (int32_t s = 32768; s >= 2; s >>= 1) {
+        LevelJobs j;
+        j.n = 0;
+        for (int m = 0; m < n_maps; ++m)
+            if (s == sides[m] || (s >= 8 && s < sides[m])) j.map[j.n++] = (uint8_t)m;
+        for (int k = j.n; k < SETS_MAX_MAPS; ++k) j.map[k] = 0;
+        if (j.n) { level_side[nlev] = s; jobs[nlev++] = j; }
+    }
+    for (int i = 0; i < nlev; ++i)
+        hipLaunchKernelGGL(reg_sets_fwd_kernel, dim3(level_parts(level_side[i]), n_sets * jobs[i].n), dim3(256), 0, st, sc, x, tab, jobs[i], set_stride,
+                           set_doubles, level_side[i]);
+    hipLaunchKernelGGL(reg_sets_finish_kernel, dim3(n_sets * n_maps), dim3(256), 0, st, sc, tab, set_doubles, vals_off, (double)scale);
+    for (int i = nlev - 1; i >= 0; --i) {
+        const int s = level_side[i];
+        hipLaunchKernelGGL(reg_sets_bwd_kernel, dim3(mgf_stream_grid((int64_t)s * s, 256, 4), n_sets * jobs[i].n), dim3(256), 0, st, dx, value,
+                           value_stride, sc, x, tab, jobs[i], set_stride, set_doubles, vals_off, s, (double)scale, accumulate_dx, accumulate_value,
+                           (int)(i == nlev - 1));
+    }
+    MGF_CHECK_LAUNCH("noise_sets_regularize_grad");
+    return MGF_OK;
+}
+
+extern "C" int mgf_noise_sets_normalize_f32(float* x, const int64_t* offsets, const int32_t* sides, int32_t n_maps, int32_t n_sets, int64_t set_stride,
+                                            const int32_t* step, int64_t step_stride, const int32_t* valid, int64_t valid_stride,
+                                            int32_t steps_total, void* scratch, mgf_stream_t stream) {
+    SetTable tab;
+    int64_t jobs_doubles = 0;
+    MGF_REQUIRE(x && scratch, MGF_EINVAL, "noise_sets_normalize: null pointer");
+    MGF_REQUIRE(step || !valid, MGF_EINVAL, "noise_sets_normalize: a valid table needs the step counters");
+    MGF_REQUIRE(!step || steps_total >= 1, MGF_EINVAL, "noise_sets_normalize: bad steps_total");
+    MGF_REQUIRE(!step || (step_stride >= 0 && valid_stride >= 0), MGF_EINVAL, "noise_sets_normalize: negative stride");
+    MGF_REQUIRE(((uintptr_t)scratch % 8) == 0, MGF_EINVAL, "noise_sets_normalize: scratch must be 8-byte aligned");
+    if (!sets_table("noise_sets_normalize", offsets, sides, n_maps, n_sets, set_stride, &tab, &jobs_doubles)) return MGF_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    int blocks = 0;
+    for (int m = 0; m < n_maps; ++m) blocks += norm_parts(sides[m]);
+    hipLaunchKernelGGL(norm_sets_partial_kernel, dim3(blocks, n_sets), dim3(256), 0, st, (double*)scratch, (const float*)x, tab, set_stride);
+    hipLaunchKernelGGL(norm_sets_apply_kernel, dim3(blocks, n_sets), dim3(256), 0, st, x, (const double*)scratch, tab, set_stride, step, step_stride,
+                       valid, valid_stride, steps_total);
+    MGF_CHECK_LAUNCH("noise_sets_normalize");
+    return MGF_OK;
+}
+
+extern "C" int mgf_noise_sets_grad_f32(float* dnoise, int64_t dnoise_stride, const float* dpre, const float* strength, int32_t n, int32_t c, int64_t hw,
+                                       int32_t accumulate, mgf_stream_t stream) {
+    MGF_REQUIRE(dnoise && dpre && strength, MGF_EINVAL, "noise_sets_grad: null pointer");
+    MGF_REQUIRE(n >= 1 && n <= 65535 && c >= 1 && hw >= 1, MGF_EINVAL, "noise_sets_grad: bad sizes");
+    MGF_REQUIRE(hw <= ((int64_t)1 << 30), MGF_EINVAL, "noise_sets_grad: map too large (%lld pixels)", (long long)hw);
+    MGF_REQUIRE(dnoise_stride >= hw, MGF_EINVAL, "noise_sets_grad: dnoise_stride %lld is smaller than a map (%lld)", (long long)dnoise_stride,
+                (long long)hw);
+    const bool vec = hw % 4 == 0 && dnoise_stride % 4 == 0 && ((uintptr_t)dpre % 16) == 0 && ((uintptr_t)dnoise % 16) == 0;
+    choose_noise_grad(vec, dnoise, dpre, strength, c, hw, accumulate, (hipStream_t)stream, n, dnoise_stride);
+    MGF_CHECK_LAUNCH("noise_sets_grad");
+    return MGF_OK;
+}
+
+extern "C" int mgf_adam_sets_f32(float* param, float* exp_avg, float* exp_avg_sq, int32_t* adam_t, const float* grad, const float* lr_table,
+                                 const int32_t* step, int64_t step_stride, const int32_t* valid, int64_t valid_stride, int64_t numel, int32_t n_sets,
+                                 int64_t set_stride, int32_t steps_total, float beta1, float beta2, float eps, float weight_decay,
+                                 mgf_stream_t stream) {
+    MGF_REQUIRE(param && exp_avg && exp_avg_sq && adam_t && grad && lr_table && step, MGF_EINVAL, "adam_sets: null pointer");
+    MGF_REQUIRE(numel >= 1 && steps_total >= 1, MGF_EINVAL, "adam_sets: bad sizes");
+    MGF_REQUIRE(n_sets >= 1 && n_sets <= 65535, MGF_EINVAL, "adam_sets: n_sets must lie in 1..65535 (got %d)", n_sets);
+    MGF_REQUIRE(set_stride >= numel, MGF_EINVAL, "adam_sets: set_stride %lld is smaller than a slice (%lld)", (long long)set_stride, (long long)numel);
+    MGF_REQUIRE(step_stride >= 0 && valid_stride >= 0, MGF_EINVAL, "adam_sets: negative stride");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(adam_sets_kernel, dim3(mgf_stream_grid(numel, 256, 4), n_sets), dim3(256), 0, st, param, exp_avg, exp_avg_sq,
+                       (const int32_t*)adam_t, grad, lr_table, step, step_stride, valid, valid_stride, numel, set_stride, steps_total, beta1, beta2, eps,
+                       weight_decay);
+    hipLaunchKernelGGL(adam_sets_advance_kernel, dim3((n_sets + 255) / 256), dim3(256), 0, st, adam_t, step, step_stride, valid, valid_stride, n_sets,
+                       steps_total);
+    MGF_CHECK_LAUNCH("adam_sets");
+    return MGF_OK;
+}
+
+extern "C" int mgf_noise_sets_pack_f32(float* dst, const float* x, const int64_t* offsets, const int32_t* sides, int32_t n_maps, int32_t n_sets,
+                                       int64_t set_stride, mgf_stream_t stream) {
+    SetTable tab;
+    int64_t jobs_doubles = 0, span = 0, total = 0;
+    MGF_REQUIRE(dst && x, MGF_EINVAL, "noise_sets_pack: null pointer");
+    if (!sets_table("noise_sets_pack", offsets, sides, n_maps, n_sets, set_stride, &tab, &jobs_doubles, &span)) return MGF_EINVAL;
+    int blocks = 0;
+    for (int m = 0; m < n_maps; ++m) {
+        tab.sc[m] = total;                                  // (the pack kernel's reading of `sc`: floats of the maps in front of m)
+        total += (int64_t)sides[m] * sides[m];
+        blocks += norm_parts(sides[m]);
+    }
+    MGF_REQUIRE(dst + total * n_sets <= x || x + span <= dst, MGF_EINVAL, "noise_sets_pack: dst must not overlap x");
+    hipLaunchKernelGGL(sets_pack_kernel, dim3(blocks, n_sets), dim3(256), 0, (hipStream_t)stream, dst, x, tab, set_stride);
+    MGF_CHECK_LAUNCH("noise_sets_pack");
     return MGF_OK;
 }

@@ -637,7 +637,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     return out
 
 
-def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_weights=None, face_crops=None, **kw):
+def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_weights=None, face_crops=None, out_prefixes=None, **kw):
     """Pair-level sharding of BASELINE configs 3/5: rank r projects `targets[r::world]` (or, with dynamic=True, whatever the
     shared `distributed.WorkQueue` hands it), then ONE all_gather returns every item's {latent, loss, step} to every rank.
     targets: list of [1,3,S,S] device tensors (or image paths); landmarks: optional list of (lm_target, lm_steps) per item.
@@ -649,6 +649,10 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_w
     region_weights: one region weight [H,W] for every item, or a list with one per item (project_image's region_weight).
     face_crops: one face crop per item (project_image's face_crop: a [2,3] matrix or "landmarks"), set before the item is projected -- a
     re-targeted engine takes it in place, a lockstep group gets its items' matrices as one [B,2,3] stack.
+    optimize_noise=True with lockstep > 1: every target of a group optimises noise maps of its own (GradientProjectionEngine(
+    noise_per_target=True)).  The maps do not fit the fixed-width gather: with out_prefixes (one path prefix per item) the rank that projected
+    item i writes out_prefixes[i] + ".mat" (the latent and the best step's maps, save_latent_mat) and a PNG rendered with those maps, like
+    project_image's out_prefix; without out_prefixes the maps are dropped and only the gathered latents remain.
     Returns dict(latents [N,k,D], losses [N], steps [N], items [N]) ordered by item id, plus `mine`: the items this rank worked on."""
     if isinstance(region_weights, (list, tuple)) and len(region_weights) != len(targets):
         raise ValueError(f"project_many: {len(region_weights)} region weights for {len(targets)} targets")
@@ -656,6 +660,12 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_w
     if face_crops is not None and len(face_crops) != len(targets):
         raise ValueError(f"project_many: {len(face_crops)} face crops for {len(targets)} targets")
     fc = lambda i: {} if face_crops is None else {"face_crop": face_crops[i]}
+    if out_prefixes is not None:
+        if len(out_prefixes) != len(targets):
+            raise ValueError(f"project_many: {len(out_prefixes)} output prefixes for {len(targets)} targets")
+        if not (lockstep > 1 and kw.get("optimize_noise")):
+            raise ValueError("project_many: out_prefixes go with lockstep > 1 and optimize_noise=True (the per-target noise maps, which the "
+                             "gather does not carry); the latents of every other run are in the result")
     import torch.distributed as dist
     from .distributed import gather_many, pack_result, run_sharded, shard_items, unpack_results
     on = dist.is_available() and dist.is_initialized()
@@ -679,6 +689,12 @@ def project_many(G, targets, landmarks=None, dynamic=False, lockstep=1, region_w
                                  region_weight=None if region_weights is None else [rw(i) for i in ids],
                                  **({} if face_crops is None else {"face_crop": [face_crops[i] for i in ids]}), **kw)
             recs += [pack_result(res["w"][j:j + 1].to(G.device), float(res["loss"][j]), int(res["step"][j]), item=i) for j, i in enumerate(ids)]
+            if out_prefixes is not None:
+                ratio = (kw.get("args") or ProjectionArgs()).ratio
+                for j, i in enumerate(ids):
+                    maps = {name: t[None] for name, t in res["noises"][j].items()}
+                    save_latent_mat(f"{out_prefixes[i]}.mat", res["w"][j:j + 1], noises=maps)
+                    save_best_png(G, res["w"][j:j + 1], f"{out_prefixes[i]}.png", ratio, noises=maps)
         rows = torch.stack(recs) if recs else torch.empty([0, width], dtype=torch.float64, device=G.device)
         out = unpack_results(gather_many(rows, -(-len(targets) // world)), lshape)
         out["mine"] = list(mine)
@@ -724,7 +740,9 @@ def morph_pairs(G, pairs, src_dir, dst_raw, dst_morph, landmarks=None, truncatio
     whose morph exists are skipped (:352).  The 2 x len(pairs) projections are independent: `project_many` shards them over the ranks of the
     process group (static or, with dynamic=True, through the work queue) and gathers every latent to every rank; the renderings are then
     dealt `pairs[rank::world]`.  pairs: [(img1, img2)] file names under src_dir (read_pair_csv); landmarks: optional {file name: (lm_target,
-    lm_steps)}; project_kw: project_image's arguments (args, percept, biometric, gamma, batch, seed, mode, dynamic, ...).
+    lm_steps)}; project_kw: project_image's arguments (args, percept, biometric, gamma, batch, seed, mode, dynamic, ...) and project_many's
+    (lockstep; with lockstep > 1 also optimize_noise / noise_init: per-target noise maps, and out_prefixes, one per projected file in
+    pair order, to keep them -- the renderings here use `noise_mode`).
     Returns dict(pairs (the ones worked on), latents [2P,k,D] (W+: [2P,k,num_ws,D]), losses, steps, written (this rank's morph paths))."""
     import torch.distributed as dist
     from .distributed import shard_items
@@ -760,10 +778,13 @@ def morph_pairs(G, pairs, src_dir, dst_raw, dst_morph, landmarks=None, truncatio
 def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=None, latent_mean=None, latent_std=None, eps=None,
                    use_graph=True, noise_mode="random", use_mse=True, seed=None, weight_decay=0.0, mode="gradient", latent_space="z",
                    biometric=None, gamma=1.0, batch=None, pipeline=None, mdf=None, region_weight=None, face_crop=None,
-                   face_crop_filter="area", **unused):
+                   face_crop_filter="area", optimize_noise=False, noise_init="randn", **unused):
     """B targets through one lockstep GradientProjectionEngine; returns dict(w [B,k,D] (W+: [B,k,num_ws,D]), step [B], loss [B],
-    losses [B,steps])."""
+    losses [B,steps]).  optimize_noise: every target optimises its own noise maps (noise_per_target=True; the regulariser's weight is
+    args.noise_regularize), and the result gains `noises`: one {layer: [res, res]} dict per target, the maps of its best step's image."""
     args = args or ProjectionArgs()
+    if noise_init not in ("randn", "const"):
+        raise ValueError(f"noise_init must be 'randn' or 'const' (got {noise_init!r})")
     if mdf is not None:
         raise _lib.MgfError("project_many(lockstep > 1): the MDF objective runs one target per engine in gradient mode; use lockstep=1")
     if unused or pipeline:                          # (`batch` is literal mode's steps per forward: gradient mode evaluates one candidate per step; `pipeline` is literal mode's too)
@@ -787,11 +808,15 @@ def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=N
     eng = GradientProjectionEngine(G, tg, latent_mean, float(latent_std), args, weight_decay=weight_decay, percept=percept,
                                    lm_target=lm_t, lm_steps=lm_s, eps=eps, noise_mode=noise_mode, use_graph=use_graph, use_mse=use_mse,
                                    seed=0 if seed is None else seed, latent_space=latent_space, biometric=biometric, gamma=gamma,
-                                   region_weight=region_weight, face_crop=crop, face_crop_filter=face_crop_filter)
+                                   region_weight=region_weight, face_crop=crop, face_crop_filter=face_crop_filter,
+                                   **(dict(optimize_noise=True, noise_per_target=True, noise_init=noise_init) if optimize_noise else {}))
     w, step, loss, losses = eng.run().result()
+    out = {"w": w, "step": step, "loss": loss, "losses": losses}
     if len(targets) == 1:
-        return {"w": w, "step": np.array([step]), "loss": np.array([loss]), "losses": losses[None]}
-    return {"w": w, "step": step, "loss": loss, "losses": losses}
+        out = {"w": w, "step": np.array([step]), "loss": np.array([loss]), "losses": losses[None]}
+    if optimize_noise:
+        out["noises"] = [{name: t[j].clone() for name, t in eng.best_noises.items()} for j in range(len(targets))]
+    return out
 
 
 def warp_morphs(G, w1, w2, landmark1, landmark2, landmark_G=None, landmark_fn=None, out_dir=None, truncation_psi=0.7, noise_mode="random"):

@@ -234,14 +234,16 @@ class GeneratorGrad:
         if self.G.last_noise[0] == "none":
             raise _lib.MgfError("GeneratorGrad: dnoises needs a forward pass that adds noise (noise_mode='none' has no noise input)")
         _lib.require_gpu(out)
-        assert out.dtype == torch.float32 and out.is_contiguous()
+        # (a map per sample may be a strided view [n, h, w] of a larger buffer, every map dense: the lockstep engine's per-target maps)
+        per_sample = out.numel() == n * h * w and n > 1 and out.dim() == 3 and out[0].is_contiguous() and out.stride(0) >= h * w
+        assert out.dtype == torch.float32 and (out.is_contiguous() or per_sample)
         L, st = _lib.lib(), _lib.stream_ptr()
         if out.numel() == h * w:          # one map shared by the batch: the samples are further terms of the same sum
             _lib.check(L.mgf_noise_grad_f32(out.data_ptr(), dz.data_ptr(), lp.noise_strength.data_ptr(), n * c, h * w, 0, st), "noise_grad")
-        elif out.numel() == n * h * w:    # a map per sample
-            for j in range(n):
-                _lib.check(L.mgf_noise_grad_f32(out.reshape(n, -1)[j].data_ptr(), dz[j].data_ptr(), lp.noise_strength.data_ptr(), c, h * w, 0, st),
-                           "noise_grad")
+        elif out.numel() == n * h * w:    # a map per sample: one launch over the samples
+            stride = out.stride(0) if per_sample else h * w
+            _lib.check(L.mgf_noise_sets_grad_f32(out.data_ptr(), stride, dz.data_ptr(), lp.noise_strength.data_ptr(), n, c, h * w, 0, st),
+                       "noise_sets_grad")
         else:
             raise _lib.MgfError(f"GeneratorGrad: dnoises[{lp.name!r}] must hold one {h}x{w} map, or one per sample (got {tuple(out.shape)})")
 

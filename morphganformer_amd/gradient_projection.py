@@ -40,7 +40,7 @@ class GradientProjectionEngine(ProjectionEngine):
                  gamma=1.0, wing_kind="wing", landmark_model=None, betas=(0.9, 0.999), adam_eps=1e-8, weight_decay=0.0,
                  latent_space="z", mdf=None, optimize_noise=False, noise_init="randn", target_b=None, morph_alpha=0.5, id_balance=0.0,
                  id_metric="mse", lm_target_b=None, region_weight=None, face_crop=None, face_crop_target=None, face_crop_target_b=None,
-                 face_crop_filter="area", **ignored):
+                 face_crop_filter="area", noise_per_target=False, **ignored):
         """latent_space: "z" -- the drivers' parameter, the gradient runs on through the mapping network -- or "w+": the parameter is the
         per-layer intermediate latent ws [k, num_ws, D] itself (north_star: "backprops into the k-component latent W+"; layer `slot` reads
         ws[:, slot], networks.py:1252-1253), perturbed, descended by Adam and kept best-of exactly like z.  latent_mean is then a w-space
@@ -53,7 +53,16 @@ class GradientProjectionEngine(ProjectionEngine):
         engine-owned tensors (`noise_init`: "randn", seeded, or "const", a copy of every layer's noise_const) the generator runs with
         (`noise_mode` is then irrelevant), the total gains args.noise_regularize * sum over the maps of the regulariser, and every step the maps take
         an Adam step with the latent's learning rate and betas followed by noise_normalize_.  `noises` holds the current maps, `best_noises`
-        those of the best step's image ({layer name: [1, res, res]}), both filled inside the launch sequence.  One target per engine.
+        those of the best step's image ({layer name: [1, res, res]}), both filled inside the launch sequence.  One target per engine, unless
+
+        noise_per_target (with optimize_noise): every lockstep target owns a SET of maps.  The maps, their gradient, the Adam moments and the
+        best step's maps are [B, total] buffers (`noise_flat`, ...; a row is one target's maps back to back), `noises` / `best_noises` /
+        `dnoises` hold [B, res, res] views into them (row j: target j), the optimizer count is [B]; with noise_init="randn" target j draws
+        its maps under seed + 0x6E6F6973 + j (target 0: the one-target engine's draw), with "const" every target starts from the layers'
+        noise_const.  Regulariser, Adam and normalisation are one call each over all targets and maps (the mgf_noise_sets_* entries: a
+        launch count that depends on neither), each target gated by its own step counter and `valid` row; the generator reads a dense
+        per-layer copy of the maps ([B, res, res] per layer, one pack launch per step; B = 1 reads the maps themselves).  B = 1 is allowed
+        and gives the one-target engine's trajectory.
 
         region_weight: as ProjectionEngine's; with B lockstep targets one map for all of them or [B,1,H,W], one per target.  A target pair's
         constants (alpha (1 - alpha) LPIPS_W(Ta, Tb) and the same of the pixel term) use the weighted values.  The noise regulariser ignores it."""
@@ -64,9 +73,13 @@ class GradientProjectionEngine(ProjectionEngine):
             target, lm_target = pair["blend"], pair["lm_blend"]
         if noise_init not in ("randn", "const"):
             raise ValueError(f"noise_init must be 'randn' or 'const' (got {noise_init!r})")
-        if optimize_noise and int(target.shape[0]) > 1:
+        if noise_per_target and not optimize_noise:
+            raise ValueError("GradientProjectionEngine: noise_per_target=True gives every lockstep target its own noise maps to optimise: pass "
+                             "optimize_noise=True with it")
+        if optimize_noise and int(target.shape[0]) > 1 and not noise_per_target:
             raise _lib.MgfError("GradientProjectionEngine: optimize_noise runs with one target per engine (lockstep targets share one generator "
-                                "forward, whose noise maps are shared by the batch; per-target maps are not built); project the targets one after the other")
+                                "forward, whose noise maps are shared by the batch; per-target maps are not built); project the targets one after the other"
+                                " -- or pass noise_per_target=True: a set of maps per target")
         if mdf is not None and not getattr(mdf, "differentiable", False):
             raise _lib.MgfError("GradientProjectionEngine: this MDF loss was built without its backward pass -- build it with "
                                 "mdf.MDFLoss(..., differentiable=True) for gradient mode (ProjectionEngine(mdf=...), the literal loop, takes either)")
@@ -88,7 +101,8 @@ class GradientProjectionEngine(ProjectionEngine):
         B = int(target.shape[0])
         assert B == 1 or (landmark_fn is None and landmark_model is None), "landmark detectors are wired for one target per engine"
         self.pair, self.id_trace, self.optimize_noise = pair, None, bool(optimize_noise)
-        self.noises = self.best_noises = self.noise_slot = None
+        self.noise_per_target = bool(noise_per_target)
+        self.noises = self.best_noises = self.noise_slot = self.noise_slots = None
         # one candidate per target and step, nothing pipelined, no improvement trail; B > 1 targets get a row each of the loop state (_init_state)
         super().__init__(G, target, latent_mean, latent_std, args, percept=percept, use_mse=use_mse, lm_target=lm_target,
                          lm_steps=lm_steps, lm_valid=lm_valid, eps=eps, noise_mode=noise_mode, seed=seed, use_graph=use_graph, batch=1,
@@ -111,7 +125,9 @@ class GradientProjectionEngine(ProjectionEngine):
         self.exp_avg_sq = self._reg(torch.zeros_like(self.latent_in))
         self.adam_t = self._reg(torch.zeros(B, dtype=torch.int32, device=dev))
         self.dimg = torch.zeros_like(self.target)
-        if self.optimize_noise:
+        if self.noise_per_target:
+            self._init_noise_sets(noise_init, seed)
+        elif self.optimize_noise:
             self._init_noise(noise_init, seed)
         if pair is not None:
             self._init_pair(float(id_balance), id_metric)
@@ -244,6 +260,87 @@ class GradientProjectionEngine(ProjectionEngine):
                                                        float(a.noise_regularize), 1, int(has_p or i > 0), self.noise_reg_scratch.data_ptr(), st),
                        "noise_regularize_grad")
 
+    def _init_noise_sets(self, noise_init, seed):
+        """A set of maps per lockstep target: [B, total] buffers for the maps, their gradient, the two Adam moments and the best step's maps,
+        [B, res, res] views per layer, and the map table (sides and offsets inside a row) the mgf_noise_sets_* entries take."""
+        G, dev, L, B = self.G, self.device, _lib.lib(), self.targets
+        layers = [lp for lp in G.plan.layers if lp.noise_strength is not None]
+        total = sum(lp.res * lp.res for lp in layers)
+        z = lambda: torch.zeros(B, total, dtype=torch.float32, device=dev)
+        self.noise_flat, self.noise_grad, self.noise_m, self.noise_v = self._reg(z()), z(), self._reg(z()), self._reg(z())
+        self.best_noise_flat = self._reg(z(), 0)
+        if noise_init == "randn":                   # (target 0: the one-target engine's draw)
+            for j in range(B):
+                self.noise_flat[j].copy_(seeded_randn((total,), dev, int(seed) + 0x6E6F6973 + j))
+        self.noises, self.best_noises, self.dnoises, self.noise_layers = {}, {}, {}, []
+        # what the generator reads: B dense maps per layer.  One target: the maps themselves
+        self.noise_dense = torch.zeros(B * total, dtype=torch.float32, device=dev) if B > 1 else None
+        self.gen_noises = {} if B > 1 else self.noises
+        off, offsets = 0, []
+        for lp in layers:
+            r = lp.res
+            if noise_init == "const":
+                self.noise_flat[:, off:off + r * r].copy_(lp.noise_const.reshape(1, -1).expand(B, -1))
+            view = lambda t: t[:, off:off + r * r].view(B, r, r)
+            self.noises[lp.name], self.best_noises[lp.name], self.dnoises[lp.name] = view(self.noise_flat), view(self.best_noise_flat), view(self.noise_grad)
+            if B > 1:
+                self.gen_noises[lp.name] = self.noise_dense[B * off:B * (off + r * r)].view(B, r, r)
+            self.noise_layers.append((lp.name, r))
+            offsets.append(off)
+            off += r * r
+        self.noise_total = total
+        self.noise_sides, self.noise_offsets, self.noise_maps = _lib.map_table([r for _, r in self.noise_layers], offsets)
+        self.noise_adam_t = self._reg(torch.zeros(B, dtype=torch.int32, device=dev))
+        self.noise_ctr = torch.zeros(B, dtype=torch.int32, device=dev)      # the step counters as they stood before select_best advanced them
+        # target j's improvement flag (see _init_noise); `noise_slot` stays target 0's
+        self.noise_slots = [ImprovementSlot(1, 1, dev) for _ in range(B)]
+        self.noise_slot = self.noise_slots[0]
+        for slot in self.noise_slots:
+            self._table += slot.state(with_take=True)
+        nbytes = int(L.mgf_noise_sets_scratch_bytes(self.noise_sides, self.noise_maps, B))
+        if nbytes <= 0:
+            raise _lib.MgfError(f"GradientProjectionEngine: noise_per_target: the set kernels do not take this generator's maps (sides "
+                                f"{[r for _, r in self.noise_layers]}: at most 32 maps, powers of two)")
+        self.noise_sets_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        self.gg.noise_grads = True
+
+    def _valid_rows(self):
+        """(pointer, row stride) of the `valid` table as the set kernels take it: a row per target."""
+        if self.valid is None:
+            return 0, 0
+        return self.valid.data_ptr(), (int(self.valid.shape[-1]) if self.targets > 1 else 0)
+
+    def _noise_sets_pack(self):
+        """The generator's dense per-layer maps from the targets' sets (B > 1; in front of the forward pass, so that maps written from outside
+        between steps count, like the one-target engine's)."""
+        if self.noise_dense is not None:
+            _lib.check(_lib.lib().mgf_noise_sets_pack_f32(self.noise_dense.data_ptr(), self.noise_flat.data_ptr(), self.noise_offsets, self.noise_sides,
+                                                          self.noise_maps, self.targets, self.noise_total, _lib.stream_ptr()), "noise_sets_pack")
+
+    def _noise_sets_regularize(self, has_p):
+        """_noise_regularize for every target in one call: p_loss[j] (+)= the weighted regulariser of target j's maps, added map after map in
+        float32 like the loop above forms it, and noise_grad += its gradient."""
+        _lib.check(_lib.lib().mgf_noise_sets_regularize_grad_f32(
+            self.noise_grad.data_ptr(), self.p_loss.data_ptr(), 1, self.noise_flat.data_ptr(), self.noise_offsets, self.noise_sides, self.noise_maps,
+            self.targets, self.noise_total, float(self.args.noise_regularize), 1, int(has_p), self.noise_sets_scratch.data_ptr(), _lib.stream_ptr()),
+            "noise_sets_regularize_grad")
+
+    def _noise_sets_update(self):
+        """_noise_update for every target: keep the maps of each improving target, one Adam call, one normalise call; a target's skipped step
+        moves none of its maps (its own counter and `valid` row gate its slices)."""
+        L, st, B = _lib.lib(), _lib.stream_ptr(), self.targets
+        for j in range(B):
+            _lib.check(L.mgf_keep_improvements(self.best_noise_flat[j].data_ptr(), self.noise_flat[j].data_ptr(), self.noise_total,
+                                               self.noise_slots[j].take.data_ptr(), 1, st), "keep_improvements(noise maps)")
+        vptr, vstride = self._valid_rows()
+        _lib.check(L.mgf_adam_sets_f32(self.noise_flat.data_ptr(), self.noise_m.data_ptr(), self.noise_v.data_ptr(), self.noise_adam_t.data_ptr(),
+                                       self.noise_grad.data_ptr(), self.lr_table.data_ptr(), self.noise_ctr.data_ptr(), 1, vptr, vstride,
+                                       self.noise_total, B, self.noise_total, self.steps, float(self.betas[0]), float(self.betas[1]), self.adam_eps,
+                                       self.weight_decay, st), "adam_sets")
+        _lib.check(L.mgf_noise_sets_normalize_f32(self.noise_flat.data_ptr(), self.noise_offsets, self.noise_sides, self.noise_maps, B,
+                                                  self.noise_total, self.noise_ctr.data_ptr(), 1, vptr, vstride, self.steps,
+                                                  self.noise_sets_scratch.data_ptr(), st), "noise_sets_normalize")
+
     # The three points at which a subclass couples the rows (demorph.DemorphEngine: rows that are linear mixes of parameters).  Here a row IS
     # a parameter: the hooks add no launch and reorder none.
     def _make_rows(self):
@@ -269,13 +366,17 @@ class GradientProjectionEngine(ProjectionEngine):
                                            self.adam_eps, self.weight_decay, st), "adam_step")
             if self.use_wing:
                 _wing_into(self.wing_kind, self.w_loss[j:], self.lm_tables[j], self.lm_target[j] if B > 1 else self.lm_target, 1, ctr)
-            self._select_best(self.latent_n[j:], 1, self.noise_slot, row=j, valid=valid, has_p=has_p)
+            slot = self.noise_slots[j] if self.noise_slots is not None else self.noise_slot
+            self._select_best(self.latent_n[j:], 1, slot, row=j, valid=valid, has_p=has_p)
 
     def _iteration(self):
         a, B = self.args, self.targets
         rows = self._make_rows()
         opt_noise = self.optimize_noise
-        nkw = dict(noise_mode="inject", noises=self.noises) if opt_noise else dict(noise_mode=self.noise_mode)
+        sets = self.noise_per_target
+        if sets:
+            self._noise_sets_pack()
+        nkw = dict(noise_mode="inject", noises=self.gen_noises if sets else self.noises) if opt_noise else dict(noise_mode=self.noise_mode)
         if self.latent_space == "w+":
             img = self.gg.forward(ws=rows, **nkw)                                 # [B, k, num_ws, D]: every layer reads its own slot
         else:
@@ -306,11 +407,11 @@ class GradientProjectionEngine(ProjectionEngine):
         dz = self._apply_row_gradients(dz)
         has_p = self.has_p or opt_noise
         if opt_noise:
-            self._noise_regularize(self.has_p)
+            (self._noise_sets_regularize if sets else self._noise_regularize)(self.has_p)
             self.noise_ctr.copy_(self.step_ctr)
         self._bookkeeping(dz, has_p)
         if opt_noise:
-            self._noise_update()
+            (self._noise_sets_update if sets else self._noise_update)()
         return img
 
     def result(self):
