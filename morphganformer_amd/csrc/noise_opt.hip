@@ -81,34 +81,24 @@ __device__ __forceinline__ void noise_grad_body(float* __restrict__ dnoise, cons
     }
 }
 
-template <int V, int S>
-__global__ __launch_bounds__(256) void noise_grad_kernel(float* __restrict__ dnoise, const float* __restrict__ dpre, const float* __restrict__ strength,
-                                                         int c, int64_t hw, int accumulate) {
-    noise_grad_body<V, S>(dnoise, dpre, strength, c, hw, accumulate);
-}
-
-// The same body for sample blockIdx.y of dpre [n, c, hw], into that sample's own map.
+// Sample blockIdx.y of dpre [n, c, hw], into that sample's own map (one map: n = 1).
 template <int V, int S>
 __global__ __launch_bounds__(256) void noise_sets_grad_kernel(float* __restrict__ dnoise, int64_t dnoise_stride, const float* __restrict__ dpre,
                                                               const float* __restrict__ strength, int c, int64_t hw, int accumulate) {
     noise_grad_body<V, S>(dnoise + (int64_t)blockIdx.y * dnoise_stride, dpre + (int64_t)blockIdx.y * c * hw, strength, c, hw, accumulate);
 }
 
-// n == 0: the per-map kernel; n >= 1: the per-sample one over n samples.
 template <int V, int S>
-void launch_noise_grad(float* dnoise, const float* dpre, const float* strength, int c, int64_t hw, int accumulate, hipStream_t st, int n = 0,
-                       int64_t dnoise_stride = 0) {
+void launch_noise_grad(float* dnoise, const float* dpre, const float* strength, int c, int64_t hw, int accumulate, hipStream_t st, int n,
+                       int64_t dnoise_stride) {
     const int64_t groups = hw / V;
     const int grid = (int)mgf_cdiv(groups, 256 / S);
-    if (n == 0)
-        hipLaunchKernelGGL((noise_grad_kernel<V, S>), dim3(grid), dim3(256), 0, st, dnoise, dpre, strength, c, hw, accumulate);
-    else
-        hipLaunchKernelGGL((noise_sets_grad_kernel<V, S>), dim3(grid, n), dim3(256), 0, st, dnoise, dnoise_stride, dpre, strength, c, hw, accumulate);
+    hipLaunchKernelGGL((noise_sets_grad_kernel<V, S>), dim3(grid, n), dim3(256), 0, st, dnoise, dnoise_stride, dpre, strength, c, hw, accumulate);
 }
 
-// The slice form for a layer of c channels and hw pixels (vec: float4 loads are possible).
+// The slice form for n samples of a layer of c channels and hw pixels (vec: float4 loads are possible).
 void choose_noise_grad(bool vec, float* dnoise, const float* dpre, const float* strength, int c, int64_t hw, int accumulate, hipStream_t st,
-                       int n = 0, int64_t dnoise_stride = 0) {
+                       int n, int64_t dnoise_stride) {
     if (vec) {
         const int64_t groups = hw / 4;
         if (groups >= 65536 || c < 16) launch_noise_grad<4, 1>(dnoise, dpre, strength, c, hw, accumulate, st, n, dnoise_stride);
@@ -324,19 +314,7 @@ __device__ __forceinline__ void adam_elementwise_body(float* param, float* m, fl
     }
 }
 
-__global__ __launch_bounds__(256) void adam_elementwise_kernel(float* param, float* m, float* v, const int32_t* t_ctr, const float* grad,
-                                                               const float* lr_table, const int32_t* step, const int32_t* valid, int64_t numel,
-                                                               int steps_total, float beta1, float beta2, float eps, float weight_decay) {
-    adam_elementwise_body(param, m, v, t_ctr, grad, lr_table, step, valid, numel, steps_total, beta1, beta2, eps, weight_decay);
-}
-
-__global__ void adam_advance_kernel(int32_t* t_ctr, const int32_t* step, const int32_t* valid, int steps_total) {
-    const int s = *step;
-    if (s >= steps_total || (valid && valid[s] == 0)) return;
-    *t_ctr = *t_ctr + 1;
-}
-
-// Slice blockIdx.y of n_sets: its own optimizer count, step counter and `valid` row.
+// Slice blockIdx.y of n_sets: its own optimizer count, step counter and `valid` row (one slice: n_sets = 1, strides 0).
 __global__ __launch_bounds__(256) void adam_sets_kernel(float* param, float* m, float* v, const int32_t* t_ctr, const float* grad, const float* lr_table,
                                                         const int32_t* step, int64_t step_stride, const int32_t* valid, int64_t valid_stride,
                                                         int64_t numel, int64_t set_stride, int steps_total, float beta1, float beta2, float eps,
@@ -353,6 +331,15 @@ __global__ void adam_sets_advance_kernel(int32_t* t_ctr, const int32_t* step, in
     const int s = step[t * step_stride];
     if (s >= steps_total || (valid && valid[t * valid_stride + s] == 0)) return;
     t_ctr[t] = t_ctr[t] + 1;
+}
+
+void launch_adam_sets(float* param, float* m, float* v, int32_t* t_ctr, const float* grad, const float* lr_table, const int32_t* step,
+                      int64_t step_stride, const int32_t* valid, int64_t valid_stride, int64_t numel, int n_sets, int64_t set_stride, int steps_total,
+                      float beta1, float beta2, float eps, float weight_decay, hipStream_t st) {
+    hipLaunchKernelGGL(adam_sets_kernel, dim3(mgf_stream_grid(numel, 256, 4), n_sets), dim3(256), 0, st, param, m, v, (const int32_t*)t_ctr, grad,
+                       lr_table, step, step_stride, valid, valid_stride, numel, set_stride, steps_total, beta1, beta2, eps, weight_decay);
+    hipLaunchKernelGGL(adam_sets_advance_kernel, dim3((n_sets + 255) / 256), dim3(256), 0, st, t_ctr, step, step_stride, valid, valid_stride, n_sets,
+                       steps_total);
 }
 
 // ---------------------------------------------------------------------------------------------- sets
@@ -560,7 +547,7 @@ extern "C" int mgf_noise_grad_f32(float* dnoise, const float* dpre, const float*
     MGF_REQUIRE(hw <= ((int64_t)1 << 30), MGF_ETOOBIG, "noise_grad: map too large (%lld pixels)", (long long)hw);
     hipStream_t st = (hipStream_t)stream;
     const bool vec = hw % 4 == 0 && ((uintptr_t)dpre % 16) == 0 && ((uintptr_t)dnoise % 16) == 0;
-    choose_noise_grad(vec, dnoise, dpre, strength, c, hw, accumulate, st);
+    choose_noise_grad(vec, dnoise, dpre, strength, c, hw, accumulate, st, 1, hw);
     MGF_CHECK_LAUNCH("noise_grad");
     return MGF_OK;
 }
@@ -641,10 +628,8 @@ extern "C" int mgf_adam_elementwise_f32(float* param, float* exp_avg, float* exp
                                         float eps, float weight_decay, mgf_stream_t stream) {
     MGF_REQUIRE(param && exp_avg && exp_avg_sq && adam_t && grad && lr_table && step, MGF_EINVAL, "adam_elementwise: null pointer");
     MGF_REQUIRE(numel >= 1 && steps_total >= 1, MGF_EINVAL, "adam_elementwise: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(adam_elementwise_kernel, dim3(mgf_stream_grid(numel, 256, 4)), dim3(256), 0, st, param, exp_avg, exp_avg_sq,
-                       (const int32_t*)adam_t, grad, lr_table, step, valid, numel, steps_total, beta1, beta2, eps, weight_decay);
-    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, st, adam_t, step, valid, steps_total);
+    launch_adam_sets(param, exp_avg, exp_avg_sq, adam_t, grad, lr_table, step, 0, valid, 0, numel, 1, numel, steps_total, beta1, beta2, eps,
+                     weight_decay, (hipStream_t)stream);
     MGF_CHECK_LAUNCH("adam_elementwise");
     return MGF_OK;
 }
@@ -743,12 +728,8 @@ extern "C" int mgf_adam_sets_f32(float* param, float* exp_avg, float* exp_avg_sq
     MGF_REQUIRE(n_sets >= 1 && n_sets <= 65535, MGF_EINVAL, "adam_sets: n_sets must lie in 1..65535 (got %d)", n_sets);
     MGF_REQUIRE(set_stride >= numel, MGF_EINVAL, "adam_sets: set_stride %lld is smaller than a slice (%lld)", (long long)set_stride, (long long)numel);
     MGF_REQUIRE(step_stride >= 0 && valid_stride >= 0, MGF_EINVAL, "adam_sets: negative stride");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(adam_sets_kernel, dim3(mgf_stream_grid(numel, 256, 4), n_sets), dim3(256), 0, st, param, exp_avg, exp_avg_sq,
-                       (const int32_t*)adam_t, grad, lr_table, step, step_stride, valid, valid_stride, numel, set_stride, steps_total, beta1, beta2, eps,
-                       weight_decay);
-    hipLaunchKernelGGL(adam_sets_advance_kernel, dim3((n_sets + 255) / 256), dim3(256), 0, st, adam_t, step, step_stride, valid, valid_stride, n_sets,
-                       steps_total);
+    launch_adam_sets(param, exp_avg, exp_avg_sq, adam_t, grad, lr_table, step, step_stride, valid, valid_stride, numel, n_sets, set_stride,
+                     steps_total, beta1, beta2, eps, weight_decay, (hipStream_t)stream);
     MGF_CHECK_LAUNCH("adam_sets");
     return MGF_OK;
 }

@@ -53,16 +53,17 @@ class GradientProjectionEngine(ProjectionEngine):
         engine-owned tensors (`noise_init`: "randn", seeded, or "const", a copy of every layer's noise_const) the generator runs with
         (`noise_mode` is then irrelevant), the total gains args.noise_regularize * sum over the maps of the regulariser, and every step the maps take
         an Adam step with the latent's learning rate and betas followed by noise_normalize_.  `noises` holds the current maps, `best_noises`
-        those of the best step's image ({layer name: [1, res, res]}), both filled inside the launch sequence.  One target per engine, unless
+        those of the best step's image ({layer name: [B, res, res]}, row j: target j), both filled inside the launch sequence.  Every target
+        owns a SET of maps (one target: a set of one): the maps, their gradient, the Adam moments and the best step's maps are [B, total]
+        buffers (`noise_flat`, ...; a row is one target's maps back to back), `noises` / `best_noises` / `dnoises` hold views into them, the
+        optimizer count is [B]; with noise_init="randn" target j draws its maps under seed + 0x6E6F6973 + j, with "const" every target
+        starts from the layers' noise_const.  Regulariser, Adam and normalisation are one call each over all targets and maps (the
+        mgf_noise_sets_* entries: a launch count that depends on neither), each target gated by its own step counter and `valid` row; with
+        B > 1 the generator reads a dense per-layer copy of the maps ([B, res, res] per layer, one pack launch per step), with B = 1 the
+        maps themselves.
 
-        noise_per_target (with optimize_noise): every lockstep target owns a SET of maps.  The maps, their gradient, the Adam moments and the
-        best step's maps are [B, total] buffers (`noise_flat`, ...; a row is one target's maps back to back), `noises` / `best_noises` /
-        `dnoises` hold [B, res, res] views into them (row j: target j), the optimizer count is [B]; with noise_init="randn" target j draws
-        its maps under seed + 0x6E6F6973 + j (target 0: the one-target engine's draw), with "const" every target starts from the layers'
-        noise_const.  Regulariser, Adam and normalisation are one call each over all targets and maps (the mgf_noise_sets_* entries: a
-        launch count that depends on neither), each target gated by its own step counter and `valid` row; the generator reads a dense
-        per-layer copy of the maps ([B, res, res] per layer, one pack launch per step; B = 1 reads the maps themselves).  B = 1 is allowed
-        and gives the one-target engine's trajectory.
+        noise_per_target (with optimize_noise): B > 1 lockstep targets optimise noise maps only when this says so (each then fits its OWN
+        maps; maps shared by the batch are not built).  With one target the keyword changes nothing.
 
         region_weight: as ProjectionEngine's; with B lockstep targets one map for all of them or [B,1,H,W], one per target.  A target pair's
         constants (alpha (1 - alpha) LPIPS_W(Ta, Tb) and the same of the pixel term) use the weighted values.  The noise regulariser ignores it."""
@@ -101,7 +102,6 @@ class GradientProjectionEngine(ProjectionEngine):
         B = int(target.shape[0])
         assert B == 1 or (landmark_fn is None and landmark_model is None), "landmark detectors are wired for one target per engine"
         self.pair, self.id_trace, self.optimize_noise = pair, None, bool(optimize_noise)
-        self.noise_per_target = bool(noise_per_target)
         self.noises = self.best_noises = self.noise_slot = self.noise_slots = None
         # one candidate per target and step, nothing pipelined, no improvement trail; B > 1 targets get a row each of the loop state (_init_state)
         super().__init__(G, target, latent_mean, latent_std, args, percept=percept, use_mse=use_mse, lm_target=lm_target,
@@ -125,9 +125,7 @@ class GradientProjectionEngine(ProjectionEngine):
         self.exp_avg_sq = self._reg(torch.zeros_like(self.latent_in))
         self.adam_t = self._reg(torch.zeros(B, dtype=torch.int32, device=dev))
         self.dimg = torch.zeros_like(self.target)
-        if self.noise_per_target:
-            self._init_noise_sets(noise_init, seed)
-        elif self.optimize_noise:
+        if self.optimize_noise:
             self._init_noise(noise_init, seed)
         if pair is not None:
             self._init_pair(float(id_balance), id_metric)
@@ -205,71 +203,16 @@ class GradientProjectionEngine(ProjectionEngine):
         return super().retarget(*args, **kw)
 
     def _init_noise(self, noise_init, seed):
-        """The noise maps as parameters: ONE flat buffer each for the maps, their gradient, the two Adam moments and the best step's maps
-        (Adam is elementwise: one launch moves all of them), per-layer views for the generator, the backward pass and the per-map kernels."""
-        G, dev, L = self.G, self.device, _lib.lib()
-        layers = [lp for lp in G.plan.layers if lp.noise_strength is not None]
-        total = sum(lp.res * lp.res for lp in layers)
-        z = lambda: torch.zeros(total, dtype=torch.float32, device=dev)
-        self.noise_flat, self.noise_grad, self.noise_m, self.noise_v = self._reg(z()), z(), self._reg(z()), self._reg(z())
-        self.best_noise_flat = self._reg(z(), 0)
-        if noise_init == "randn":                   # (a stream of its own, not the head of the latent's eps stream)
-            self.noise_flat.copy_(seeded_randn((total,), dev, int(seed) + 0x6E6F6973))
-        self.noises, self.best_noises, self.dnoises, self.noise_layers = {}, {}, {}, []
-        off = 0
-        for lp in layers:
-            r = lp.res
-            if noise_init == "const":
-                self.noise_flat[off:off + r * r].copy_(lp.noise_const.reshape(-1))
-            self.noises[lp.name] = self.noise_flat[off:off + r * r].view(1, r, r)
-            self.best_noises[lp.name] = self.best_noise_flat[off:off + r * r].view(1, r, r)
-            self.dnoises[lp.name] = self.noise_grad[off:off + r * r].view(1, r, r)
-            self.noise_layers.append((lp.name, r))
-            off += r * r
-        self.noise_adam_t = self._reg(torch.zeros(1, dtype=torch.int32, device=dev))
-        self.noise_ctr = torch.zeros(1, dtype=torch.int32, device=dev)      # the step counter as it stood before select_best advanced it
-        # the improvement flag of select_best: take[0] = 0 where this step improved, else -1 (_noise_update reads it after the launch that wrote it)
-        self.noise_slot = ImprovementSlot(1, 1, dev)
-        self._table += self.noise_slot.state(with_take=True)
-        nbytes = max(int(L.mgf_noise_regularize_scratch_bytes(r)) for _, r in self.noise_layers)
-        self.noise_reg_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        self.noise_norm_scratch = torch.empty(int(L.mgf_noise_normalize_scratch_bytes()) // 8, dtype=torch.float64, device=dev)
-        self.gg.noise_grads = True
-
-    def _noise_update(self):
-        """After select_best: keep the maps of an improving step (they still are the ones its image was generated with), then move them --
-        Adam on d total / d maps = the generator's d<img, dimg>/d maps (already in noise_grad) + noise_regularize * d reg / d maps, then
-        noise_normalize_ per map; a skipped step moves nothing (every kernel reads the step counter and the `valid` table itself)."""
-        L, st, a = _lib.lib(), _lib.stream_ptr(), self.args
-        _lib.check(L.mgf_keep_improvements(self.best_noise_flat.data_ptr(), self.noise_flat.data_ptr(), self.noise_flat.numel(),
-                                           self.noise_slot.take.data_ptr(), 1, st), "keep_improvements(noise maps)")
-        _lib.check(L.mgf_adam_elementwise_f32(self.noise_flat.data_ptr(), self.noise_m.data_ptr(), self.noise_v.data_ptr(),
-                                              self.noise_adam_t.data_ptr(), self.noise_grad.data_ptr(), self.lr_table.data_ptr(),
-                                              self.noise_ctr.data_ptr(), _lib.ptr(self.valid), self.noise_flat.numel(), self.steps,
-                                              float(self.betas[0]), float(self.betas[1]), self.adam_eps, self.weight_decay, st), "adam_elementwise")
-        for name, r in self.noise_layers:
-            _lib.check(L.mgf_noise_normalize_f32(self.noises[name].data_ptr(), r * r, self.noise_ctr.data_ptr(), _lib.ptr(self.valid), self.steps,
-                                                 self.noise_norm_scratch.data_ptr(), st), "noise_normalize")
-
-    def _noise_regularize(self, has_p):
-        """p_loss (+)= noise_regularize * sum_maps reg and noise_grad += noise_regularize * d reg / d maps, map after map on one stream (the
-        regulariser rides in the float32 p_loss slot like the biometric and MDF terms; select_best forms the total in float64)."""
-        L, st, a = _lib.lib(), _lib.stream_ptr(), self.args
-        for i, (name, r) in enumerate(self.noise_layers):
-            _lib.check(L.mgf_noise_regularize_grad_f32(self.dnoises[name].data_ptr(), self.p_loss.data_ptr(), self.noises[name].data_ptr(), r,
-                                                       float(a.noise_regularize), 1, int(has_p or i > 0), self.noise_reg_scratch.data_ptr(), st),
-                       "noise_regularize_grad")
-
-    def _init_noise_sets(self, noise_init, seed):
-        """A set of maps per lockstep target: [B, total] buffers for the maps, their gradient, the two Adam moments and the best step's maps,
-        [B, res, res] views per layer, and the map table (sides and offsets inside a row) the mgf_noise_sets_* entries take."""
+        """The noise maps as parameters, a SET of maps per target (one target: a set of one): [B, total] buffers for the maps, their gradient,
+        the two Adam moments and the best step's maps (a row is one target's maps back to back), [B, res, res] views per layer for the
+        generator and the backward pass, and the map table (sides and offsets inside a row) the mgf_noise_sets_* entries take."""
         G, dev, L, B = self.G, self.device, _lib.lib(), self.targets
         layers = [lp for lp in G.plan.layers if lp.noise_strength is not None]
         total = sum(lp.res * lp.res for lp in layers)
         z = lambda: torch.zeros(B, total, dtype=torch.float32, device=dev)
         self.noise_flat, self.noise_grad, self.noise_m, self.noise_v = self._reg(z()), z(), self._reg(z()), self._reg(z())
         self.best_noise_flat = self._reg(z(), 0)
-        if noise_init == "randn":                   # (target 0: the one-target engine's draw)
+        if noise_init == "randn":                   # (streams of their own, not the head of the latent's eps stream)
             for j in range(B):
                 self.noise_flat[j].copy_(seeded_randn((total,), dev, int(seed) + 0x6E6F6973 + j))
         self.noises, self.best_noises, self.dnoises, self.noise_layers = {}, {}, {}, []
@@ -292,16 +235,17 @@ class GradientProjectionEngine(ProjectionEngine):
         self.noise_sides, self.noise_offsets, self.noise_maps = _lib.map_table([r for _, r in self.noise_layers], offsets)
         self.noise_adam_t = self._reg(torch.zeros(B, dtype=torch.int32, device=dev))
         self.noise_ctr = torch.zeros(B, dtype=torch.int32, device=dev)      # the step counters as they stood before select_best advanced them
-        # target j's improvement flag (see _init_noise); `noise_slot` stays target 0's
+        # target j's improvement flag of select_best: take[0] = 0 where this step improved, else -1 (_noise_update reads it after the launch
+        # that wrote it); `noise_slot` is target 0's
         self.noise_slots = [ImprovementSlot(1, 1, dev) for _ in range(B)]
         self.noise_slot = self.noise_slots[0]
         for slot in self.noise_slots:
             self._table += slot.state(with_take=True)
         nbytes = int(L.mgf_noise_sets_scratch_bytes(self.noise_sides, self.noise_maps, B))
         if nbytes <= 0:
-            raise _lib.MgfError(f"GradientProjectionEngine: noise_per_target: the set kernels do not take this generator's maps (sides "
+            raise _lib.MgfError(f"GradientProjectionEngine: optimize_noise: the set kernels do not take this generator's maps (sides "
                                 f"{[r for _, r in self.noise_layers]}: at most 32 maps, powers of two)")
-        self.noise_sets_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        self.noise_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
         self.gg.noise_grads = True
 
     def _valid_rows(self):
@@ -310,24 +254,27 @@ class GradientProjectionEngine(ProjectionEngine):
             return 0, 0
         return self.valid.data_ptr(), (int(self.valid.shape[-1]) if self.targets > 1 else 0)
 
-    def _noise_sets_pack(self):
+    def _noise_pack(self):
         """The generator's dense per-layer maps from the targets' sets (B > 1; in front of the forward pass, so that maps written from outside
-        between steps count, like the one-target engine's)."""
+        between steps count, as they do with one target, whose maps the generator reads in place)."""
         if self.noise_dense is not None:
             _lib.check(_lib.lib().mgf_noise_sets_pack_f32(self.noise_dense.data_ptr(), self.noise_flat.data_ptr(), self.noise_offsets, self.noise_sides,
                                                           self.noise_maps, self.targets, self.noise_total, _lib.stream_ptr()), "noise_sets_pack")
 
-    def _noise_sets_regularize(self, has_p):
-        """_noise_regularize for every target in one call: p_loss[j] (+)= the weighted regulariser of target j's maps, added map after map in
-        float32 like the loop above forms it, and noise_grad += its gradient."""
+    def _noise_regularize(self, has_p):
+        """One call for every target: p_loss[j] (+)= noise_regularize * sum_maps reg of target j's maps, added map after map in float32, and
+        noise_grad += noise_regularize * d reg / d maps (the regulariser rides in the float32 p_loss slot like the biometric and MDF terms;
+        select_best forms the total in float64)."""
         _lib.check(_lib.lib().mgf_noise_sets_regularize_grad_f32(
             self.noise_grad.data_ptr(), self.p_loss.data_ptr(), 1, self.noise_flat.data_ptr(), self.noise_offsets, self.noise_sides, self.noise_maps,
-            self.targets, self.noise_total, float(self.args.noise_regularize), 1, int(has_p), self.noise_sets_scratch.data_ptr(), _lib.stream_ptr()),
+            self.targets, self.noise_total, float(self.args.noise_regularize), 1, int(has_p), self.noise_scratch.data_ptr(), _lib.stream_ptr()),
             "noise_sets_regularize_grad")
 
-    def _noise_sets_update(self):
-        """_noise_update for every target: keep the maps of each improving target, one Adam call, one normalise call; a target's skipped step
-        moves none of its maps (its own counter and `valid` row gate its slices)."""
+    def _noise_update(self):
+        """After select_best: keep the maps of each improving target (they still are the ones its image was generated with), then move them --
+        one Adam call on d total / d maps = the generator's d<img, dimg>/d maps (already in noise_grad) + noise_regularize * d reg / d maps,
+        one noise_normalize_ call over every map; a target's skipped step moves none of its maps (its own counter and `valid` row gate its
+        slices inside the kernels)."""
         L, st, B = _lib.lib(), _lib.stream_ptr(), self.targets
         for j in range(B):
             _lib.check(L.mgf_keep_improvements(self.best_noise_flat[j].data_ptr(), self.noise_flat[j].data_ptr(), self.noise_total,
@@ -339,7 +286,7 @@ class GradientProjectionEngine(ProjectionEngine):
                                        self.weight_decay, st), "adam_sets")
         _lib.check(L.mgf_noise_sets_normalize_f32(self.noise_flat.data_ptr(), self.noise_offsets, self.noise_sides, self.noise_maps, B,
                                                   self.noise_total, self.noise_ctr.data_ptr(), 1, vptr, vstride, self.steps,
-                                                  self.noise_sets_scratch.data_ptr(), st), "noise_sets_normalize")
+                                                  self.noise_scratch.data_ptr(), st), "noise_sets_normalize")
 
     # The three points at which a subclass couples the rows (demorph.DemorphEngine: rows that are linear mixes of parameters).  Here a row IS
     # a parameter: the hooks add no launch and reorder none.
@@ -366,17 +313,15 @@ class GradientProjectionEngine(ProjectionEngine):
                                            self.adam_eps, self.weight_decay, st), "adam_step")
             if self.use_wing:
                 _wing_into(self.wing_kind, self.w_loss[j:], self.lm_tables[j], self.lm_target[j] if B > 1 else self.lm_target, 1, ctr)
-            slot = self.noise_slots[j] if self.noise_slots is not None else self.noise_slot
-            self._select_best(self.latent_n[j:], 1, slot, row=j, valid=valid, has_p=has_p)
+            self._select_best(self.latent_n[j:], 1, self.noise_slots[j] if self.noise_slots else None, row=j, valid=valid, has_p=has_p)
 
     def _iteration(self):
         a, B = self.args, self.targets
         rows = self._make_rows()
         opt_noise = self.optimize_noise
-        sets = self.noise_per_target
-        if sets:
-            self._noise_sets_pack()
-        nkw = dict(noise_mode="inject", noises=self.gen_noises if sets else self.noises) if opt_noise else dict(noise_mode=self.noise_mode)
+        if opt_noise:
+            self._noise_pack()
+        nkw = dict(noise_mode="inject", noises=self.gen_noises) if opt_noise else dict(noise_mode=self.noise_mode)
         if self.latent_space == "w+":
             img = self.gg.forward(ws=rows, **nkw)                                 # [B, k, num_ws, D]: every layer reads its own slot
         else:
@@ -407,11 +352,11 @@ class GradientProjectionEngine(ProjectionEngine):
         dz = self._apply_row_gradients(dz)
         has_p = self.has_p or opt_noise
         if opt_noise:
-            (self._noise_sets_regularize if sets else self._noise_regularize)(self.has_p)
+            self._noise_regularize(self.has_p)
             self.noise_ctr.copy_(self.step_ctr)
         self._bookkeeping(dz, has_p)
         if opt_noise:
-            (self._noise_sets_update if sets else self._noise_update)()
+            self._noise_update()
         return img
 
     def result(self):

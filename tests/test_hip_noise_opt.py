@@ -297,7 +297,9 @@ def test_dnoises_none_is_the_call_without_the_keyword(tiny, monkeypatch):
 
 
 NEW_CALLS = ["mgf_noise_grad_f32", "mgf_noise_regularize_f32", "mgf_noise_regularize_grad_f32", "mgf_noise_normalize_f32",
-             "mgf_adam_elementwise_f32", "mgf_noise_regularize_scratch_bytes", "mgf_noise_normalize_scratch_bytes"]
+             "mgf_adam_elementwise_f32", "mgf_noise_regularize_scratch_bytes", "mgf_noise_normalize_scratch_bytes",
+             "mgf_noise_sets_scratch_bytes", "mgf_noise_sets_regularize_grad_f32", "mgf_noise_sets_normalize_f32", "mgf_noise_sets_grad_f32",
+             "mgf_noise_sets_pack_f32", "mgf_adam_sets_f32"]
 
 
 class _Counting:
@@ -521,12 +523,15 @@ def test_default_engine_makes_none_of_the_new_calls(tiny, monkeypatch):
         eng.run().result()
         assert eng.noises is None and eng.best_noises is None and not eng.gg.noise_grads
     assert counts == {n: 0 for n in NEW_CALLS}
-    # ... and the counter does count: the same run with the switch on
+    # ... and the counter does count: the same run with the switch on, one eager step (one target is a set of one: one set call each)
     GradientProjectionEngine(G, case["target"].cuda(), case["latent_mean"].cuda(), 1.0, ProjectionArgs(step=3, lr=LR, noise_regularize=1.0),
                              eps=case["eps"][:3].cuda(), use_graph=False, optimize_noise=True).run(1)
     nmaps = len(_noise_layers(G))
-    assert counts["mgf_noise_grad_f32"] == nmaps and counts["mgf_noise_regularize_grad_f32"] == nmaps
-    assert counts["mgf_noise_normalize_f32"] == nmaps and counts["mgf_adam_elementwise_f32"] == 1
+    assert counts["mgf_noise_grad_f32"] == nmaps
+    assert counts["mgf_noise_sets_regularize_grad_f32"] == counts["mgf_noise_sets_normalize_f32"] == counts["mgf_adam_sets_f32"] == 1
+    assert counts["mgf_noise_sets_pack_f32"] == counts["mgf_noise_sets_grad_f32"] == 0
+    assert counts["mgf_noise_regularize_f32"] == counts["mgf_noise_regularize_grad_f32"] == 0
+    assert counts["mgf_noise_normalize_f32"] == counts["mgf_adam_elementwise_f32"] == 0
 
 
 def test_cli_project_with_optimised_noise_writes_the_maps(tmp_path):

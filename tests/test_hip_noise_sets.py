@@ -1,6 +1,7 @@
 """Per-target noise maps for lockstep targets: the set entries of csrc/noise_opt.hip (mgf_noise_sets_*, mgf_adam_sets_f32) on their own,
-then GradientProjectionEngine(optimize_noise=True, noise_per_target=True) with one target (against the one-target engine, bit for bit) and
-with two different targets (each against its own autograd + Adam run on the CPU), then the drivers.
+then GradientProjectionEngine(optimize_noise=True) with one target (a set of one, against the per-map loops of
+tests/noise_per_map_engine.py, bit for bit) and with two different targets and noise_per_target=True (each against its own autograd + Adam
+run on the CPU), then the drivers.
 
 A set kernel and its per-map counterpart share their body, their partial counts and their fold order, so per (set, map) the bits are the
 per-map entry's: asserted with torch.equal against n_sets x n_maps per-map calls.  The float64 gates are those of
@@ -13,6 +14,7 @@ import torch
 
 import test_hip_noise_opt as base
 from guarded_buffers import NAN, Guarded
+from noise_per_map_engine import PerMapNoiseEngine
 from noise_opt_torch_ref import projection_noise_ref
 from noise_sets_torch_ref import BIG_SIDES, SIDES, gapped_table, make_sets, map_of, normalize_sets, regularize_sets
 from test_hip_noise_opt import ADAM_EPS, LR, REG_WEIGHT, SKIPPED, STEPS, dist, gate, make_map
@@ -288,15 +290,15 @@ def tiny():
     return Generator(sd, TINY, "cuda", max_batch=2), to_torch_state(sd), TINY
 
 
-def _engine(case, objective, noise_init, use_graph, G, **extra):
-    """base._engine with further keywords (the one-target engines of the comparison)."""
+def _engine(case, objective, noise_init, use_graph, G, cls=None, **extra):
+    """base._engine with further keywords and the engine's class (the one-target engines of the comparison)."""
     from morphganformer_amd.lpips import PerceptualLoss
     from morphganformer_amd.projection import GradientProjectionEngine
     kw = dict(lm_valid=case["valid"], eps=case["eps"].cuda(), noise_mode="const", use_graph=use_graph, optimize_noise=True, noise_init=noise_init,
               adam_eps=ADAM_EPS, **extra)
     if objective == "lpips":
         kw.update(percept=PerceptualLoss(net="squeeze", allow_random_backbone=True), lm_target=case["lm_t"], lm_steps=case["lm_s"])
-    eng = GradientProjectionEngine(G, case["target"].cuda(), case["latent_mean"].cuda(), 1.0, case["args"], **kw)
+    eng = (cls or GradientProjectionEngine)(G, case["target"].cuda(), case["latent_mean"].cuda(), 1.0, case["args"], **kw)
     if noise_init == "randn":
         for k, v in case["start"].items():
             eng.noises[k].copy_(v)
@@ -305,8 +307,9 @@ def _engine(case, objective, noise_init, use_graph, G, **extra):
 
 @pytest.mark.parametrize("objective,noise_init", [("mse", "randn"), ("lpips", "const")])
 def test_one_target_on_the_set_path_is_the_one_target_engine(tiny, objective, noise_init):
-    """One target with noise_per_target=True (hipGraph replay, and eager) against the optimize_noise=True engine: latent and map
-    trajectories, losses, best step, best latent and best_noises bit for bit; and the engines' own seeded draws coincide."""
+    """One target is a set of one: the engine (set kernels; hipGraph replay, and eager) against PerMapNoiseEngine, the same engine with the
+    regulariser, Adam and the normalisation restated as loops over the per-map entries: latent and map trajectories, images, losses, best
+    step, best latent and best_noises bit for bit; and the engine's own seeded draws with noise_per_target on and off coincide."""
     from morphganformer_amd.projection import GradientProjectionEngine
     G, tsd, cfg = tiny
     case = base._loop_case(objective, noise_init)
@@ -315,7 +318,7 @@ def test_one_target_on_the_set_path_is_the_one_target_engine(tiny, objective, no
         a = GradientProjectionEngine(G, case["target"].cuda(), case["latent_mean"].cuda(), 1.0, case["args"], **kw)
         b = GradientProjectionEngine(G, case["target"].cuda(), case["latent_mean"].cuda(), 1.0, case["args"], noise_per_target=True, **kw)
         assert all(torch.equal(a.noises[k], b.noises[k]) and tuple(b.noises[k].shape) == tuple(a.noises[k].shape) for k in a.noises)
-    ref_eng = base._engine(case, objective, noise_init, True, G)
+    ref_eng = _engine(case, objective, noise_init, True, G, cls=PerMapNoiseEngine)
     want = base._run(ref_eng) + (ref_eng.result(), {k: v.clone() for k, v in ref_eng.best_noises.items()})
     for use_graph in (True, False) if objective == "mse" else (True,):
         eng = _engine(case, objective, noise_init, use_graph, G, noise_per_target=True)
@@ -477,7 +480,8 @@ def test_wplus_two_targets_moves_and_normalises_every_map(tiny):
 
 def test_calls_per_step(tiny, monkeypatch):
     """The new path: one regulariser, one normalise, one Adam and one pack call per step whatever the number of targets and maps, one
-    channel-sum call per noise layer, none of the per-map calls.  With the keyword off: none of the set calls."""
+    channel-sum call per noise layer, none of the per-map calls.  Without optimize_noise: none of either family.  One target: the same
+    set calls without the pack, the per-map channel sum, and none of the per-map regulariser, normalise or Adam calls."""
     from morphganformer_amd.projection import GradientProjectionEngine, ProjectionArgs
     G, tsd, cfg = tiny
     counts = base._count_calls(monkeypatch, PER_MAP_CALLS + SET_CALLS)
@@ -493,10 +497,22 @@ def test_calls_per_step(tiny, monkeypatch):
     tg2 = torch.cat([c["target"] for c in cases]).cuda()
     for use_graph in (False, True):
         GradientProjectionEngine(G, tg2, one["latent_mean"].cuda(), 1.0, ProjectionArgs(step=2, lr=LR), noise_mode="const", use_graph=use_graph).run()
-        GradientProjectionEngine(G, one["target"].cuda(), one["latent_mean"].cuda(), 1.0, ProjectionArgs(step=2, lr=LR, noise_regularize=1.0),
-                                 use_graph=use_graph, optimize_noise=True).run()
-    assert all(counts[n] == 0 for n in SET_CALLS), counts
-    assert counts["mgf_noise_regularize_grad_f32"] > 0
+    assert counts == {n: 0 for n in counts}, counts
+    # one target is a set of one: the set calls (no pack, the per-map channel sum: one map per layer), none of the per-map loops
+    loops = ["mgf_noise_regularize_f32", "mgf_noise_regularize_grad_f32", "mgf_noise_normalize_f32", "mgf_adam_elementwise_f32"]
+    mk = lambda use_graph: GradientProjectionEngine(G, one["target"].cuda(), one["latent_mean"].cuda(), 1.0,
+                                                    ProjectionArgs(step=2, lr=LR, noise_regularize=1.0), use_graph=use_graph, optimize_noise=True)
+    eng = mk(False)
+    for step in (1, 2):
+        eng.run(1)
+        assert counts == {**{n: 0 for n in loops}, "mgf_noise_grad_f32": step * nmaps, "mgf_noise_sets_regularize_grad_f32": step,
+                          "mgf_noise_sets_normalize_f32": step, "mgf_adam_sets_f32": step, "mgf_noise_sets_pack_f32": 0,
+                          "mgf_noise_sets_grad_f32": 0}, counts
+    for n in counts:
+        counts[n] = 0
+    mk(True).run()
+    assert all(counts[n] == 0 for n in loops), counts
+    assert all(counts[n] >= 1 for n in ("mgf_noise_sets_regularize_grad_f32", "mgf_noise_sets_normalize_f32", "mgf_adam_sets_f32")), counts
 
 
 def test_engine_refusals(tiny):

@@ -2,8 +2,8 @@
     python tools/noise_opt_bench.py [--steps 60] [--reps 3] [--out profiles/noise_opt_bench.jsonl]
     python tools/noise_opt_bench.py --lockstep 8 [--out profiles/noise_sets_bench.jsonl]      (+ the lockstep leg, see the end)
 alternates optimize_noise off and on, `reps` times each on one device (one JSON line per run), then times the added launches by group
-between two events -- the channel sums of all noise layers (mgf_noise_grad_f32), the regulariser over all maps, Adam + normalisation -- and
-ends with a summary line.  The on-engine also runs its backward pass without the fused style / activation / blur-gradient pass (the noise
+between two events -- the channel sums of all noise layers (mgf_noise_grad_f32), the regulariser over all maps (one set call), keep + Adam +
+normalisation (one set call each) -- and ends with a summary line.  The on-engine also runs its backward pass without the fused style / activation / blur-gradient pass (the noise
 layers' pre-activation gradient has to reach memory): that difference is part of the step-time figure, not of the three groups.
 
 --lockstep B adds, alternated on the same device, `reps` times each: (i) B lockstep targets without noise optimisation, (ii) B lockstep
@@ -132,8 +132,8 @@ def lockstep_leg(B):
             _lib.check(L.mgf_noise_sets_grad_f32(e.dnoises[lp.name].data_ptr(), e.noise_total, dpre_b.data_ptr(), lp.noise_strength.data_ptr(), B, lp.cout,
                                                  lp.res * lp.res, 0, _lib.stream_ptr()), "noise_sets_grad")
 
-    us = {"noise_sets_grad_all_layers_us": timed_us(channel_sums_sets), "pack_us": timed_us(e._noise_sets_pack),
-          "regulariser_sets_us": timed_us(lambda: e._noise_sets_regularize(True)), "keep_adam_and_normalise_sets_us": timed_us(e._noise_sets_update)}
+    us = {"noise_sets_grad_all_layers_us": timed_us(channel_sums_sets), "pack_us": timed_us(e._noise_pack),
+          "regulariser_sets_us": timed_us(lambda: e._noise_regularize(True)), "keep_adam_and_normalise_sets_us": timed_us(e._noise_update)}
     for dst, src in zip(list(e._state()) + [e.p_loss, e.noise_grad], keep):
         dst.copy_(src)
     m = {k: sum(v) / len(v) for k, v in per_target.items()}

@@ -119,13 +119,14 @@ def summarise(parent_a, parent_b, head):
     """One summary line per configuration: the call list of the head against the parent's, and every result field on which the parent's two
     runs agree against the head's."""
     runs = [{r["config"]: r for r in map(json.loads, open(p))} for p in (parent_a, parent_b, head)]
-    call_keys = ("n_mgf_calls", "n_torch_ops", "calls_sha256", "torch_ops_sha256")
+    # (graph_kernel_nodes, where a workload reports it, counts launches: it belongs to the call list, not to the results)
+    call_keys = ("n_mgf_calls", "n_torch_ops", "calls_sha256", "torch_ops_sha256", "graph_kernel_nodes")
     skip = call_keys + ("config", "run", "variant")
     for cfg, a in runs[0].items():
         b, h = runs[1][cfg], runs[2][cfg]
         la, lb, lh = (dict(x for x in _leaves(r) if x[0] not in skip) for r in (a, b, h))
         differs = sorted(k for k in la if la[k] != lb.get(k))
-        line = {"config": cfg, "summary": True, "calls_identical": all(a[k] == b[k] == h[k] for k in call_keys),
+        line = {"config": cfg, "summary": True, "calls_identical": all(a.get(k) == b.get(k) == h.get(k) for k in call_keys),
                 "parent_reproducible": not differs,
                 "results_bit_identical": set(lh) == set(la) and all(lh[k] == la[k] for k in la if k not in differs)}
         if differs:
