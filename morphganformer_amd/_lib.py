@@ -3,23 +3,86 @@
 There is NO CPU fallback: if the shared library is missing, `lib()` raises, and every op checks that its tensors
 live on a HIP device.  (The reference silently falls back to slow torch ops when its plugin build fails,
 torch_utils/ops/bias_act.py:39-43; a drop-in for the GPU hot path must not.)
+
+The header is the one statement of the ABI: the signature of every entry point and every MGF_* constant are read from it at import
+(`parse_header`), so the compiler checks the definitions in csrc/ and this module against the same text.  Only the struct classes
+below are written by hand (tests/test_host_and_abi.py compares their layouts with a C compiler's).
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGF_LIB_PATH") or os.path.join(HERE, "libmgf_hip.so")     # env override: kernel experiments only
-
-MGF_F32, MGF_F64, MGF_F16 = 0, 1, 2
-ACT_IDS = {"linear": 1, "relu": 2, "lrelu": 3, "tanh": 4, "sigmoid": 5, "elu": 6, "selu": 7, "softplus": 8, "swish": 9,
-           "relu_post": 10}      # mgf_conv1x1_f32 only: ReLU AFTER the residual add
-MAX_TAPS = 9
+HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "mgf.h")                # (csrc/mgf_common.h includes it by the same relative path)
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
+
+
+class MgfError(RuntimeError):
+    pass
+
+
+# One rule per C type of the header.  Every pointer parameter is c_void_p -- struct pointers too: `const mgf_style_job*` is a host
+# struct (byref) in one entry and a device address (int) in another, and c_void_p takes None, int, byref(...) and ctypes arrays alike.
+# A type outside the rules is refused, never bound as int by default.
+_SCALARS = {"int": C.c_int, "int32_t": i32, "int64_t": i64, "uint64_t": C.c_uint64, "float": f32, "double": f64, "mgf_stream_t": vp}
+_PROTOTYPE = re.compile(r"([A-Za-z_][\w\s*]*?)\b(mgf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+
+
+def _ctype(decl, proto, result=False):
+    words = decl.replace("*", " * ").split()
+    plain = [w for w in words if w != "const"]
+    if result and plain == ["void"]:
+        return None
+    if "*" in plain:
+        if not result:
+            return vp
+        if words == ["const", "char", "*"]:
+            return C.c_char_p
+    elif plain and plain[0] in _SCALARS and (len(plain) == 1 or (len(plain) == 2 and not result and plain[1].isidentifier())):
+        return _SCALARS[plain[0]]
+    raise MgfError(f"include/mgf.h: no binding rule for {' '.join(words)!r} in `{proto}`")
+
+
+def parse_header(text):
+    """(signatures, constants) of a C header in the dialect of include/mgf.h: `name -> (restype, [argtypes])` for every `mgf_*`
+    prototype, and `NAME -> int` for every enumerator of an `enum { NAME = value, ... };` block and every `#define MGF_NAME <integer>`.
+    Raises MgfError for what it does not understand (a type outside _SCALARS, an `mgf_*(` that is no plain prototype: a function-pointer
+    parameter, a declaration inside a macro), so that no export drops out of the binding silently."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {name: int(value) for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(MGF_\w+)[ \t]+(-?\d+)[ \t]*$", text, re.M)}
+    for body in re.findall(r"\benum\s*\{([^{}]*)\}\s*;", text):
+        for item in filter(None, map(str.strip, body.split(","))):
+            m = re.fullmatch(r"(\w+)\s*=\s*(-?\d+)", item)
+            if not m:
+                raise MgfError(f"include/mgf.h: enumerator `{item}` has no explicit decimal value")
+            consts[m.group(1)] = int(m.group(2))
+    sigs = {}
+    for m in _PROTOTYPE.finditer(re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)):
+        ret, name, params = m.groups()
+        proto = " ".join(m.group(0).split())
+        params = [] if params.split() in ([], ["void"]) else params.split(",")
+        sigs[name] = (_ctype(ret, proto, result=True), [_ctype(p, proto) for p in params])
+    unparsed = sorted(set(re.findall(r"\b(mgf_[a-z0-9_]+)\s*\(", text)) - set(sigs))
+    if unparsed:
+        raise MgfError(f"include/mgf.h: {', '.join(unparsed)}: not a plain prototype `type mgf_name(type arg, ...);`, cannot be bound")
+    return sigs, consts
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        _SIGS, CONSTANTS = parse_header(_f.read())
+except OSError as e:
+    raise MgfError(f"{HEADER_PATH}: the C header the binding is read from is missing ({e}); the package is used in place, in its tree") from None
+globals().update(CONSTANTS)           # MGF_OK / MGF_E*, MGF_F32 / MGF_F64 / MGF_F16, MGF_ACT_*, MGF_FILTER_*, MGF_CROP_*, MGF_MAX_TAPS
+EXPORTED_SYMBOLS = sorted(_SIGS)
+MAX_TAPS = CONSTANTS["MGF_MAX_TAPS"]
+ACT_IDS = {name[len("MGF_ACT_"):].lower(): value for name, value in CONSTANTS.items() if name.startswith("MGF_ACT_")}
 
 
 class Epilogue(C.Structure):
@@ -63,174 +126,7 @@ class AttnBwdJob(C.Structure):
     _fields_ = [("wmv", vp), ("dvwb", vp), ("c", i32), ("pad_", i32)]
 
 
-_SIGS = {
-    "mgf_last_error": (C.c_char_p, []),
-    "mgf_version": (C.c_int, []),
-    "mgf_device_ok": (C.c_int, []),
-    "mgf_bias_act": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, i64, i64, i64, C.c_int, C.c_int, f32, f32, f32, vp]),
-    "mgf_upfirdn2d": (C.c_int, [vp, vp, vp, C.c_int, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i64, i64, i64, i64,
-                                i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, C.POINTER(Epilogue), vp]),
-    "mgf_conv_taps_f32": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(ConvDesc), C.POINTER(Epilogue), vp]),
-    "mgf_conv_taps_bf16x3_f32": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(ConvDesc), C.POINTER(Epilogue), vp]),
-    "mgf_tconv3x3s2_border_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp]),
-    "mgf_tconv3x3s2_blur_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_float, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, C.POINTER(Epilogue), vp]),
-    "mgf_tconv3x3s2_winograd_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i64, vp]),
-    "mgf_tconv_winograd_weights_f32": (C.c_int, [vp, vp, i32, i32, C.c_double, vp]),
-    "mgf_winograd_weights_f32": (C.c_int, [vp, vp, i32, i32, f32, vp]),
-    "mgf_conv3x3_winograd_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(Epilogue), vp]),
-    "mgf_winograd2_weights_f32": (C.c_int, [vp, vp, i32, i32, f32, vp]),
-    "mgf_conv3x3_winograd2_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(Epilogue), vp]),
-    "mgf_conv3x3_winograd2_rgb_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
-    "mgf_conv3x3_winograd3_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(Epilogue), vp]),
-    "mgf_conv1x1_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i32, C.POINTER(Epilogue), vp]),
-    "mgf_conv3x3s2_few_inputs_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
-    "mgf_tconv3x3s2_few_outputs_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, vp]),
-    "mgf_conv1x1_force_shape": (C.c_int, [i32]),
-    "mgf_conv3x3_winograd3_slice_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i32, C.POINTER(Epilogue), vp]),
-    "mgf_conv3x3_winograd3_up2res_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(Epilogue), vp]),
-    "mgf_winograd3_force_shape": (C.c_int, [i32]),
-    "mgf_conv3x3_winograd3_rgb_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
-    "mgf_conv3x3_winograd2_slice_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i32, C.POINTER(Epilogue), vp]),
-    "mgf_pack_conv_weights": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
-    "mgf_conv_profile_begin": (C.c_int, []),
-    "mgf_conv_profile_end": (C.c_int, [C.POINTER(ConvProfRec), i32]),
-    "mgf_demod_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
-    "mgf_demod_bwd_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
-    "mgf_style_demod": (C.c_int, [C.POINTER(StyleJob), vp, i64, i32, i32, vp]),
-    "mgf_style_demod_multi": (C.c_int, [vp, i32, vp, i64, i32, i32, i32, vp]),
-    "mgf_duplex_attention": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(Epilogue), i32, vp, vp, vp]),
-    "mgf_att_map_upsample_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
-    "mgf_attn_values": (C.c_int, [C.POINTER(AttnJob), vp, i64, i64, i32, i32, i32, vp]),
-    "mgf_attn_values_multi": (C.c_int, [vp, i32, vp, i64, i64, i32, i32, i32, vp]),
-    "mgf_randn_f32": (C.c_int, [vp, i64, C.c_uint64, vp, vp]),
-    "mgf_rgb_weights_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
-    "mgf_torgb_compose_weights_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
-    "mgf_conv3x3_few_outputs_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_mapping_param_floats": (i64, [i32, i32, i32]),
-    "mgf_mapping_forward": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_reduce_scratch_floats": (i64, []),
-    "mgf_mse_f32": (C.c_int, [vp, vp, vp, i32, i64, i64, f32, i32, vp, vp]),
-    "mgf_dssim_scratch_bytes": (i64, [i32, i32, i32, i32]),
-    "mgf_dssim_u8_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i64, f32, f32, i32, vp, vp]),
-    "mgf_dssim_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i64, f32, f32, i32, vp, vp]),
-    "mgf_dssim_grad_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i64, f32, f32, i32, i32, vp, vp]),
-    "mgf_msssim_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
-    "mgf_msssim_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i64, vp, i32, f32, f32, i32, vp, vp]),
-    "mgf_msssim_grad_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, i32, f32, f32, i32, i32, vp, vp]),
-    "mgf_lbp_scratch_bytes": (i64, [i32]),
-    "mgf_lbp_gray224_u8": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
-    "mgf_lbp_codes_u8": (C.c_int, [vp, vp, vp, i32, vp]),
-    "mgf_lbp_distance_f64": (C.c_int, [vp, vp, vp, vp, i32, vp, vp]),
-    "mgf_wing_loss_f64": (C.c_int, [vp, vp, vp, i32, i64, f64, f64, vp, i32, vp]),
-    "mgf_adaptive_wing_loss_f64": (C.c_int, [vp, vp, vp, i32, i64, f64, f64, f64, f64, vp, i32, vp]),
-    "mgf_embed_pair_loss_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, f32, f32, i32, i32, vp, i32, vp]),
-    "mgf_lpips_unit_f32": (C.c_int, [vp, vp, i32, i32, i64, vp]),
-    "mgf_lpips_layer_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, i64, i32, vp, vp]),
-    "mgf_lpips_stem_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
-    "mgf_lpips_layer_map_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, i64, vp]),
-    "mgf_lpips_upsample_sum_f32": (C.c_int, [vp, C.POINTER(vp), C.POINTER(i32), i32, i32, i32, i32, vp]),
-    "mgf_channel_affine_prelu_f32":(C.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, vp]),
-    "mgf_linear_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp]),
-    "mgf_resize_bilinear_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_spatial_mean_f32": (C.c_int, [vp, vp, i32, i64, vp]),
-    "mgf_l2_normalize_f32": (C.c_int, [vp, vp, i32, i32, f32, vp]),
-    "mgf_l2_normalize_bwd_f32": (C.c_int, [vp, vp, vp, i32, i32, f32, vp]),
-    "mgf_spatial_mean_bwd_f32": (C.c_int, [vp, vp, i32, i64, vp]),
-    "mgf_relu_bwd_slice_f32": (C.c_int, [vp, vp, i32, i32, vp, i32, i32, i32, i32, i64, vp]),
-    "mgf_maxpool_s2_floor_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
-    "mgf_maxpool3x3s2_ceil_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_latent_perturb": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, vp]),
-    "mgf_latent_perturb_mean": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, i32, vp]),
-    "mgf_select_best": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, vp, vp, f64, f32, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp]),
-    "mgf_keep_improvements": (C.c_int, [vp, vp, i64, vp, i32, vp]),
-    "mgf_to_uint8_hwc": (C.c_int, [vp, vp, i32, i32, i32, vp]),
-    "mgf_reference_gray_scratch_floats": (i64, []),
-    "mgf_reference_gray_u8": (C.c_int, [vp, vp, i32, i32, i32, vp, vp]),
-    "mgf_bwd_chunks": (i32, [i64]),
-    "mgf_layer_act_bwd_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, f32, f32, vp]),
-    "mgf_channel_dot_f32": (C.c_int, [vp, vp, vp, i32, i32, i64, vp]),
-    "mgf_style_grad_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, i32, vp]),
-    "mgf_style_grad_act_bwd_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i64, f32, f32, vp]),
-    "mgf_style_act_fir_tiles": (i32, [i32, i32]),
-    "mgf_style_act_fir_bwd_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, i32, i32, i32, i32, f32, f32, vp]),
-    "mgf_layer_act_bwd_low_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i64, f32, f32, vp]),
-    "mgf_duplex_attention_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
-    "mgf_attn_values_grad": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
-    "mgf_attn_values_grad_workspace_floats": (C.c_int64, [i32, i32]),
-    "mgf_attn_values_grad_ws": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, i64, vp]),
-    "mgf_style_demod_bwd_multi": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
-    "mgf_attn_values_bwd_multi": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
-    "mgf_attn_values_grad_slices": (i32, [i32, i32, i32, i32]),
-    "mgf_attn_grad_job_bytes": (i64, []),
-    "mgf_attn_grad_multi": (C.c_int, [vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_latent_bwd_multi": (C.c_int, [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_latent_grad_gather": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, f32, vp]),
-    "mgf_lpips_layer_bwd_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, i64, f32, i32, vp]),
-    "mgf_lpips_layer_bwd_relu_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i64, f32, vp]),
-    "mgf_lpips_layer_stats_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, i64, i32, vp, vp]),
-    "mgf_lpips_layer_defer_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, i64, C.POINTER(i32), vp]),
-    "mgf_lpips_finish_taps_f32": (C.c_int, [vp, vp, i64, i32, C.POINTER(i32), C.POINTER(f32), i32, i32, vp]),
-    "mgf_lpips_layer_bwd_relu_stats_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i64, f32, vp]),
-    "mgf_relu_bwd_split_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, vp]),
-    "mgf_maxpool3x3s2_ceil_idx_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_maxpool3x3s2_ceil_bwd_idx_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_maxpool3x3s2_ceil_bwd_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_maxpool_s2_floor_bwd_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
-    "mgf_mse_grad_f32": (C.c_int, [vp, vp, vp, i32, i64, i64, f32, i32, vp]),
-    "mgf_lpips_layer_defer_weighted_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i64, i64, i64, C.POINTER(i32), vp]),
-    "mgf_lpips_layer_bwd_weighted_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, i64, i64, f32, i32, vp]),
-    "mgf_lpips_layer_bwd_relu_stats_weighted_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, f32, vp]),
-    "mgf_mse_weighted_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, i64, i64, f32, i32, vp, vp]),
-    "mgf_mse_weighted_grad_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, i64, i64, f32, i32, vp]),
-    "mgf_prelu_bwd_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, vp]),
-    "mgf_linear_bwd_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
-    "mgf_resize_bilinear_bwd_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_face_crop_check": (C.c_int, [vp, i32, i32]),
-    "mgf_face_crop_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
-    "mgf_face_crop_bwd_f32": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
-    "mgf_dwconv_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
-    "mgf_dwconv_bwd_data_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
-    "mgf_cv_warp_triangle_bytes": (i64, []),
-    "mgf_cv_warp_triangles_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
-    "mgf_adam_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, vp]),
-    "mgf_adam_elementwise_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, vp]),
-    "mgf_latent_mix_f32": (C.c_int, [vp, vp, vp, i32, i32, i64, vp]),
-    "mgf_latent_mix_bwd_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, vp]),
-    "mgf_joint_losses_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, f64, f32, vp, vp, i32, i32, vp]),
-    "mgf_es_recombine_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i64, f64, vp, vp]),
-    "mgf_noise_grad_f32": (C.c_int, [vp, vp, vp, i32, i64, i32, vp]),
-    "mgf_noise_regularize_scratch_bytes": (i64, [i32]),
-    "mgf_noise_regularize_f32": (C.c_int, [vp, vp, i32, f32, i32, vp, vp]),
-    "mgf_noise_regularize_grad_f32": (C.c_int, [vp, vp, vp, i32, f32, i32, i32, vp, vp]),
-    "mgf_noise_normalize_scratch_bytes": (i64, []),
-    "mgf_noise_normalize_f32": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
-    # (sides / offsets: HOST arrays, e.g. (i32 * n)(*sides) -- see map_table())
-    "mgf_noise_sets_scratch_bytes": (i64, [vp, i32, i32]),
-    "mgf_noise_sets_regularize_grad_f32": (C.c_int, [vp, vp, i64, vp, vp, vp, i32, i32, i64, f32, i32, i32, vp, vp]),
-    "mgf_noise_sets_normalize_f32": (C.c_int, [vp, vp, vp, i32, i32, i64, vp, i64, vp, i64, i32, vp, vp]),
-    "mgf_noise_sets_grad_f32": (C.c_int, [vp, i64, vp, vp, i32, i32, i64, i32, vp]),
-    "mgf_noise_sets_pack_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i64, vp]),
-    "mgf_adam_sets_f32":(C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i32, i64, i32, f32, f32, f32, f32, vp]),
-    "mgf_mapping_bwd_scratch_floats": (i64, [i32, i32, i32]),
-    "mgf_mapping_backward": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_mapping_forward_save": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_mapping_backward_saved": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_mdf_partials": (i64, [i32, i32]),
-    "mgf_mdf_head_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
-    "mgf_mdf_body_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
-    "mgf_mdf_tail_f32": (C.c_int, [vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mgf_mdf_finish_f32": (C.c_int, [vp, vp, i32, i64, C.POINTER(f64), i32, f32, i32, vp]),
-    "mgf_mdf_tail_backward_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp]),
-    "mgf_mdf_body_backward_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]),
-    "mgf_mdf_head_backward_f32": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, vp]),
-}
-
-EXPORTED_SYMBOLS = sorted(_SIGS)
 _lib = None
-
-
-class MgfError(RuntimeError):
-    pass
 
 
 def lib() -> C.CDLL:
@@ -268,6 +164,11 @@ def map_table(sides, offsets):
     n = len(sides)
     assert len(offsets) == n
     return (i32 * n)(*[int(s) for s in sides]), (i64 * n)(*[int(o) for o in offsets]), n
+
+
+def device_table(arr, device):
+    """A ctypes array of job records as a uint8 tensor on `device`: the `*_jobs_dev` argument of the batched entries."""
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
 
 
 def require_gpu(*tensors):

@@ -632,7 +632,7 @@ def tconv3x3s2_blur_forward(x, pc: PackedConv, f1d, gain, in_scale=None, out_sca
         rc = _lib.lib().mgf_tconv3x3s2_blur_f32(out.data_ptr(), x.data_ptr(), pc.wp.data_ptr(), _lib.ptr(in_scale), _lib.ptr(out_scale),
                                                 f1d.data_ptr(), float(gain), n, cin, h, w, pc.cout, pc.cout_pad, sy[2], sy[1], sy[0],
                                                 _scale_stride(out_scale), C.byref(epilogue) if epilogue is not None else None, _lib.stream_ptr())
-        if rc != -2:                                   # MGF_EUNSUPPORTED: the three launches below
+        if rc != _lib.MGF_EUNSUPPORTED:                # (unsupported: the three launches below)
             _lib.check(rc, "tconv3x3s2_blur")
             return out
     if f2d is None:
@@ -654,7 +654,7 @@ def upfirdn_into(y, x, f2d, up=1, pad=(0, 0, 0, 0), gain=1.0, flip=False, epilog
     sx, sy = x.stride(), y.stride()
     rc = _lib.lib().mgf_upfirdn2d(y.data_ptr(), x.data_ptr(), f2d.data_ptr(), _lib.MGF_F32, n, c, h, w, sx[0], sx[1], sx[2],
                                   sx[3], oh, ow, sy[0], sy[1], sy[2], sy[3], fh, fw, up, up, down, down, px0, px1, py0, py1,
-                                  int(flip) | (2 if separable else 0) | 4,      # 4 = MGF_FILTER_LARGE: the engine's own calls
+                                  int(flip) | (_lib.MGF_FILTER_SEPARABLE if separable else 0) | _lib.MGF_FILTER_LARGE,    # (LARGE: the engine's own calls)
                                   float(gain), C.byref(epilogue) if epilogue is not None else None,
                                   _lib.stream_ptr())
     _lib.check(rc, "upfirdn2d")

@@ -73,7 +73,7 @@ class ArcFaceEmbedder(FaceEmbedder):
     the aligned, antialiased crop of mgf_face_crop_f32 and the scatter its adjoint."""
     _gp = _gn = None                 # transposed taps / batch size of the backward workspace (`_grad_ws` of the network, on first use)
     _crop = None                     # (float64 [m,2,3] device buffer, filter id) of set_crop; in `_MUTABLE`: a clone starts without one
-    CROP_FILTERS = {"area": 0, "bilinear": 1}
+    CROP_FILTERS = {"area": _lib.MGF_CROP_AREA, "bilinear": _lib.MGF_CROP_BILINEAR}
 
     def set_crop(self, matrices, filter="area"):
         """matrices [2,3], [1,2,3] (shared) or [n,2,3] (one per image): crop pixel index (u, v) -> source pixel index, (x, y) = M (u, v, 1)

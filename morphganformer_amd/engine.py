@@ -457,11 +457,8 @@ class Generator:
                 if lp.attn is not None:
                     aj.append(_lib.AttnJob(lp.attn.wmv.data_ptr(), lp.attn.bmv.data_ptr(),
                                            self.vtabs.data_ptr() + 4 * lp.attn.v_off * n, lp.attn.c, lp.slot * D if per_layer else 0))
-            sjt = torch.frombuffer(bytearray(bytes(sj)), dtype=torch.uint8).to(self.device)
-            ajt = None
-            if aj:
-                arr = (_lib.AttnJob * len(aj))(*aj)
-                ajt = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+            sjt = _lib.device_table(sj, self.device)
+            ajt = _lib.device_table((_lib.AttnJob * len(aj))(*aj), self.device) if aj else None
             return sjt, ajt, len(aj)
 
         self.style_jobs, self.attn_jobs, self.n_attn_jobs = tables(False)

@@ -106,13 +106,10 @@ class GeneratorGrad:
                 self.dvwb[lp.name] = e(n, lp.attn.c, T)
                 aj.append(_lib.AttnBwdJob(lp.attn.wmv.data_ptr(), self.dvwb[lp.name].data_ptr(), lp.attn.c, 0))
         self._build_deferred_attention(n)
-        arr = (_lib.StyleBwdJob * len(sj))(*sj)
-        self.style_jobs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(G.device)
+        self.style_jobs = _lib.device_table((_lib.StyleBwdJob * len(sj))(*sj), G.device)
         self.n_style_jobs = len(sj)
-        self.attn_jobs, self.n_attn_jobs = None, len(aj)
-        if aj:
-            arr = (_lib.AttnBwdJob * len(aj))(*aj)
-            self.attn_jobs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(G.device)
+        self.n_attn_jobs = len(aj)
+        self.attn_jobs = _lib.device_table((_lib.AttnBwdJob * len(aj))(*aj), G.device) if aj else None
         self.dwg = e(n, len(sj), D)
         self.dyc = e(n, max(len(aj), 1), T, D)
         self.dw = e(n, cfg.k, D)
@@ -172,8 +169,7 @@ class GeneratorGrad:
             for j in D["jobs"]:
                 j.cpre = D["cpre"][j.dg]
             D["cpre_ptrs"] = tuple(j.cpre for j in D["jobs"])
-            arr = (_lib.AttnGradJob * len(D["jobs"]))(*D["jobs"])
-            D["table"] = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.G.device)
+            D["table"] = _lib.device_table((_lib.AttnGradJob * len(D["jobs"]))(*D["jobs"]), self.G.device)
         g, d, r = D["blocks"]
         _lib.check(_lib.lib().mgf_attn_grad_multi(D["table"].data_ptr(), len(D["jobs"]), self.G.n, g, d, r, _lib.stream_ptr()), "attn_grad_multi")
 

@@ -47,5 +47,5 @@ def g_out(*shape, span=1):
 
 def device_table(jobs, kind):
     """A device array of job records (ctypes structures of type `kind`), uploaded the way engine.py and grad.py upload theirs."""
-    arr = (kind * len(jobs))(*jobs)
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).cuda()
+    from morphganformer_amd import _lib
+    return _lib.device_table((kind * len(jobs))(*jobs), "cuda")

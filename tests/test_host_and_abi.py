@@ -46,10 +46,20 @@ def test_abi_struct_layouts_match_header():
 
 
 def test_abi_struct_layouts_match_a_c_compiler(tmp_path):
-    """include/mgf.h is plain C: compile a probe with gcc and compare every struct's size and field offsets with ctypes."""
+    """include/mgf.h is plain C: compile a probe with gcc and compare every struct's size and field offsets with ctypes.  Every
+    `typedef struct mgf_*` the header defines is probed: mgf_conv_prof_rec -> _lib.ConvProfRec, and a struct without a class fails."""
     from morphganformer_amd import _lib
-    structs = {"mgf_epilogue": _lib.Epilogue, "mgf_conv_desc": _lib.ConvDesc, "mgf_conv_prof_rec": _lib.ConvProfRec,
-               "mgf_style_job": _lib.StyleJob, "mgf_attn_job": _lib.AttnJob}
+    hdr = open(os.path.join(ROOT, "include", "mgf.h")).read()
+    cnames = re.findall(r"\btypedef\s+struct\s+(mgf_\w+)\s*\{", hdr)
+    assert len(cnames) == len(set(cnames)) >= 7 and hdr.count("typedef struct") == len(cnames)
+    structs = {}
+    for cname in cnames:
+        cls = getattr(_lib, "".join(part.capitalize() for part in cname.split("_")[1:]), None)
+        assert isinstance(cls, type) and issubclass(cls, ctypes.Structure), f"{cname} of include/mgf.h has no ctypes class in _lib.py"
+        structs[cname] = cls
+    assert {"mgf_epilogue": _lib.Epilogue, "mgf_conv_desc": _lib.ConvDesc, "mgf_conv_prof_rec": _lib.ConvProfRec,
+            "mgf_style_job": _lib.StyleJob, "mgf_attn_job": _lib.AttnJob, "mgf_style_bwd_job": _lib.StyleBwdJob,
+            "mgf_attn_bwd_job": _lib.AttnBwdJob}.items() <= structs.items()
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mgf.h"', "int main(void) {"]
     for cname, cls in structs.items():
         lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
