@@ -1030,6 +1030,24 @@ int mgf_mdf_body_backward_f32(float* d, const float* g, const float* u_adj, cons
 int mgf_mdf_head_backward_f32(float* dimg, const float* d0, const float* x1, const float* x1_target, const float* w, int32_t n, int32_t c,
                               int32_t h, int32_t wd, float coef1, float slope, int32_t accumulate, mgf_stream_t stream);
 
+/* Block mean in front of the LPIPS backbone and its adjoint (lpips.PerceptualLoss(pool_above=N); projection_example_v1.py:148-155 average the
+ * generated image over height // 256 blocks before the perceptual network).  planes = n * channels; x and dx are contiguous [planes, h, w].
+ *   block_mean:         out[p, Y, X] = (1 / f^2) sum_{dy < f} sum_{dx < f} x[p, Y f + dy, X f + dx]            out [planes, h / f, w / f], contiguous
+ *   block_mean_adjoint: dx[p, y, x] (+)= dy[p, y / f, x / f] / f^2 where y / f < gh and x / f < gw,  (+)= 0 elsewhere
+ *           dy is [planes, gh, gw] with its own row pitch and plane stride (in elements) and may cover less than [h / f, w / f]: the
+ *           backbone's input gradient is a view that stops where the stride-2 stem stops reading.  accumulate = 0 writes every element of
+ *           dx (zeros where dy does not reach); accumulate = 1 adds, and leaves the uncovered elements untouched.
+ * Summation order of block_mean, float32, the same for every f, width, alignment, plane count and grid: a block's columns are cut into runs of
+ * four from the left (a last run of f % 4 columns when that is not 0; f = 2 is one run of two); within a row a run is summed left to right,
+ * ((a + b) + c) + d; each run is accumulated over the block's rows from the top; the runs' sums are added from the left; the total is divided
+ * by f^2 once.  So |out - exact| <= (f^2 + 1) 2^-24 mean_block |x|, and image i pools to the same bits alone or in a batch.
+ * MGF_EINVAL: f < 2, h % f or w % f non-zero, gh > h / f or gw > w / f (or < 1), a pitch or stride that cannot hold dy, planes h w > INT32_MAX.
+ * f = 2, 4, 8 with w % 4 == 0 and a 16-byte aligned x / dx move 16 bytes per lane; everything else takes the scalar bodies.  Launches on
+ * `stream`, no synchronisation, no allocation (capturable). */
+int mgf_block_mean_f32(float* out, const float* x, int32_t planes, int32_t h, int32_t w, int32_t f, mgf_stream_t stream);
+int mgf_block_mean_adjoint_f32(float* dx, const float* dy, int32_t planes, int32_t h, int32_t w, int32_t f, int32_t gh, int32_t gw,
+                               int64_t dy_row_pitch, int64_t dy_plane_stride, int32_t accumulate, mgf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,14 @@ def _lpips_arguments(p):
                    help="score with SEEDED RANDOM backbone features (smoke runs only: the LPIPS term is then not a perceptual distance)")
 
 
+def _lpips_pool_argument(p):
+    """--lpips-pool-above: the LPIPS term's own block mean.  The module entries (`python -m morphganformer_amd.demorph`, `... .evolution`) add it;
+    the subcommands of this parser keep the option tables tests/test_cli_parser_host.py pins, so they do not have it yet."""
+    p.add_argument("--lpips-pool-above", type=int, default=0, metavar="N",
+                   help="block-average images taller than N by height // N in front of the LPIPS backbone only (256: the v1 drivers' LPIPS size); "
+                        "the pixel, biometric and MDF terms keep the full-size image, and gradient mode gets the adjoint")
+
+
 def _loop_arguments(p, align_help=None):
     """The projection loop's arguments, shared by `project` and `morph-pairs` (1024_example_wing_loss_perceptual_sqz_MSE.py:222-245)."""
     p.add_argument("--model", type=str, default="models/ffhq-snapshot-1024_v2.pkl")
@@ -244,12 +252,15 @@ def _lpips_term(a, what, spatial=False, device="cuda"):
     if a.lpips_backbone is None and not a.lpips_random_backbone:
         raise SystemExit(f"{what}: the LPIPS term needs the torchvision backbone weights: --lpips-backbone <state dict> "
                          "(or --no-lpips / --lpips-random-backbone)")
+    pool_above = int(getattr(a, "lpips_pool_above", 0) or 0)
+    if spatial and pool_above:
+        raise SystemExit(f"{what}: --lpips-pool-above with an LPIPS map: the map is defined at the image's own size")
     from .lpips import PerceptualLoss, load_backbone_state
     state = load_backbone_state(a.lpips_backbone) if a.lpips_backbone else None
     if state is None:
         print("WARNING: LPIPS runs on seeded random backbone weights (--lpips-random-backbone); the term is not a perceptual distance")
     return PerceptualLoss(model="net-lin", net=a.net, spatial=spatial, use_gpu=True, device=device, backbone_state=state,
-                          allow_random_backbone=state is None)
+                          allow_random_backbone=state is None, pool_above=pool_above)
 
 
 def _embedder_state(a, missing, warning):

@@ -164,6 +164,7 @@ def build_parser():
     ap.add_argument("--pixel-term", choices=["mse", "dssim", "msssim"], default="mse", help="the pixel term, of the unquantised pixels")
     ap.add_argument("--ratio", type=float, default=1.0, help="height / width of the largest centred rectangle the restored image is cropped to")
     cli._objective_arguments(ap)
+    cli._lpips_pool_argument(ap)
     ap.add_argument("--gpus", type=str, default="0", help="the visible device(s)")
     return ap
 

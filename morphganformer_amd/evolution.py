@@ -151,6 +151,7 @@ def build_parser():
     ap.add_argument("--keep-images", type=int, default=64, help="device slots of the improvement trail (raised to --batch if smaller)")
     ap.add_argument("--ratio", type=float, default=1.0, help="height / width of the largest centred rectangle an image is cropped to when written")
     cli._objective_arguments(ap)
+    cli._lpips_pool_argument(ap)
     ap.add_argument("--gpus", type=str, default="0", help="the visible device(s)")
     return ap
 

@@ -94,8 +94,8 @@ class GradientProjectionEngine(ProjectionEngine):
         if a.pixel_term not in ("mse", "dssim", "msssim") or a.pool_above:
             raise _lib.MgfError("GradientProjectionEngine: pixel_term='psnr', pixel_term='lbp' and pool_above are literal-mode objectives with no backward pass "
                                 "here: PSNR as the script minimises it descends towards a LARGER error, the LBP distance is a histogram of integer codes "
-                                "(its gradient is zero almost everywhere), and pool_above is the v1 driver's block mean in front of the losses, which has "
-                                "no adjoint kernel; gradient mode descends Wing / LPIPS / MSE / DSSIM / MS-SSIM / biometric / MDF")
+                                "(its gradient is zero almost everywhere), and pool_above is the v1 driver's block mean in front of EVERY image-space loss, which has "
+                                "no adjoint here (the LPIPS term alone has one: percept=PerceptualLoss(pool_above=N)); gradient mode descends Wing / LPIPS / MSE / DSSIM / MS-SSIM / biometric / MDF")
         assert latent_space in ("z", "w+"), latent_space
         self.latent_space = latent_space
         ls = (G.cfg.k, G.cfg.num_ws, G.cfg.w_dim) if latent_space == "w+" else (G.cfg.k, G.cfg.z_dim)

@@ -11,6 +11,8 @@ vendored in the reference and whose ImageNet weights are a remote fetch).
   * All convolutions run on the FP32-MFMA tap kernel with a fused bias+ReLU epilogue; Fire expand branches write their
     halves of the concat buffer directly.
   * The target image's 7 feature maps are computed once (`set_target`) -- the reference recomputes them every iteration.
+  * `pool_above=N` block-averages every image taller than N by height // N in front of the backbone (projection_example_v1.py:148-155, for
+    this term only) and `grad_into` applies the adjoint: callers hand in and get back full-size tensors (csrc/block_pool.hip).
 """
 from __future__ import annotations
 
@@ -74,16 +76,25 @@ class PerceptualLoss(torch.nn.Module):
     with spatial=True -> the [N,1,H,W] map of PNetLin(spatial=True) (networks_basic.py:75-76,85-92; `distance_map_into`)."""
 
     def __init__(self, model="net-lin", net="squeeze", colorspace="rgb", spatial=False, use_gpu=True, gpu_ids=(0,),
-                 backbone_state=None, backbone_seed=None, allow_random_backbone=False, device="cuda"):
+                 backbone_state=None, backbone_seed=None, allow_random_backbone=False, device="cuda", pool_above=0):
         """backbone_state: the torchvision feature weights (`features.N...` keys, tensors or arrays; `load_backbone_state` reads a
         .pth / .npz) -- what the reference obtains with tv.<net>(pretrained=True) (pretrained_networks.py:9,60,100).  Without it
         the distance would be computed on meaningless features, so that is an ERROR unless the caller opts in to the seeded random
         backbone (allow_random_backbone=True or an explicit backbone_seed: benchmarks and parity tests, where only the arithmetic
-        matters)."""
+        matters).
+        pool_above: an image [n,3,H,W] with H > pool_above is block-averaged by f = H // pool_above in front of the backbone (0 = off; the
+        rule of ProjectionArgs.pool_above, misc.pool_factor, for this term alone): targets, candidates and region weights are given at
+        their full size, `grad_into` fills a full-size gradient.  An image at or below pool_above goes through untouched."""
         super().__init__()
         if model != "net-lin" or colorspace != "rgb":
             raise NotImplementedError("the MI355X path implements model='net-lin', colorspace='rgb'")
         self.spatial = bool(spatial)
+        self.pool_above = int(pool_above)
+        if self.pool_above < 0:
+            raise _lib.MgfError(f"PerceptualLoss(pool_above={pool_above!r}): a size in pixels, or 0 for no pooling")
+        if self.spatial and self.pool_above:
+            raise _lib.MgfError("PerceptualLoss(spatial=True, pool_above=...): the map is defined at the image's own size; a map of the "
+                                "pooled image is not built")
         if net not in NET_CHNS:
             raise NotImplementedError(f"unknown LPIPS backbone {net!r} (squeeze, vgg, alex)")
         if not use_gpu:
@@ -105,6 +116,7 @@ class PerceptualLoss(torch.nn.Module):
         lin = np.load(os.path.join(WEIGHTS_DIR, f"lpips_lin_{net}.npz"))
         self.lins = [torch.as_tensor(lin[f"lin{i}"], dtype=torch.float32, device=self.device_) for i in range(len(self.chns))]
         self._feats = {}
+        self._pooled = {}                 # (n, H, W) -> the block-averaged image [n,3,H/f,W/f] (pool_above); allocated on first use
         self._stats = {}
         self._map_ws = {}                 # (n, H) -> per-tap maps of distance_map_into (spatial=True)
         self._map_taps = None             # spatial=True beside the fused stem: the target's unit taps through the un-fused path
@@ -113,7 +125,8 @@ class PerceptualLoss(torch.nn.Module):
         self.pair_offset = None           # [B] float32 = alpha (1 - alpha) LPIPS(Ta, Tb) while a target pair is set (set_target_pair)
         self._pair_offset_buf = None      # ... its buffer, kept across pairs of the same count (a captured graph reads it)
         self._last, self._last_hw = None, None
-        self._region = None               # float64 [nw, H, W] on the CPU while a region weight is set (set_region_weight)
+        self._region = None               # float64 [nw, H, W] on the CPU while a region weight is set (set_region_weight), at the backbone's size
+        self._region_given = None         # ... and the (H, W) it was handed in at (the images' own size; differs under pool_above)
         self._region_taps = {}            # (nw, H, W) -> per-tap normalised weights [nw, h_l * w_l], rewritten in place per weight
         # the one-pass stem exists for SqueezeNet's first three layers; MGF_LPIPS_STEM=0 (tuning hook) keeps them separate
         self.fused_stem = net == "squeeze" and os.environ.get("MGF_LPIPS_STEM", "1") != "0"
@@ -133,17 +146,45 @@ class PerceptualLoss(torch.nn.Module):
             self._feats[key] = f
         return f
 
+    def _pool_factor(self, H, W):
+        """Block side for H x W images (1: not pooled); MgfError when the image is not a whole number of blocks."""
+        f = misc.pool_factor(H, self.pool_above)
+        if f > 1 and (H % f or W % f):
+            raise _lib.MgfError(f"PerceptualLoss(pool_above={self.pool_above}): a {H}x{W} image is not a whole number of {f}x{f} blocks "
+                                f"(f = {H} // {self.pool_above})")
+        return f
+
+    def _pool(self, img):
+        """img [n,3,H,W] as the backbone sees it: itself, or under pool_above its block mean in the buffer cached for (n, H, W)."""
+        if not self.pool_above:
+            return img
+        n, c, H, W = img.shape
+        f = self._pool_factor(H, W)
+        if f == 1:
+            return img
+        _lib.require_gpu(img)
+        x = img.float().contiguous()
+        out = self._pooled.get((n, H, W))
+        if out is None:
+            out = self._pooled[(n, H, W)] = torch.empty(n, c, H // f, W // f, dtype=torch.float32, device=self.device_)
+        _lib.check(_lib.lib().mgf_block_mean_f32(out.data_ptr(), x.data_ptr(), n * c, H, W, f, _lib.stream_ptr()), "block_mean")
+        return out
+
     def set_region_weight(self, weight):
         """Weight the distance by region: weight [H,W], [1,1,H,W] (one map for every candidate) or [n,1,H,W] (one per candidate) >= 0 at the
-        image size; None: the uniform spatial mean again, with today's dispatch (fused stem included).  Per tap the weight is pooled to the
-        tap's grid and normalised (`region_tap_weights`), and `distance_into`, `grad_into`, `distance_per_tap` and the scalar module call
+        image size (the full size under pool_above: the weight is block-averaged like the images, in float64 on the host); None: the uniform
+        spatial mean again, with today's dispatch (fused stem included).  Per tap the weight is pooled to the tap's grid and normalised (`region_tap_weights`), and `distance_into`, `grad_into`, `distance_per_tap` and the scalar module call
         compute sum_l sum_p omega_l[p] m_l[p] on the un-fused path (the fused stem consumes tap 0 with a uniform mean).  `distance_map_into`
         is unaffected.  The per-tap weights live in buffers that are rewritten in place while the geometry stays (captured graphs read
         them).  With a target pair set, call `set_target_pair` again afterwards: its constant depends on the weight."""
         if weight is None:
-            self._region = None
+            self._region = self._region_given = None
             return
         w = check_region_weight(weight, "set_region_weight")
+        given = tuple(w.shape[1:])
+        f = self._pool_factor(*given)
+        if f > 1:
+            w = w.reshape(w.shape[0], given[0] // f, f, given[1] // f, f).mean(dim=(2, 4)).contiguous()
         nw, H, W = w.shape
         om = region_tap_weights(w, [s[1:] for s in self._features(nw, H, W).tap_shapes])
         bufs = self._region_taps.get((nw, H, W))
@@ -151,16 +192,19 @@ class PerceptualLoss(torch.nn.Module):
             bufs = self._region_taps[(nw, H, W)] = [torch.empty(nw, o.shape[1] * o.shape[2], dtype=torch.float32, device=self.device_) for o in om]
         for b, o in zip(bufs, om):
             b.copy_(o.reshape(nw, -1))
-        self._region = w
+        self._region, self._region_given = w, given
         self.pair_offset = None
 
-    def _region_for(self, n, h, w):
-        """(per-tap weight buffers, nw) of the weight that is set, checked against n candidates of size h x w; None without a weight."""
+    def _region_for(self, n, h, w, full=None):
+        """(per-tap weight buffers, nw) of the weight that is set, checked against n candidates of size h x w at the backbone (the pooled
+        size under pool_above; full: the size they were handed in at); None without a weight."""
         if self._region is None:
             return None
         nw, H, W = self._region.shape
         if (H, W) != (h, w):
             raise ValueError(f"region weight is {H}x{W} but the images are {h}x{w}")
+        if full is not None and tuple(full) != self._region_given:          # (pool_above: a weight handed in at the pooled size)
+            raise ValueError(f"region weight was given at {self._region_given[0]}x{self._region_given[1]} but the images are {full[0]}x{full[1]}")
         if nw not in (1, n):
             raise ValueError(f"{nw} region weights cannot pair with {n} candidates")
         return self._region_taps[(nw, H, W)], nw
@@ -169,6 +213,7 @@ class PerceptualLoss(torch.nn.Module):
         """Cache the target's feature maps, unit-normalised over channels (they do not change across projection iterations; the
         reference recomputes and re-normalises them every step).  One target [1,3,H,W] is shared by every candidate of
         `distance_into`; n targets pair up with n candidates (independent projections advanced in lockstep)."""
+        target = self._pool(target)
         n, _, h, w = target.shape
         self._target_n = n
         f = self._features(n, h, w)
@@ -242,10 +287,19 @@ class PerceptualLoss(torch.nn.Module):
 
     def grad_into(self, dimg, scale=1.0, accumulate=False):
         """dimg (+)= d(scale * distance)/d(pred) for the pred of the latest `distance_into(..., keep_taps=True)` call
-        (what autograd computes through networks_basic.py:64-92 and the backbone).  SqueezeNet and VGG16 backbones."""
+        (what autograd computes through networks_basic.py:64-92 and the backbone).  SqueezeNet and VGG16 backbones.  dimg has that pred's
+        own size: under pool_above the backward pass runs at the pooled size and the block mean's adjoint spreads it over dimg."""
         f = self._last
-        assert f is not None and tuple(dimg.shape) == (f.n, 3, *self._last_hw), "call distance_into(..., keep_taps=True) first"
-        g = f.backward(self._target_taps, self.lins, scale, per_sample=self._target_n > 1, region=self._region_for(f.n, *self._last_hw))
+        assert f is not None and tuple(dimg.shape) == (f.n, 3, *self._last_hw[0]), "call distance_into(..., keep_taps=True) first"
+        full, pooled = self._last_hw
+        g = f.backward(self._target_taps, self.lins, scale, per_sample=self._target_n > 1, region=self._region_for(f.n, *pooled, full=full))
+        if full != pooled:
+            # g is a view of the backbone's input gradient (it may stop short of the pooled image): its own extent, pitch and plane stride
+            assert dimg.dtype == torch.float32 and dimg.is_contiguous() and g.stride(3) == 1 and g.stride(0) == 3 * g.stride(1)
+            _lib.check(_lib.lib().mgf_block_mean_adjoint_f32(dimg.data_ptr(), g.data_ptr(), f.n * 3, full[0], full[1], full[0] // pooled[0],
+                                                             g.shape[2], g.shape[3], g.stride(2), g.stride(1), int(bool(accumulate)),
+                                                             _lib.stream_ptr()), "block_mean_adjoint")
+            return dimg
         if not accumulate:
             dimg.zero_()
         dimg[:, :, :g.shape[2], :g.shape[3]].add_(g)
@@ -256,7 +310,9 @@ class PerceptualLoss(torch.nn.Module):
         checked against pred's, the reduce scratch, `tap_stats` reset, the region weight that is set, and the forward -- the fused stem
         (which adds tap 0 to out [n], or writes row 0 of out [taps, n]; entry 0 of taps is then None) where nothing needs tap 0 itself.
         keep_taps: None leaves what `grad_into` reads alone.  out=None: the [taps, n] rows of `distance_per_tap` are allocated here.
-        scalar=False (the map): no scratch, no region weight, every tap in the workspace."""
+        scalar=False (the map): no scratch, no region weight, every tap in the workspace.  Under pool_above pred is block-averaged first."""
+        full = tuple(pred.shape[2:])
+        pred = self._pool(pred)
         n, _, h, w = pred.shape
         f = self._features(n, h, w)
         assert self._target_taps is not None, "call set_target first"
@@ -269,9 +325,9 @@ class PerceptualLoss(torch.nn.Module):
             if out is None:
                 out = torch.zeros(len(self.chns), n, dtype=torch.float32, device=self.device_)
         if keep_taps is not None:
-            self._last, self._last_hw = (f, (h, w)) if keep_taps else (None, None)
+            self._last, self._last_hw = (f, (full, (h, w))) if keep_taps else (None, None)      # (the size handed in, the backbone's)
         f.tap_stats = {}                            # tap index -> per-pixel sums of this forward (keep_taps only)
-        region = self._region_for(n, h, w) if scalar else None
+        region = self._region_for(n, h, w, full=full) if scalar else None
         if scalar and self.fused_stem and not keep_taps and not per_sample and region is None:
             f.stem(pred.contiguous(), feat_ref=self._target_taps[0], lin=self.lins[0], dist_out=out if out.dim() == 1 else out[0],
                    scratch=self._scratch)

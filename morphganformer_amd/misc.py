@@ -20,6 +20,13 @@ def as_numpy(x, dtype=None):
     return np.asarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=dtype)
 
 
+def pool_factor(size, pool_above):
+    """The block side an image `size` pixels tall is averaged by in front of a loss that pools above `pool_above` pixels
+    (projection_example_v1.py:150-155: height // 256); 1 = not pooled (pool_above 0, or an image at or below it).  The one expression behind
+    ProjectionArgs.pool_above and PerceptualLoss(pool_above=...)."""
+    return size // pool_above if pool_above and size > pool_above else 1
+
+
 def crop_center(img, cw, ch):
     """misc.py:88-90."""
     w, h = img.size

@@ -33,7 +33,7 @@ from functools import partial
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, misc
 from .pixel_term import MSSSIM_WEIGHTS, PixelTerm, msssim_max_levels, msssim_weights  # noqa: F401  (the MS-SSIM helpers are public here)
 from .trail import ImprovementTrail
 
@@ -94,7 +94,7 @@ class ProjectionArgs:
 
     def pool_factor(self, resolution):
         """The block side `pool_above` averages a resolution x resolution image by (1 = not pooled): the losses see resolution // factor pixels."""
-        return resolution // self.pool_above if self.pool_above and resolution > self.pool_above else 1
+        return misc.pool_factor(resolution, self.pool_above)
 
 
 def get_lr(t, initial_lr, rampdown=0.25, rampup=0.05):
