@@ -528,7 +528,8 @@ int mgf_maxpool3x3s2_ceil_f32(float* y, const float* x, int32_t nc, int32_t in_h
  *   select:  for j in 0..batch-1 (in step order, s = *step + j < steps_total):
  *              total = (double)p_loss[j] + lamda * w_loss[j] + (double)(beta * mse[j])
  *            -- torch's promotion of `p_loss + args.lamda * w_loss + args.beta * mse_loss` (:179): lamda is a python double times a
- *            float64 tensor, beta a python scalar times a float32 tensor (float32 product) --
+ *            float64 tensor, beta a python scalar times a float32 tensor (float32 product); the two products and the sums of the three terms
+ *            (left to right from 0.0, an absent slot skipped) are separate roundings, no fused multiply-add --
  *            if total < *min_loss: min_loss=total, best_latent=latent_n[j], best_step=s.
  *            losses_out[s] = total (NaN when valid[s] == 0 = "no face", ...sqz_MSE.py:165-166; valid NULL = always valid).
  *            Finally *step = min(*step + batch, steps_total).  All state lives on the device -> graph-replayable.

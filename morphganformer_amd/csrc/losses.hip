@@ -453,11 +453,13 @@ __global__ __launch_bounds__(256) void select_kernel(double* min_loss, float* be
         }
         if (threadIdx.x == 0) {
             const int valid = valid_tab ? valid_tab[s] : 1;
-            // same evaluation order and promotions as `p_loss + lamda * w_loss + beta * mse_loss` with a float64 wing term
+            // same evaluation order and promotions as `p_loss + lamda * w_loss + beta * mse_loss` with a float64 wing term; every product and
+            // sum is a rounding of its own like torch's (`total += lamda * w` would contract into one fma under -ffp-contract=on) -- the
+            // spelling of demorph.hip's row totals, which promise these bits
             double total = 0.0;
-            if (p_loss) total += (double)p_loss[j];
-            if (w_loss) total += lamda * w_loss[j];
-            if (mse_loss) total += (double)(beta * mse_loss[j]);
+            if (p_loss) total = __dadd_rn(total, (double)p_loss[j]);
+            if (w_loss) total = __dadd_rn(total, __dmul_rn(lamda, w_loss[j]));
+            if (mse_loss) total = __dadd_rn(total, (double)__fmul_rn(beta, mse_loss[j]));
             if (losses_out) losses_out[s] = valid ? total : __longlong_as_double(0x7ff8000000000000LL);
             take = valid && total < min_loss[0];
             if (take) { min_loss[0] = total; best_step[0] = s; }

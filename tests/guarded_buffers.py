@@ -15,26 +15,37 @@ def rel(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
+INT_FILL = {torch.int32: -1515870811}        # the "nothing was written here" pattern of the integer variant (0xA5 bytes)
+
+
 class Guarded:
     """A float32 device tensor `t` at the head of a NaN-filled buffer.  span = 16: room for a [rows][T] table read or written with row
-    stride 16 (the padded width of the kernels' tables); span = 1: 64 floats behind the end."""
+    stride 16 (the padded width of the kernels' tables); span = 1: 64 floats behind the end.
+    dtype: float64 likewise; an int32 buffer is filled with INT_FILL's pattern instead of NaN (a value no test writes on purpose)."""
 
-    def __init__(self, shape, data=None, span=1, offset=0):
+    def __init__(self, shape, data=None, span=1, offset=0, dtype=torch.float32):
         numel = int(np.prod(shape))
-        self.buf = torch.full((offset + numel * span + 64,), NAN, dtype=torch.float32, device="cuda")
+        self.fill = NAN if dtype.is_floating_point else INT_FILL[dtype]
+        self.buf = torch.full((offset + numel * span + 64,), self.fill, dtype=dtype, device="cuda")
         self.t = self.buf[offset:offset + numel].view(*shape)
         self.end = offset + numel
         if data is not None:
-            self.t.copy_(data.detach().to(torch.float32))
+            self.t.copy_(torch.as_tensor(data).detach().to(dtype))
 
     def ptr(self):
         return self.t.data_ptr()
 
+    def _blank(self, x):
+        return torch.isnan(x) if x.dtype.is_floating_point else x == self.fill
+
     def guard_intact(self):
-        return bool(torch.isnan(self.buf[self.end:]).all())
+        return bool(self._blank(self.buf[self.end:]).all())
 
     def written(self):
-        return not bool(torch.isnan(self.t).any())
+        return not bool(self._blank(self.t).any())
+
+    def numpy(self):
+        return self.t.detach().cpu().numpy()
 
 
 def g_in(t64, span=1):
