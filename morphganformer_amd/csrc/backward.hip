@@ -14,27 +14,52 @@ namespace {
 
 constexpr int BWD_CHUNK = 4096;          // elements of one (sample, channel) plane handled by one workgroup
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
+// Chunk `chunk` of plane (n, ch) of [n][c][hw] maps: the plane's offset and the chunk's element range inside it.
+struct Chunk { int64_t base, i0, i1; };
+__device__ __forceinline__ Chunk chunk_of(int chunk, int ch, int n, int c, int64_t hw) {
+    const int64_t i0 = (int64_t)chunk * BWD_CHUNK;
+    return {((int64_t)n * c + ch) * hw, i0, min(hw, i0 + (int64_t)BWD_CHUNK)};
+}
+
+// part[n, ch, index] (of `count` per plane) = the workgroup's sum of acc
+__device__ __forceinline__ void store_partial(float* part, float acc, float* red, int n, int c, int ch, int count, int index) {
+    const float tot = mgf_block_sum_256(acc, red);
+    if (threadIdx.x == 0) part[((int64_t)n * c + ch) * count + index] = tot;
 }
 
 // ------------------------------------------------------------------------------------------ activation backward
+// The activation side of a layer:  y = lrelu(z, alpha) * gain [+ residual]  with  z = c + noise * strength + bias  (c: the conv's output).
+struct ActSide {
+    const float* bias; const float* noise; const float* nstr;
+    int noise_n;
+    float alpha, gain;
+};
+
+// ... for one (sample, channel) plane of `plane` elements, built once per workgroup.  v is the activation's own output (y - residual).
+struct ActPlane {
+    float b, ns, inv_gain, inv_alpha, alpha, gain;
+    const float* nz;                    // the plane's noise map (null: none)
+    __device__ __forceinline__ ActPlane(const ActSide& a, int n, int ch, int64_t plane)
+        : b(a.bias ? a.bias[ch] : 0.f), ns(a.noise ? (a.nstr ? *a.nstr : 1.f) : 0.f), inv_gain(1.f / a.gain), inv_alpha(1.f / a.alpha),
+          alpha(a.alpha), gain(a.gain), nz(a.noise ? a.noise + (int64_t)(a.noise_n > 1 ? n : 0) * plane : nullptr) {}
+    // d(z) from the gradient d of the activation's output
+    __device__ __forceinline__ float dz(float d, float v) const { return d * gain * (v > 0.f ? 1.f : alpha); }
+    // c, recovered by inverting the activation (nv: the element's noise value)
+    __device__ __forceinline__ float c(float v, float nv) const {
+        const float zv = (v > 0.f ? v : v * inv_alpha) * inv_gain;
+        return zv - b - nv * ns;
+    }
+};
+
 struct ActBwdParams {
     float* dz;
     float* part;
     const float* dy;
     const float* y;
     const float* res;
-    const float* bias;
-    const float* noise;
-    const float* nstr;
-    int noise_n, c, nchunk;
+    ActSide act;
+    int c, nchunk;
     int64_t hw;
-    float alpha, gain;
     const float* res_low;   // LOW: the residual at half resolution [n][c][h/2][w/2] (res is null), up-sampled here
     int w;                  // LOW: row length of the maps (w % 4 == 0, h = hw / w even)
 };
@@ -59,6 +84,13 @@ __device__ __forceinline__ float4 up2_residual4(const float* lowp, int lh, int l
     return make_float4(0.25f * cc[0] + 0.75f * cc[1], 0.75f * cc[1] + 0.25f * cc[2], 0.25f * cc[1] + 0.75f * cc[2], 0.75f * cc[2] + 0.25f * cc[3]);
 }
 
+// ... for elements i .. i + 3 (i % 4 == 0) of plane (n, ch); P: ActBwdParams or StyleActParams (res_low, w, c, hw)
+template <class P>
+__device__ __forceinline__ float4 residual_low4(const P& p, int n, int ch, int64_t i) {
+    const int yy = (int)(i / p.w);
+    return up2_residual4(p.res_low + ((int64_t)n * p.c + ch) * (p.hw >> 2), (int)(p.hw / p.w) >> 1, p.w >> 1, yy, (int)(i - (int64_t)yy * p.w));
+}
+
 // grid (nchunk, c, n).  y = lrelu(z) * gain + res  with  z = cval + noise * strength + bias:
 //   dz = dy * gain * (y - res > 0 ? 1 : alpha);    part[n,c,chunk] = sum dz * cval   (cval recovered by inverting the activation)
 template <bool VEC, bool LOW = false>
@@ -66,35 +98,22 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(ActBwdParams p) {
     static_assert(VEC || !LOW, "the half-resolution residual rides on the 16-byte path");
     __shared__ float red[4];
     const int chunk = blockIdx.x, ch = blockIdx.y, n = blockIdx.z;
-    const int64_t base = ((int64_t)n * p.c + ch) * p.hw;
-    const int64_t i0 = (int64_t)chunk * BWD_CHUNK;
-    const int64_t i1 = min(p.hw, i0 + (int64_t)BWD_CHUNK);
-    const float b = p.bias ? p.bias[ch] : 0.f;
-    const float ns = p.noise ? (p.nstr ? *p.nstr : 1.f) : 0.f;
-    const float* nz = p.noise ? p.noise + (int64_t)(p.noise_n > 1 ? n : 0) * p.hw : nullptr;
-    const float inv_gain = 1.f / p.gain, inv_alpha = 1.f / p.alpha;
+    const auto [base, i0, i1] = chunk_of(chunk, ch, n, p.c, p.hw);
+    const ActPlane act(p.act, n, ch, p.hw);
     float acc = 0.f;
     auto one = [&](float yv, float rv, float dyv, float nv, float& dzv) {
         const float v = yv - rv;
-        const bool pos = v > 0.f;
-        dzv = dyv * p.gain * (pos ? 1.f : p.alpha);
-        if (p.part) {
-            const float zv = (pos ? v : v * inv_alpha) * inv_gain;
-            acc += dzv * (zv - b - nv * ns);
-        }
+        dzv = act.dz(dyv, v);
+        if (p.part) acc += dzv * act.c(v, nv);
     };
     if (VEC) {          // hw % 4 == 0 and 16-byte aligned operands: four elements per lane and access
         for (int64_t i = i0 + 4 * threadIdx.x; i < i1; i += 1024) {
             const float4 yv = *reinterpret_cast<const float4*>(p.y + base + i);
             const float4 dv = *reinterpret_cast<const float4*>(p.dy + base + i);
             float4 rv;
-            if (LOW) {
-                const int yy = (int)(i / p.w);
-                rv = up2_residual4(p.res_low + ((int64_t)n * p.c + ch) * (p.hw >> 2), (int)(p.hw / p.w) >> 1, p.w >> 1, yy, (int)(i - (int64_t)yy * p.w));
-            } else {
-                rv = p.res ? *reinterpret_cast<const float4*>(p.res + base + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            const float4 nv = nz ? *reinterpret_cast<const float4*>(nz + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (LOW) rv = residual_low4(p, n, ch, i);
+            else rv = p.res ? *reinterpret_cast<const float4*>(p.res + base + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 nv = act.nz ? *reinterpret_cast<const float4*>(act.nz + i) : make_float4(0.f, 0.f, 0.f, 0.f);
             float4 o;
             one(yv.x, rv.x, dv.x, nv.x, o.x); one(yv.y, rv.y, dv.y, nv.y, o.y);
             one(yv.z, rv.z, dv.z, nv.z, o.z); one(yv.w, rv.w, dv.w, nv.w, o.w);
@@ -103,26 +122,20 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(ActBwdParams p) {
     } else {
         for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
             float o;
-            one(p.y[base + i], p.res ? p.res[base + i] : 0.f, p.dy[base + i], nz ? nz[i] : 0.f, o);
+            one(p.y[base + i], p.res ? p.res[base + i] : 0.f, p.dy[base + i], act.nz ? act.nz[i] : 0.f, o);
             p.dz[base + i] = o;
         }
     }
-    if (p.part) {
-        const float tot = block_sum(acc, red);
-        if (threadIdx.x == 0) p.part[((int64_t)n * p.c + ch) * p.nchunk + chunk] = tot;
-    }
+    if (p.part) store_partial(p.part, acc, red, n, p.c, ch, p.nchunk, chunk);
 }
 
 // part[n,c,chunk] = sum a * b over the chunk
 __device__ __forceinline__ void channel_dot_body(float* part, const float* a, const float* b, int c, int64_t hw, int nchunk, int chunk, int ch, int n,
                                                  float* red) {
-    const int64_t base = ((int64_t)n * c + ch) * hw;
-    const int64_t i0 = (int64_t)chunk * BWD_CHUNK;
-    const int64_t i1 = min(hw, i0 + (int64_t)BWD_CHUNK);
+    const auto [base, i0, i1] = chunk_of(chunk, ch, n, c, hw);
     float acc = 0.f;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) acc += a[base + i] * b[base + i];
-    const float tot = block_sum(acc, red);
-    if (threadIdx.x == 0) part[((int64_t)n * c + ch) * nchunk + chunk] = tot;
+    store_partial(part, acc, red, n, c, ch, nchunk, chunk);
 }
 
 __global__ __launch_bounds__(256) void channel_dot_kernel(float* part, const float* a, const float* b, int c, int64_t hw, int nchunk) {
@@ -136,9 +149,7 @@ __global__ __launch_bounds__(256) void style_grad_kernel(float* part, float* dx,
                                                          int64_t hw, int nchunk, int accumulate) {
     __shared__ float red[4];
     const int chunk = blockIdx.x, ch = blockIdx.y, n = blockIdx.z;
-    const int64_t base = ((int64_t)n * c + ch) * hw;
-    const int64_t i0 = (int64_t)chunk * BWD_CHUNK;
-    const int64_t i1 = min(hw, i0 + (int64_t)BWD_CHUNK);
+    const auto [base, i0, i1] = chunk_of(chunk, ch, n, c, hw);
     const float sv = s ? s[(int64_t)n * c + ch] : 1.f;
     float acc = 0.f;
     if (VEC) {
@@ -161,8 +172,7 @@ __global__ __launch_bounds__(256) void style_grad_kernel(float* part, float* dx,
             dx[base + i] = accumulate ? dx[base + i] + o : o;
         }
     }
-    const float tot = block_sum(acc, red);
-    if (threadIdx.x == 0) part[((int64_t)n * c + ch) * nchunk + chunk] = tot;
+    store_partial(part, acc, red, n, c, ch, nchunk, chunk);
 }
 
 // ------------------------------------------------------------------------------------------ duplex attention backward
@@ -815,290 +825,21 @@ __global__ __launch_bounds__(256) void latent_grad_gather_kernel(float* dw, cons
         dw[(int64_t)n * k * wdim + idx] = acc * scale;
     }
 }
-
-// ------------------------------------------------------------------------------------------ loss-side backward
-// LPIPS tap (networks_basic.py:70-87): l = (scale / hw) * sum_p sum_c lin[c] (f0[c] q - u1[c])^2 with q = 1 / (|f0| + 1e-10).
-// One lane per pixel, two sweeps over the channels:  A = sum f0^2, B = sum lin f0^2, Cc = sum lin u1 f0  give
-//   <du0, f0> = k (q B - Cc),   df0[c] = q k lin[c] (f0[c] q - u1[c]) - <du0, f0> q^2 / |f0| * f0[c],   k = 2 scale / hw.
-// An all-zero pixel (|f0| = 0) gets a zero gradient (torch autograd yields NaN there: sqrt'(0) * 0).
-// RELU: the tap is a ReLU output (all of them are) and the ReLU's backward rides along: dz = f0 > 0 ? din + df0 : 0 (din may be
-// null), channels [0, c_split) to oa [n, c_split, hw], the rest to ob [n, c - c_split, hw] (mgf_relu_bwd_split_f32's layout); without
-// RELU oa is df0 [n, c, hw] and `accumulate` adds to it.
-// CPT > 0: c <= CPT * (256 / PXB), and the lane keeps its CPT channels of f0 and f1 in registers between the two sweeps: 629 -> 588 us
-// at 8 x 64 x 511^2 with 16 channels per lane; with 32 (128 channels) the registers cost more residency than the second sweep's
-// mostly cache-resident reads (321 -> 435 us), so only CPT = 16 is built.  Wider pixel blocks (128, 256) measured no faster than 64.
-// WEIGHTED (region weights): l = scale * sum_p omega[p] sum_c ..., so k = 2 scale omega[p] per pixel -- the host passes 2 scale and every lane
-// multiplies by its pixel's weight (one more buffer load); omega = 0 gives g = 0 exactly, i.e. din through the ReLU mask.
-template <int PXB, bool RELU, int CPT, bool WEIGHTED = false>
-__global__ __launch_bounds__(256) void lpips_layer_bwd_kernel(float* oa, float* ob, const float* din, const float* f0, const float* f1u,
-                                                              const float* lin, int c, int c_split, int64_t hw, int64_t f1_bs, float k,
-                                                              int accumulate, const float* stats, const float* wmap, int64_t w_bs) {
-    // a workgroup owns PXB consecutive pixels; its G = 256 / PXB lane groups split the channels and meet in LDS
-    constexpr int G = 256 / PXB;
-    constexpr int NV = CPT > 0 ? CPT : 1;
-    __shared__ float part[3][G][PXB];
-    const int n = blockIdx.y, px = threadIdx.x % PXB, grp = threadIdx.x / PXB;
-    const int64_t p = (int64_t)blockIdx.x * PXB + px;
-    const bool valid = p < hw;
-    const int64_t pc = valid ? p : hw - 1;
-    // Buffer addressing (round 3, like the forward kernel): a thread's channels are G planes apart, so the channel part of every address is
-    // a scalar offset (j G hw) on one per-lane offset (grp hw + pixel); the range check covers both, so a channel past c -- or past
-    // c_split in the first output, before it in the second -- reads 0 / is not stored, without a per-lane test.  Host: c * hw * 4 < 2^32.
-    const unsigned plane_b = 4u * (unsigned)hw;
-    const unsigned vo = (unsigned)grp * plane_b + 4u * (unsigned)pc;
-    const unsigned cbytes = (unsigned)c * plane_b;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(f0 + (int64_t)n * c * hw), 0, (int)cbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)(f1u + (int64_t)n * f1_bs), 0, (int)cbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void*)lin, 0, 4 * c, 0x00020000);
-    auto ld = [&](const __amdgpu_buffer_rsrc_t& r, int j) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, (int)((unsigned)(j * G) * plane_b), 0));
-    };
-    auto ldlin = [&](int j) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, 4u * (unsigned)grp, 4 * j * G, 0)); };
-    const int nj = (c + G - 1) / G;                   // channel steps (a lane whose channel of the last step is past c reads zeros)
-    if (WEIGHTED) {
-        const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(wmap + (int64_t)n * w_bs), 0, (int)plane_b, 0x00020000);
-        k *= __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, 4u * (unsigned)pc, 0, 0));
-    }
-    float va[NV], vb[NV];
-    float A = 0.f, B = 0.f, Cc = 0.f;
-    // stats: the per-pixel sums A, B, C of the forward (mgf_lpips_layer_stats_f32, [n][3][hw]) -- no first sweep, no meeting in LDS
-    if (CPT == 0 && stats) {
-        const float* sp = stats + (int64_t)n * 3 * hw + pc;
-        A = sp[0]; B = sp[hw]; Cc = sp[2 * hw];
-    } else {
-    if (CPT > 0) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) { va[j] = ld(ra, j); vb[j] = ld(rb, j); }
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const float l = ldlin(j);
-            A += va[j] * va[j];
-            B += l * va[j] * va[j];
-            Cc += l * vb[j] * va[j];
-        }
-    } else {
-#pragma unroll 4
-        for (int j = 0; j < nj; ++j) {
-            const float v = ld(ra, j), l = ldlin(j);
-            A += v * v;
-            B += l * v * v;
-            Cc += l * ld(rb, j) * v;
-        }
-    }
-    part[0][grp][px] = A; part[1][grp][px] = B; part[2][grp][px] = Cc;
-    __syncthreads();
-    A = B = Cc = 0.f;
-#pragma unroll
-    for (int g = 0; g < G; ++g) { A += part[0][g][px]; B += part[1][g][px]; Cc += part[2][g][px]; }
-    }
-    const float nrm = sqrtf(A);
-    const float q = 1.f / (nrm + 1e-10f);
-    const float dot = k * (q * B - Cc);
-    const float coef = nrm > 0.f ? dot * q * q / nrm : 0.f;
-    // outputs: RELU -> channels [0, c_split) to oa, the rest to ob; else oa holds all c channels
-    const unsigned vst = valid ? vo : 0xFFFFFFF0u;
-    const int ca = RELU ? c_split : c;
-    const __amdgpu_buffer_rsrc_t rda = __builtin_amdgcn_make_buffer_rsrc((void*)(oa + (int64_t)n * ca * hw), 0, (int)((unsigned)ca * plane_b), 0x00020000);
-    const bool has_b = RELU && ob != nullptr && c > c_split;
-    const __amdgpu_buffer_rsrc_t rdb = __builtin_amdgcn_make_buffer_rsrc((void*)(has_b ? ob + (int64_t)n * (c - c_split) * hw : oa), 0,
-                                                                         has_b ? (int)((unsigned)(c - c_split) * plane_b) : 0, 0x00020000);
-    const bool has_di = RELU && din != nullptr;
-    const __amdgpu_buffer_rsrc_t rdi = __builtin_amdgcn_make_buffer_rsrc((void*)(has_di ? din + (int64_t)n * c * hw : f0), 0, has_di ? (int)cbytes : 0, 0x00020000);
-    auto one = [&](int j, float v, float u) {
-        const int so = (int)((unsigned)(j * G) * plane_b);
-        float g = q * k * ldlin(j) * (v * q - u) - coef * v;
-        if (RELU) {
-            g = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rdi, vo, so, 0)) + g;       // (no din: zero-size descriptor, reads 0)
-            g = v > 0.f ? g : 0.f;
-            const int ch = grp + j * G, cb = j * G - c_split;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, g), rda, vst, so, 0);       // ch >= c_split: past rda's end
-            // second output: channel ch - c_split.  With c_split a multiple of G the step's channel base j G - c_split is wave-uniform (a
-            // negative one means this step lies in the first output); otherwise the whole offset is per lane.  (The range check adds
-            // vector and scalar offset WITHOUT 32-bit wrap: an offset that "wraps back" into range is still out of range.)
-            const bool even = c_split % G == 0;
-            const unsigned vsb = !valid ? 0xFFFFFFF0u
-                               : even ? (cb >= 0 ? vo : 0xFFFFFFF0u)
-                                      : (ch >= c_split ? (unsigned)(ch - c_split) * plane_b + 4u * (unsigned)pc : 0xFFFFFFF0u);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, g), rdb, vsb, (even && cb >= 0) ? (int)((unsigned)cb * plane_b) : 0, 0);
-        } else {
-            if (accumulate) g += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rda, vo, so, 0));
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, g), rda, vst, so, 0);
-        }
-    };
-    if (CPT > 0) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) one(j, va[j], vb[j]);
-    } else {
-#pragma unroll 4
-        for (int j = 0; j < nj; ++j) one(j, ld(ra, j), ld(rb, j));
-    }
-}
-
-// dz = dy where y > 0 else 0, channels [0, cs) to dz_a [n, cs, hw] and [cs, c) to dz_b [n, c - cs, hw] (Fire concat halves)
-__global__ __launch_bounds__(256) void relu_bwd_split_kernel(float* dz_a, float* dz_b, const float* dy, const float* y, int c, int cs,
-                                                             int64_t hw, int64_t total) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t p = i % hw, r = i / hw;
-        const int ch = (int)(r % c);
-        const int64_t nn = r / c;
-        const float v = y[i] > 0.f ? dy[i] : 0.f;
-        if (ch < cs) dz_a[(nn * cs + ch) * hw + p] = v;
-        else dz_b[(nn * (c - cs) + (ch - cs)) * hw + p] = v;
-    }
-}
-
-// MaxPool2d(3, 2, ceil_mode=True) backward: the gradient of a window goes to its FIRST maximum in row-major order (torch's argmax rule).
-// A workgroup owns a 32 x 32 tile of INPUT elements of one plane.  The 17 x 17 windows that touch it (one row / column of them
-// belongs to the neighbouring tile and is recomputed) read a 35 x 35 input patch from LDS; every window's argmax (as a patch offset)
-// and gradient are computed once, then each input element collects from the <= 4 windows that cover it.
-// Input tile owned by a workgroup: 64 columns x 32 rows (both even: windows start on even rows / columns), the (32/2 + 1) x (64/2 + 1)
-// windows that touch it, and their (32 + 3) x (64 + 3) input patch.  The kernel is bound by its instruction count, not by memory
-// (2.1 TB/s in its first form): no coordinates are divided, the patch is padded with -inf so the window scan needs no bounds tests,
-// and a lane scatters the windows' gradients to one 2 x 2 block of inputs (whose four window memberships are fixed by parity).
-constexpr int MPTX = 64, MPTY = 32, MPWX = MPTX / 2 + 1, MPWY = MPTY / 2 + 1, MPIX = MPTX + 3, MPIY = MPTY + 3, MPS = MPIX + 1;
-__global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(float* dx, const float* dy, const float* x, int ih, int iw, int oh, int ow,
-                                                               int tiles_x, int tiles_y) {
-    __shared__ float patch[MPIY * MPS];
-    __shared__ int16_t arg[MPWY][MPWX + 1];
-    __shared__ float gw[MPWY][MPWX + 1];
-    const int tid = threadIdx.x;
-    const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y;
-    const int64_t pl = blockIdx.x / ((int64_t)tiles_x * tiles_y);
-    const int iy0 = ty * MPTY, ix0 = tx * MPTX;          // first owned input row / column
-    const int py0 = iy0 - 2, px0 = ix0 - 2;              // patch origin: patch[2 wy + ky][2 wx + kx] is tap (ky, kx) of local window (wy, wx)
-    const int wy0 = iy0 / 2 - 1, wx0 = ix0 / 2 - 1;      // first window row / column (may be -1)
-    const float* xp = x + pl * ih * iw;
-    const float* dp = dy + pl * oh * ow;
-    const float NEG = -__builtin_inff();
-    {
-        const int cc = tid & 63, r0 = tid >> 6;
-        const int xx = px0 + cc;
-        const bool xin = xx >= 0 && xx < iw;
-#pragma unroll
-        for (int r = r0; r < MPIY; r += 4) {
-            const int yy = py0 + r;
-            patch[r * MPS + cc] = (xin && yy >= 0 && yy < ih) ? xp[(int64_t)yy * iw + xx] : NEG;
-        }
-        if (tid < 3 * MPIY) {                            // the three columns past the 64th
-            const int r = tid / 3, c3 = 64 + tid - 3 * r;
-            const int yy = py0 + r, x3 = px0 + c3;
-            patch[r * MPS + c3] = (x3 < iw && yy >= 0 && yy < ih) ? xp[(int64_t)yy * iw + x3] : NEG;
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < MPWY * MPWX; i += 256) {
-        const int wy = i / MPWX, wx = i - wy * MPWX;
-        const int oy = wy0 + wy, ox = wx0 + wx;
-        int best = -1;
-        float g = 0.f;
-        if (oy >= 0 && ox >= 0 && oy < oh && ox < ow) {  // tap (0, 0) of a window that exists is inside the input
-            const int base = 2 * wy * MPS + 2 * wx;
-            float bv = patch[base];
-            best = base;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    if (ky == 0 && kx == 0) continue;
-                    const float v = patch[base + ky * MPS + kx];
-                    if (v > bv) { bv = v; best = base + ky * MPS + kx; }       // first maximum in row-major order (torch)
-                }
-            g = dp[(int64_t)oy * ow + ox];
-        }
-        arg[wy][wx] = (int16_t)best;
-        gw[wy][wx] = g;
-    }
-    __syncthreads();
-    // input block (2 br, 2 bc) + {0,1}^2 of the tile: windows (br, bc) .. (br + 1, bc + 1) in local indices; element (0,0) is in
-    // all four, (0,1) in the right two, (1,0) in the lower two, (1,1) in the last -- summed in ascending window order like torch
-#pragma unroll
-    for (int i = tid; i < (MPTY / 2) * (MPTX / 2); i += 256) {
-        const int br = i / (MPTX / 2), bc = i - br * (MPTX / 2);
-        const int yy = iy0 + 2 * br, xx = ix0 + 2 * bc;
-        if (yy >= ih || xx >= iw) continue;
-        const int me = (2 * br + 2) * MPS + 2 * bc + 2;
-        const int a00 = arg[br][bc], a01 = arg[br][bc + 1], a10 = arg[br + 1][bc], a11 = arg[br + 1][bc + 1];
-        const float g00 = gw[br][bc], g01 = gw[br][bc + 1], g10 = gw[br + 1][bc], g11 = gw[br + 1][bc + 1];
-        float e00 = 0.f, e01 = 0.f, e10 = 0.f, e11 = 0.f;
-        if (a00 == me) e00 += g00;
-        if (a01 == me) e00 += g01;
-        if (a10 == me) e00 += g10;
-        if (a11 == me) e00 += g11;
-        if (a01 == me + 1) e01 += g01;
-        if (a11 == me + 1) e01 += g11;
-        if (a10 == me + MPS) e10 += g10;
-        if (a11 == me + MPS) e10 += g11;
-        if (a11 == me + MPS + 1) e11 += g11;
-        float* o = dx + pl * ih * iw + (int64_t)yy * iw + xx;
-        const bool x1 = xx + 1 < iw;
-        o[0] = e00;
-        if (x1) o[1] = e01;
-        if (yy + 1 < ih) {
-            o[iw] = e10;
-            if (x1) o[iw + 1] = e11;
-        }
-    }
-}
-
-// MaxPool2d(2, 2) backward (VGG): windows do not overlap, an input element belongs to at most one
-__global__ __launch_bounds__(256) void maxpool2x2s2_bwd_kernel(float* dx, const float* dy, const float* x, int ih, int iw, int oh, int ow,
-                                                               int64_t total) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int ix = (int)(i % iw);
-        const int64_t r = i / iw;
-        const int iy = (int)(r % ih);
-        const int64_t pl = r / ih;
-        const int oy = iy / 2, ox = ix / 2;
-        float g = 0.f;
-        if (oy < oh && ox < ow) {
-            const float* xp = x + pl * ih * iw + (int64_t)(2 * oy) * iw + 2 * ox;
-            const float v00 = xp[0], v01 = xp[1], v10 = xp[iw], v11 = xp[iw + 1];
-            int best = 0;
-            float bv = v00;
-            if (v01 > bv) { bv = v01; best = 1; }
-            if (v10 > bv) { bv = v10; best = 2; }
-            if (v11 > bv) { bv = v11; best = 3; }
-            if (best == (iy & 1) * 2 + (ix & 1)) g = dy[pl * oh * ow + (int64_t)oy * ow + ox];
-        }
-        dx[i] = g;
-    }
-}
-
-// dimg (+)= scale * 2 (a - b) / numel    (gradient of scale * mean((a - b)^2) per sample)
-__global__ __launch_bounds__(256) void mse_grad_kernel(float* d, const float* a, const float* b, int64_t numel, int64_t b_bs, float k,
-                                                       int accumulate, int64_t total) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t nn = i / numel, p = i % numel;
-        const float g = k * (a[i] - b[nn * b_bs + p]);
-        d[i] = accumulate ? d[i] + g : g;
-    }
-}
-
-// torch.optim.Adam (single tensor, amsgrad off, weight_decay optional as L2 like torch) on a small parameter, one workgroup;
-// the optimizer's own step count lives on the device (it only advances when a step is taken, like optimizer.step()).
-__global__ __launch_bounds__(256) void adam_step_kernel(float* param, float* m, float* v, int32_t* t_ctr, const float* grad, const float* lr_table,
-                                                        const int32_t* step, const int32_t* valid, int64_t numel, int steps_total, float beta1,
-                                                        float beta2, float eps, float weight_decay) {
-    const int s = *step;
-    if (s >= steps_total || (valid && valid[s] == 0)) return;               // past the end / "no face": `continue` before optimizer.step()
-    const int t = *t_ctr + 1;
-    __syncthreads();
-    const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
-    const float step_size = (float)((double)lr_table[s] / bc1);
-    const float bc2_sqrt = (float)sqrt(bc2);
-    for (int64_t i = threadIdx.x; i < numel; i += 256) {
-        float g = grad[i];
-        if (weight_decay != 0.f) g += weight_decay * param[i];
-        const float mi = m[i] + (g - m[i]) * (1.f - beta1);                 // exp_avg.lerp_(grad, 1 - beta1)
-        const float vi = v[i] * beta2 + (1.f - beta2) * g * g;
-        m[i] = mi;
-        v[i] = vi;
-        param[i] -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    }
-    if (threadIdx.x == 0) *t_ctr = t;
-}
-
 }  // namespace
+
+static bool al16(const void* q) { return q == nullptr || ((uintptr_t)q % 16) == 0; }
+
+// The argument checks the entries that invert the activation share (`name`: the entry's, for the message; vec: every map is on the 16-byte
+// path; residual / residual_low null where the entry takes none).  MGF_OK, or the code with the error set.
+static int act_bwd_check(const char* name, float alpha, float gain, int32_t n, int32_t c, const float* residual, const float* residual_low, bool vec,
+                         int32_t w, int64_t hw) {
+    MGF_REQUIRE(alpha != 0.f && gain != 0.f, MGF_EINVAL, "%s: alpha and gain must be non-zero (the activation is inverted)", name);
+    MGF_REQUIRE(n <= 65535 && c <= 65535, MGF_ETOOBIG, "%s: n and c must be <= 65535", name);
+    MGF_REQUIRE(!(residual && residual_low), MGF_EINVAL, "%s: the residual comes at full OR at half resolution", name);
+    MGF_REQUIRE(!residual_low || (vec && w >= 4 && w % 4 == 0 && hw % w == 0 && (hw / w) % 2 == 0 && hw / w <= INT32_MAX), MGF_EUNSUPPORTED,
+                "%s: the half-resolution residual needs 16-byte aligned maps with w %% 4 == 0 and an even height (w %d, hw %lld)", name, w, (long long)hw);
+    return MGF_OK;
+}
 
 extern "C" int32_t mgf_bwd_chunks(int64_t hw) { return (int32_t)mgf_cdiv(hw, BWD_CHUNK); }
 
@@ -1113,18 +854,12 @@ extern "C" int mgf_layer_act_bwd_low_f32(float* dz, float* dot_part, const float
                                          const float* noise_strength, int32_t noise_n, int32_t n, int32_t c, int64_t hw, float alpha, float gain,
                                          mgf_stream_t stream) {
     MGF_REQUIRE(dz && dy && y && n >= 1 && c >= 1 && hw >= 1, MGF_EINVAL, "layer_act_bwd: bad arguments");
-    MGF_REQUIRE(alpha != 0.f && gain != 0.f, MGF_EINVAL, "layer_act_bwd: alpha and gain must be non-zero (the activation is inverted)");
-    MGF_REQUIRE(n <= 65535 && c <= 65535, MGF_ETOOBIG, "layer_act_bwd: n and c must be <= 65535");
-    MGF_REQUIRE(!(residual && residual_low), MGF_EINVAL, "layer_act_bwd: the residual comes at full OR at half resolution");
-    ActBwdParams p{dz, dot_part, dy, y, residual, bias, noise, noise_strength, noise_n, c, (int)mgf_cdiv(hw, BWD_CHUNK), hw, alpha, gain,
-                   residual_low, w};
-    auto al16 = [](const void* q) { return q == nullptr || ((uintptr_t)q % 16) == 0; };
     const bool vec = hw % 4 == 0 && al16(dz) && al16(dy) && al16(y) && al16(residual) && al16(noise);
-    if (residual_low) {
-        MGF_REQUIRE(vec && w >= 4 && w % 4 == 0 && hw % w == 0 && (hw / w) % 2 == 0 && hw / w <= INT32_MAX, MGF_EUNSUPPORTED,
-                    "layer_act_bwd: the half-resolution residual needs 16-byte aligned maps with w %% 4 == 0 and an even height (w %d, hw %lld)", w, (long long)hw);
-        hipLaunchKernelGGL((act_bwd_kernel<true, true>), dim3(p.nchunk, c, n), dim3(256), 0, (hipStream_t)stream, p);
-    } else if (vec) hipLaunchKernelGGL((act_bwd_kernel<true>), dim3(p.nchunk, c, n), dim3(256), 0, (hipStream_t)stream, p);
+    if (const int rc = act_bwd_check("layer_act_bwd", alpha, gain, n, c, residual, residual_low, vec, w, hw)) return rc;
+    ActBwdParams p{dz, dot_part, dy, y, residual, {bias, noise, noise_strength, noise_n, alpha, gain}, c, (int)mgf_cdiv(hw, BWD_CHUNK), hw,
+                   residual_low, w};
+    if (residual_low) hipLaunchKernelGGL((act_bwd_kernel<true, true>), dim3(p.nchunk, c, n), dim3(256), 0, (hipStream_t)stream, p);
+    else if (vec) hipLaunchKernelGGL((act_bwd_kernel<true>), dim3(p.nchunk, c, n), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((act_bwd_kernel<false>), dim3(p.nchunk, c, n), dim3(256), 0, (hipStream_t)stream, p);
     MGF_CHECK_LAUNCH("layer_act_bwd");
     return MGF_OK;
@@ -1159,10 +894,10 @@ extern "C" int mgf_style_grad_f32(float* dot_part, float* dx, const float* x, co
 // after the other (d is rounded to float32 before it is used), at 3 tensor passes instead of 6.  Layer L must have no residual.
 struct StyleActParams {
     float* part_s; float* part_dc; float* dz; float* dx;
-    const float* x; const float* g; const float* s; const float* res; const float* bias; const float* noise; const float* nstr;
-    int noise_n, c, nchunk;
+    const float* x; const float* g; const float* s; const float* res;
+    ActSide act;
+    int c, nchunk;
     int64_t hw;
-    float alpha, gain;
     const float* res_low;   // LOW: the residual at half resolution (res is null), see ActBwdParams
     int w;
 };
@@ -1174,35 +909,24 @@ __global__ __launch_bounds__(256) void style_grad_act_bwd_kernel(StyleActParams 
     static_assert(!LOW || (VEC && RES), "the half-resolution residual rides on the 16-byte residual path");
     __shared__ float red[4];
     const int chunk = blockIdx.x, ch = blockIdx.y, n = blockIdx.z;
-    const int64_t base = ((int64_t)n * p.c + ch) * p.hw;
-    const int64_t i0 = (int64_t)chunk * BWD_CHUNK;
-    const int64_t i1 = min(p.hw, i0 + (int64_t)BWD_CHUNK);
+    const auto [base, i0, i1] = chunk_of(chunk, ch, n, p.c, p.hw);
     const float sv = p.s ? p.s[(int64_t)n * p.c + ch] : 1.f;
-    const float b = p.bias ? p.bias[ch] : 0.f;
-    const float ns = p.noise ? (p.nstr ? *p.nstr : 1.f) : 0.f;
-    const float* nz = p.noise ? p.noise + (int64_t)(p.noise_n > 1 ? n : 0) * p.hw : nullptr;
-    const float inv_gain = 1.f / p.gain, inv_alpha = 1.f / p.alpha;
+    const ActPlane act(p.act, n, ch, p.hw);
     float acc_s = 0.f, acc_c = 0.f;
     auto one = [&](float xv, float rv, float gv, float nv, float& dv, float& dzv) {
         dv = sv * gv;                                // (the value style_grad would have stored)
         const float v = RES ? xv - rv : xv;
-        const bool pos = v > 0.f;
-        dzv = dv * p.gain * (pos ? 1.f : p.alpha);
-        if (p.part_dc) {
-            const float zv = (pos ? v : v * inv_alpha) * inv_gain;
-            acc_c += dzv * (zv - b - nv * ns);
-        }
+        dzv = act.dz(dv, v);
+        if (p.part_dc) acc_c += dzv * act.c(v, nv);
     };
     if (VEC) {
         for (int64_t i = i0 + 4 * threadIdx.x; i < i1; i += 1024) {
             const float4 gv = *reinterpret_cast<const float4*>(p.g + base + i);
             const float4 xv = *reinterpret_cast<const float4*>(p.x + base + i);
-            const float4 nv = nz ? *reinterpret_cast<const float4*>(nz + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 nv = act.nz ? *reinterpret_cast<const float4*>(act.nz + i) : make_float4(0.f, 0.f, 0.f, 0.f);
             float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (LOW) {
-                const int yy = (int)(i / p.w);
-                rv = up2_residual4(p.res_low + ((int64_t)n * p.c + ch) * (p.hw >> 2), (int)(p.hw / p.w) >> 1, p.w >> 1, yy, (int)(i - (int64_t)yy * p.w));
-            } else if (RES) rv = *reinterpret_cast<const float4*>(p.res + base + i);
+            if (LOW) rv = residual_low4(p, n, ch, i);
+            else if (RES) rv = *reinterpret_cast<const float4*>(p.res + base + i);
             acc_s += xv.x * gv.x + xv.y * gv.y + xv.z * gv.z + xv.w * gv.w;       // (the association of style_grad_kernel: bit-identical partials)
             float4 o, d;
             one(xv.x, rv.x, gv.x, nv.x, d.x, o.x); one(xv.y, rv.y, gv.y, nv.y, d.y, o.y);
@@ -1215,17 +939,15 @@ __global__ __launch_bounds__(256) void style_grad_act_bwd_kernel(StyleActParams 
             float o, d;
             const float xs = p.x[base + i], gs = p.g[base + i];
             acc_s += xs * gs;
-            one(xs, RES ? p.res[base + i] : 0.f, gs, nz ? nz[i] : 0.f, d, o);
+            one(xs, RES ? p.res[base + i] : 0.f, gs, act.nz ? act.nz[i] : 0.f, d, o);
             p.dz[base + i] = o;
             if (RES) p.dx[base + i] = d;
         }
     }
-    const float ts = block_sum(acc_s, red);
-    if (threadIdx.x == 0) p.part_s[((int64_t)n * p.c + ch) * p.nchunk + chunk] = ts;
+    store_partial(p.part_s, acc_s, red, n, p.c, ch, p.nchunk, chunk);
     if (p.part_dc) {
         __syncthreads();
-        const float tc = block_sum(acc_c, red);
-        if (threadIdx.x == 0) p.part_dc[((int64_t)n * p.c + ch) * p.nchunk + chunk] = tc;
+        store_partial(p.part_dc, acc_c, red, n, p.c, ch, p.nchunk, chunk);
     }
 }
 }  // namespace
@@ -1235,19 +957,14 @@ extern "C" int mgf_style_grad_act_bwd_f32(float* style_part, float* dot_part, fl
                                           const float* noise, const float* noise_strength, int32_t noise_n, int32_t n, int32_t c, int64_t hw,
                                           float alpha, float gain, mgf_stream_t stream) {
     MGF_REQUIRE(style_part && dz && x && g && n >= 1 && c >= 1 && hw >= 1, MGF_EINVAL, "style_grad_act_bwd: bad arguments");
-    MGF_REQUIRE(!(residual && residual_low), MGF_EINVAL, "style_grad_act_bwd: the residual comes at full OR at half resolution");
     MGF_REQUIRE((dx != nullptr) == (residual != nullptr || residual_low != nullptr), MGF_EINVAL,
                 "style_grad_act_bwd: dx and a residual go together (both or neither)");
-    MGF_REQUIRE(alpha != 0.f && gain != 0.f, MGF_EINVAL, "style_grad_act_bwd: alpha and gain must be non-zero (the activation is inverted)");
-    MGF_REQUIRE(n <= 65535 && c <= 65535, MGF_ETOOBIG, "style_grad_act_bwd: n and c must be <= 65535");
-    StyleActParams p{style_part, dot_part, dz, dx, x, g, s, residual, bias, noise, noise_strength, noise_n, c, (int)mgf_cdiv(hw, BWD_CHUNK),
-                     hw, alpha, gain, residual_low, w};
-    auto al16 = [](const void* q) { return q == nullptr || ((uintptr_t)q % 16) == 0; };
     const bool vec = hw % 4 == 0 && al16(dz) && al16(x) && al16(g) && al16(noise) && al16(dx) && al16(residual);
+    if (const int rc = act_bwd_check("style_grad_act_bwd", alpha, gain, n, c, residual, residual_low, vec, w, hw)) return rc;
+    StyleActParams p{style_part, dot_part, dz, dx, x, g, s, residual, {bias, noise, noise_strength, noise_n, alpha, gain}, c,
+                     (int)mgf_cdiv(hw, BWD_CHUNK), hw, residual_low, w};
     const dim3 grid(p.nchunk, c, n);
     if (residual_low) {
-        MGF_REQUIRE(vec && w >= 4 && w % 4 == 0 && hw % w == 0 && (hw / w) % 2 == 0 && hw / w <= INT32_MAX, MGF_EUNSUPPORTED,
-                    "style_grad_act_bwd: the half-resolution residual needs 16-byte aligned maps with w %% 4 == 0 and an even height (w %d, hw %lld)", w, (long long)hw);
         hipLaunchKernelGGL((style_grad_act_bwd_kernel<true, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     } else if (residual) {
         if (vec) hipLaunchKernelGGL((style_grad_act_bwd_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
@@ -1268,9 +985,10 @@ extern "C" int mgf_style_grad_act_bwd_f32(float* style_part, float* dot_part, fl
 // csrc/upfirdn2d.hip's fir_up1_sep runs on it.  Traffic per element: 2 x 4 B x 1.18 in, 4 B out, against 12 B + 8.7 B for the two launches.
 struct StyleActFirParams {
     float* part_s; float* part_dc; float* dt;
-    const float* x; const float* g; const float* s; const float* bias; const float* noise; const float* nstr; const float* f;
-    int noise_n, n, c, h, w, flip, ntiles, tiles_x;
-    float alpha, gain, fir_gain;
+    const float* x; const float* g; const float* s; const float* f;
+    ActSide act;
+    int n, c, h, w, flip, ntiles, tiles_x;
+    float fir_gain;
 };
 namespace {
 __global__ __launch_bounds__(256) void style_act_fir_bwd_kernel(StyleActFirParams p) {
@@ -1291,10 +1009,7 @@ __global__ __launch_bounds__(256) void style_act_fir_bwd_kernel(StyleActFirParam
     const int64_t plane = (int64_t)p.h * p.w;
     const int64_t base = ((int64_t)n * p.c + ch) * plane;
     const float sv = p.s ? p.s[(int64_t)n * p.c + ch] : 1.f;
-    const float b = p.bias ? p.bias[ch] : 0.f;
-    const float ns = p.noise ? (p.nstr ? *p.nstr : 1.f) : 0.f;
-    const float* nz = p.noise ? p.noise + (int64_t)(p.noise_n > 1 ? n : 0) * plane : nullptr;
-    const float inv_gain = 1.f / p.gain, inv_alpha = 1.f / p.alpha;
+    const ActPlane act(p.act, n, ch, plane);
     float acc_s = 0.f, acc_c = 0.f;
     const int xa = ox0 - 4, iy0 = oy0 - 2;                          // pad 2: output (oy, ox) reads input rows oy - 2 .. oy + 1
     for (int i = tid; i < IH * WV; i += 256) {
@@ -1305,21 +1020,17 @@ __global__ __launch_bounds__(256) void style_act_fir_bwd_kernel(StyleActFirParam
             const int64_t off = (int64_t)iy * p.w + ix;
             const float4 gv = *reinterpret_cast<const float4*>(p.g + base + off);
             const float4 xv = *reinterpret_cast<const float4*>(p.x + base + off);
-            const float4 nv = nz ? *reinterpret_cast<const float4*>(nz + off) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 nv = act.nz ? *reinterpret_cast<const float4*>(act.nz + off) : make_float4(0.f, 0.f, 0.f, 0.f);
             const bool own = iy >= oy0 && iy < oy0 + T && ix >= ox0 && ix < ox0 + T;
             const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w}, nn[4] = {nv.x, nv.y, nv.z, nv.w};
             float dz[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float dv = sv * gs[e];                         // (what style_grad would have stored: rounded before it is used)
-                const bool pos = xs[e] > 0.f;
-                dz[e] = dv * p.gain * (pos ? 1.f : p.alpha);
+                dz[e] = act.dz(dv, xs[e]);
                 if (own) {
                     acc_s += xs[e] * gs[e];
-                    if (p.part_dc) {
-                        const float zv = (pos ? xs[e] : xs[e] * inv_alpha) * inv_gain;
-                        acc_c += dz[e] * (zv - b - nn[e] * ns);
-                    }
+                    if (p.part_dc) acc_c += dz[e] * act.c(xs[e], nn[e]);
                 }
             }
             o = make_float4(dz[0], dz[1], dz[2], dz[3]);
@@ -1361,12 +1072,10 @@ __global__ __launch_bounds__(256) void style_act_fir_bwd_kernel(StyleActFirParam
             if (oy0 + row < out_h) yb[(int64_t)(oy0 + row) * out_w] = so[row * RS + col];
         }
     }
-    const float ts = block_sum(acc_s, red);
-    if (tid == 0) p.part_s[((int64_t)n * p.c + ch) * p.ntiles + tile] = ts;
+    store_partial(p.part_s, acc_s, red, n, p.c, ch, p.ntiles, tile);
     if (p.part_dc) {
         __syncthreads();
-        const float tc = block_sum(acc_c, red);
-        if (tid == 0) p.part_dc[((int64_t)n * p.c + ch) * p.ntiles + tile] = tc;
+        store_partial(p.part_dc, acc_c, red, n, p.c, ch, p.ntiles, tile);
     }
 }
 }  // namespace
@@ -1378,12 +1087,11 @@ extern "C" int mgf_style_act_fir_bwd_f32(float* style_part, float* dot_part, flo
                                          int32_t flip, float fir_gain, int32_t n, int32_t c, int32_t h, int32_t w, float alpha, float gain,
                                          mgf_stream_t stream) {
     MGF_REQUIRE(style_part && dt && x && g && f && n >= 1 && c >= 1 && h >= 1 && w >= 4, MGF_EINVAL, "style_act_fir_bwd: bad arguments");
-    MGF_REQUIRE(alpha != 0.f && gain != 0.f, MGF_EINVAL, "style_act_fir_bwd: alpha and gain must be non-zero (the activation is inverted)");
-    MGF_REQUIRE(w % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)g % 16) == 0 && (!noise || ((uintptr_t)noise % 16) == 0), MGF_EUNSUPPORTED,
-                "style_act_fir_bwd: needs 16-byte aligned maps with w %% 4 == 0 (w = %d)", w);
-    MGF_REQUIRE(n <= 65535 && c <= 65535, MGF_ETOOBIG, "style_act_fir_bwd: n and c must be <= 65535");
-    StyleActFirParams p{style_part, dot_part, dt, x, g, s, bias, noise, noise_strength, f, noise_n, n, c, h, w, flip & 1,
-                        mgf_style_act_fir_tiles(h, w), (int)mgf_cdiv(w + 1, 64), alpha, gain, fir_gain};
+    const bool vec = w % 4 == 0 && al16(x) && al16(g) && al16(noise);
+    if (const int rc = act_bwd_check("style_act_fir_bwd", alpha, gain, n, c, nullptr, nullptr, vec, w, (int64_t)h * w)) return rc;
+    MGF_REQUIRE(vec, MGF_EUNSUPPORTED, "style_act_fir_bwd: needs 16-byte aligned maps with w %% 4 == 0 (w = %d)", w);
+    StyleActFirParams p{style_part, dot_part, dt, x, g, s, f, {bias, noise, noise_strength, noise_n, alpha, gain}, n, c, h, w, flip & 1,
+                        mgf_style_act_fir_tiles(h, w), (int)mgf_cdiv(w + 1, 64), fir_gain};
     hipLaunchKernelGGL(style_act_fir_bwd_kernel, dim3(p.ntiles, c, n), dim3(256), 0, (hipStream_t)stream, p);
     MGF_CHECK_LAUNCH("style_act_fir_bwd");
     return MGF_OK;
@@ -1517,206 +1225,5 @@ extern "C" int mgf_latent_grad_gather(float* dw, const float* dwg, int32_t n_sty
     hipLaunchKernelGGL(latent_grad_gather_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, dw, dwg, n_style_jobs, dyc, n_attn_jobs, k, wdim,
                        scale);
     MGF_CHECK_LAUNCH("latent_grad_gather");
-    return MGF_OK;
-}
-
-// Pixels per workgroup: 64 (256-byte row segments per channel) while that leaves >= 512 workgroups, else 32 while >= 256, else 16 -- the
-// 16-pixel form moves 64-byte segments and streams at half the rate (1.7 vs 3.4 TB/s at 8 x 256 x 127^2).  MGF_LPIPS_BWD_PXB pins one,
-// MGF_LPIPS_BWD_CACHE=0 turns the register-resident second sweep off (tuning).
-template <bool RELU>
-static void lpips_bwd_launch(float* oa, float* ob, const float* din, const float* f0, const float* f1u, const float* lin, int n, int c,
-                             int c_split, int64_t hw, int64_t f1_bs, float k, int accumulate, hipStream_t st, const float* stats = nullptr,
-                             const float* wmap = nullptr, int64_t w_bs = 0) {
-    static const int env_pxb = [] { const char* e = mgf_knob("MGF_LPIPS_BWD_PXB"); return e ? atoi(e) : 0; }();
-    int pxb = mgf_cdiv(hw, 64) * n >= 512 ? 64 : mgf_cdiv(hw, 32) * n >= 256 ? 32 : 16;
-    if (env_pxb == 16 || env_pxb == 32 || env_pxb == 64) pxb = env_pxb;
-    static const bool no_cache = [] { const char* e = mgf_knob("MGF_LPIPS_BWD_CACHE"); return e && e[0] == '0'; }();
-    const dim3 grid((unsigned)mgf_cdiv(hw, pxb), n);
-#define MGF_LPB_LAUNCH(PX, CP)                                                                                                                     \
-    do {                                                                                                                                           \
-        if (wmap)                                                                                                                                  \
-            hipLaunchKernelGGL((lpips_layer_bwd_kernel<PX, RELU, CP, true>), grid, dim3(256), 0, st, oa, ob, din, f0, f1u, lin, c, c_split, hw,    \
-                               f1_bs, k, accumulate, stats, wmap, w_bs);                                                                           \
-        else                                                                                                                                       \
-            hipLaunchKernelGGL((lpips_layer_bwd_kernel<PX, RELU, CP>), grid, dim3(256), 0, st, oa, ob, din, f0, f1u, lin, c, c_split, hw, f1_bs,   \
-                               k, accumulate, stats, nullptr, 0);                                                                                  \
-    } while (0)
-    if (pxb == 64) {
-        if (c <= 64 && !no_cache && !stats) MGF_LPB_LAUNCH(64, 16);
-        else MGF_LPB_LAUNCH(64, 0);
-    } else if (pxb == 32) {
-        if (c <= 128 && !no_cache && !stats) MGF_LPB_LAUNCH(32, 16);
-        else MGF_LPB_LAUNCH(32, 0);
-    } else MGF_LPB_LAUNCH(16, 0);
-#undef MGF_LPB_LAUNCH
-}
-
-extern "C" int mgf_lpips_layer_bwd_f32(float* df0, const float* f0, const float* f1_unit, const float* lin, int32_t n, int32_t c, int64_t hw,
-                                       int64_t f1_batch_stride, float scale, int32_t accumulate, mgf_stream_t stream) {
-    MGF_REQUIRE(df0 && f0 && f1_unit && lin && n >= 1 && c >= 1 && hw >= 1, MGF_EINVAL, "lpips_layer_bwd: bad arguments");
-    MGF_REQUIRE((int64_t)c * hw < (1LL << 30), MGF_ETOOBIG, "lpips_layer_bwd: one sample's tap must stay below 4 GiB (32-bit buffer offsets)");
-    MGF_REQUIRE(n <= 65535, MGF_ETOOBIG, "lpips_layer_bwd: n must be <= 65535");
-    const float kk = 2.f * scale / (float)hw;
-    lpips_bwd_launch<false>(df0, nullptr, nullptr, f0, f1_unit, lin, n, c, c, hw, f1_batch_stride, kk, accumulate, (hipStream_t)stream);
-    MGF_CHECK_LAUNCH("lpips_layer_bwd");
-    return MGF_OK;
-}
-
-extern "C" int mgf_lpips_layer_bwd_relu_f32(float* dz_a, float* dz_b, const float* dy, const float* f0, const float* f1_unit,
-                                            const float* lin, int32_t n, int32_t c, int32_t c_split, int64_t hw, int64_t f1_batch_stride,
-                                            float scale, mgf_stream_t stream) {
-    return mgf_lpips_layer_bwd_relu_stats_f32(dz_a, dz_b, dy, f0, f1_unit, lin, nullptr, n, c, c_split, hw, f1_batch_stride, scale, stream);
-}
-
-extern "C" int mgf_lpips_layer_bwd_relu_stats_f32(float* dz_a, float* dz_b, const float* dy, const float* f0, const float* f1_unit,
-                                                  const float* lin, const float* stats, int32_t n, int32_t c, int32_t c_split, int64_t hw,
-                                                  int64_t f1_batch_stride, float scale, mgf_stream_t stream) {
-    MGF_REQUIRE(dz_a && f0 && f1_unit && lin && n >= 1 && c >= 1 && hw >= 1, MGF_EINVAL, "lpips_layer_bwd_relu: bad arguments");
-    MGF_REQUIRE(c_split >= 1 && c_split <= c && (dz_b || c_split == c), MGF_EINVAL, "lpips_layer_bwd_relu: bad split %d of %d channels", c_split, c);
-    MGF_REQUIRE(n <= 65535, MGF_ETOOBIG, "lpips_layer_bwd_relu: n must be <= 65535");
-    MGF_REQUIRE((int64_t)c * hw < (1LL << 30), MGF_ETOOBIG, "lpips_layer_bwd_relu: one sample's tap must stay below 4 GiB (32-bit buffer offsets)");
-    const float kk = 2.f * scale / (float)hw;
-    lpips_bwd_launch<true>(dz_a, dz_b, dy, f0, f1_unit, lin, n, c, c_split, hw, f1_batch_stride, kk, 0, (hipStream_t)stream, stats);
-    MGF_CHECK_LAUNCH("lpips_layer_bwd_relu");
-    return MGF_OK;
-}
-
-/* The region-weighted forms: the factor 2 scale / hw becomes 2 scale omega[p] (wmap: normalised weights, w_batch_stride 0 = shared) */
-extern "C" int mgf_lpips_layer_bwd_weighted_f32(float* df0, const float* f0, const float* f1_unit, const float* lin, const float* wmap, int32_t n,
-                                                int32_t c, int64_t hw, int64_t f1_batch_stride, int64_t w_batch_stride, float scale,
-                                                int32_t accumulate, mgf_stream_t stream) {
-    MGF_REQUIRE(df0 && f0 && f1_unit && lin && wmap && n >= 1 && c >= 1 && hw >= 1 && w_batch_stride >= 0, MGF_EINVAL, "lpips_layer_bwd_weighted: bad arguments");
-    MGF_REQUIRE((int64_t)c * hw < (1LL << 30), MGF_ETOOBIG, "lpips_layer_bwd_weighted: one sample's tap must stay below 4 GiB (32-bit buffer offsets)");
-    MGF_REQUIRE(n <= 65535, MGF_ETOOBIG, "lpips_layer_bwd_weighted: n must be <= 65535");
-    lpips_bwd_launch<false>(df0, nullptr, nullptr, f0, f1_unit, lin, n, c, c, hw, f1_batch_stride, 2.f * scale, accumulate, (hipStream_t)stream, nullptr,
-                            wmap, w_batch_stride);
-    MGF_CHECK_LAUNCH("lpips_layer_bwd_weighted");
-    return MGF_OK;
-}
-
-extern "C" int mgf_lpips_layer_bwd_relu_stats_weighted_f32(float* dz_a, float* dz_b, const float* dy, const float* f0, const float* f1_unit,
-                                                           const float* lin, const float* stats, const float* wmap, int32_t n, int32_t c,
-                                                           int32_t c_split, int64_t hw, int64_t f1_batch_stride, int64_t w_batch_stride,
-                                                           float scale, mgf_stream_t stream) {
-    MGF_REQUIRE(dz_a && f0 && f1_unit && lin && wmap && n >= 1 && c >= 1 && hw >= 1 && w_batch_stride >= 0, MGF_EINVAL, "lpips_layer_bwd_relu_weighted: bad arguments");
-    MGF_REQUIRE(c_split >= 1 && c_split <= c && (dz_b || c_split == c), MGF_EINVAL, "lpips_layer_bwd_relu_weighted: bad split %d of %d channels", c_split, c);
-    MGF_REQUIRE(n <= 65535, MGF_ETOOBIG, "lpips_layer_bwd_relu_weighted: n must be <= 65535");
-    MGF_REQUIRE((int64_t)c * hw < (1LL << 30), MGF_ETOOBIG, "lpips_layer_bwd_relu_weighted: one sample's tap must stay below 4 GiB (32-bit buffer offsets)");
-    lpips_bwd_launch<true>(dz_a, dz_b, dy, f0, f1_unit, lin, n, c, c_split, hw, f1_batch_stride, 2.f * scale, 0, (hipStream_t)stream, stats, wmap,
-                           w_batch_stride);
-    MGF_CHECK_LAUNCH("lpips_layer_bwd_relu_weighted");
-    return MGF_OK;
-}
-
-extern "C" int mgf_relu_bwd_split_f32(float* dz_a, float* dz_b, const float* dy, const float* y, int32_t n, int32_t c, int32_t c_split,
-                                      int64_t hw, mgf_stream_t stream) {
-    MGF_REQUIRE(dz_a && dy && y && n >= 1 && c >= 1 && hw >= 1, MGF_EINVAL, "relu_bwd_split: bad arguments");
-    MGF_REQUIRE(c_split >= 1 && c_split <= c && (dz_b || c_split == c), MGF_EINVAL, "relu_bwd_split: bad split %d of %d channels", c_split, c);
-    const int64_t total = (int64_t)n * c * hw;
-    hipLaunchKernelGGL(relu_bwd_split_kernel, dim3(mgf_stream_grid(total, 256, 4)), dim3(256), 0, (hipStream_t)stream, dz_a, dz_b, dy, y, c,
-                       c_split, hw, total);
-    MGF_CHECK_LAUNCH("relu_bwd_split");
-    return MGF_OK;
-}
-
-namespace {
-// dx of the 3x3 / stride-2 ceil-mode pool from the forward's stored tap indices: one lane per 2 x 2 input block (2 bi, 2 bj) + {0,1}^2,
-// whose elements sit at fixed taps of the <= 4 windows around it -- (0,0): tap 8 of window (bi-1, bj-1), 6 of (bi-1, bj), 2 of
-// (bi, bj-1), 0 of (bi, bj); (0,1): 7 of (bi-1, bj), 1 of (bi, bj); (1,0): 5 of (bi, bj-1), 3 of (bi, bj); (1,1): 4 of (bi, bj) --
-// summed in ascending window order like torch.  No LDS, no input map: a stream of stores.
-__global__ __launch_bounds__(256) void maxpool3x3s2_bwd_idx_kernel(float* __restrict__ dx, const float* __restrict__ dy,
-                                                                   const uint8_t* __restrict__ idx, int ih, int iw, int oh, int ow) {
-    const int bj = blockIdx.x * 256 + threadIdx.x, bi = blockIdx.y;
-    const int64_t pl = blockIdx.z;
-    const int yy = 2 * bi, xx = 2 * bj;
-    if (xx >= iw) return;
-    const float* dp = dy + pl * oh * ow;
-    const uint8_t* ip = idx + pl * oh * ow;
-    float g[2][2];
-    int t[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int oy = bi - 1 + a, ox = bj - 1 + b;
-            const bool in = oy >= 0 && ox >= 0 && oy < oh && ox < ow;
-            g[a][b] = in ? dp[(int64_t)oy * ow + ox] : 0.f;
-            t[a][b] = in ? (int)ip[(int64_t)oy * ow + ox] : -1;
-        }
-    float e00 = 0.f, e01 = 0.f, e10 = 0.f, e11 = 0.f;
-    if (t[0][0] == 8) e00 += g[0][0];
-    if (t[0][1] == 6) e00 += g[0][1];
-    if (t[1][0] == 2) e00 += g[1][0];
-    if (t[1][1] == 0) e00 += g[1][1];
-    if (t[0][1] == 7) e01 += g[0][1];
-    if (t[1][1] == 1) e01 += g[1][1];
-    if (t[1][0] == 5) e10 += g[1][0];
-    if (t[1][1] == 3) e10 += g[1][1];
-    if (t[1][1] == 4) e11 += g[1][1];
-    float* o = dx + pl * ih * iw + (int64_t)yy * iw + xx;
-    const bool x1 = xx + 1 < iw;
-    o[0] = e00;
-    if (x1) o[1] = e01;
-    if (yy + 1 < ih) {
-        o[iw] = e10;
-        if (x1) o[iw + 1] = e11;
-    }
-}
-}  // namespace
-
-extern "C" int mgf_maxpool3x3s2_ceil_bwd_idx_f32(float* dx, const float* dy, const uint8_t* idx, int32_t nc, int32_t in_h, int32_t in_w,
-                                                 int32_t out_h, int32_t out_w, mgf_stream_t stream) {
-    MGF_REQUIRE(dx && dy && idx && nc >= 1 && in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1, MGF_EINVAL, "maxpool3x3s2_ceil_bwd_idx: bad arguments");
-    MGF_REQUIRE(2 * (out_h - 1) < in_h && 2 * (out_w - 1) < in_w, MGF_EINVAL, "maxpool3x3s2_ceil_bwd_idx: output extent does not match the input");
-    MGF_REQUIRE(nc <= 65535 && (in_h + 1) / 2 <= 65535, MGF_ETOOBIG, "maxpool3x3s2_ceil_bwd_idx: at most 65535 planes and 131070 rows");
-    const dim3 grid((unsigned)mgf_cdiv((in_w + 1) / 2, 256), (unsigned)((in_h + 1) / 2), nc);
-    hipLaunchKernelGGL(maxpool3x3s2_bwd_idx_kernel, grid, dim3(256), 0, (hipStream_t)stream, dx, dy, idx, in_h, in_w, out_h, out_w);
-    MGF_CHECK_LAUNCH("maxpool3x3s2_ceil_bwd_idx");
-    return MGF_OK;
-}
-
-extern "C" int mgf_maxpool3x3s2_ceil_bwd_f32(float* dx, const float* dy, const float* x, int32_t nc, int32_t in_h, int32_t in_w, int32_t out_h,
-                                             int32_t out_w, mgf_stream_t stream) {
-    MGF_REQUIRE(dx && dy && x && nc >= 1 && in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1, MGF_EINVAL, "maxpool3x3s2_ceil_bwd: bad arguments");
-    MGF_REQUIRE(2 * (out_h - 1) < in_h && 2 * (out_w - 1) < in_w, MGF_EINVAL, "maxpool3x3s2_ceil_bwd: output extent does not match the input");
-    const int tiles_x = (int)mgf_cdiv(in_w, MPTX), tiles_y = (int)mgf_cdiv(in_h, MPTY);
-    MGF_REQUIRE((int64_t)nc * tiles_x * tiles_y <= INT32_MAX, MGF_ETOOBIG, "maxpool3x3s2_ceil_bwd: too many tiles");
-    hipLaunchKernelGGL(maxpool3x3s2_bwd_kernel, dim3((unsigned)((int64_t)nc * tiles_x * tiles_y)), dim3(256), 0, (hipStream_t)stream, dx, dy, x,
-                       in_h, in_w, out_h, out_w, tiles_x, tiles_y);
-    MGF_CHECK_LAUNCH("maxpool3x3s2_ceil_bwd");
-    return MGF_OK;
-}
-
-extern "C" int mgf_mse_grad_f32(float* d, const float* a, const float* b, int32_t n, int64_t numel, int64_t b_batch_stride, float scale,
-                                int32_t accumulate, mgf_stream_t stream) {
-    MGF_REQUIRE(d && a && b && n >= 1 && numel >= 1, MGF_EINVAL, "mse_grad: bad arguments");
-    const int64_t total = (int64_t)n * numel;
-    hipLaunchKernelGGL(mse_grad_kernel, dim3(mgf_stream_grid(total, 256, 4)), dim3(256), 0, (hipStream_t)stream, d, a, b, numel, b_batch_stride,
-                       2.f * scale / (float)numel, accumulate, total);
-    MGF_CHECK_LAUNCH("mse_grad");
-    return MGF_OK;
-}
-
-extern "C" int mgf_adam_step_f32(float* param, float* exp_avg, float* exp_avg_sq, int32_t* adam_t, const float* grad, const float* lr_table,
-                                 const int32_t* step, const int32_t* valid, int64_t numel, int32_t steps_total, float beta1, float beta2,
-                                 float eps, float weight_decay, mgf_stream_t stream) {
-    MGF_REQUIRE(param && exp_avg && exp_avg_sq && adam_t && grad && lr_table && step, MGF_EINVAL, "adam_step: null pointer");
-    MGF_REQUIRE(numel >= 1 && steps_total >= 1, MGF_EINVAL, "adam_step: bad sizes");
-    MGF_REQUIRE(numel <= (1 << 20), MGF_EUNSUPPORTED, "adam_step: single-workgroup kernel for latent-sized parameters (numel <= 2^20)");
-    hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, param, exp_avg, exp_avg_sq, adam_t, grad, lr_table, step,
-                       valid, numel, steps_total, beta1, beta2, eps, weight_decay);
-    MGF_CHECK_LAUNCH("adam_step");
-    return MGF_OK;
-}
-
-extern "C" int mgf_maxpool_s2_floor_bwd_f32(float* dx, const float* dy, const float* x, int32_t nc, int32_t in_h, int32_t in_w, int32_t ksize,
-                                            mgf_stream_t stream) {
-    MGF_REQUIRE(dx && dy && x && nc >= 1 && (ksize == 2 || ksize == 3) && in_h >= ksize && in_w >= ksize, MGF_EINVAL, "maxpool_s2_floor_bwd: bad arguments");
-    const int out_h = (in_h - ksize) / 2 + 1, out_w = (in_w - ksize) / 2 + 1;
-    if (ksize == 3) return mgf_maxpool3x3s2_ceil_bwd_f32(dx, dy, x, nc, in_h, in_w, out_h, out_w, stream);      // same rule, fewer windows
-    const int64_t total = (int64_t)nc * in_h * in_w;
-    hipLaunchKernelGGL(maxpool2x2s2_bwd_kernel, dim3(mgf_stream_grid(total, 256, 2)), dim3(256), 0, (hipStream_t)stream, dx, dy, x, in_h, in_w,
-                       out_h, out_w, total);
-    MGF_CHECK_LAUNCH("maxpool_s2_floor_bwd");
     return MGF_OK;
 }

@@ -8,6 +8,7 @@ namespace {
 
 constexpr int RED_BLOCKS = 16384;     // scratch floats per sample
 
+// (not mgf_block_sum_256 of mgf_common.h: this one's second barrier comes AFTER the read -- sm is free on return, not on entry)
 __device__ __forceinline__ float block_sum_256(float v, float* sm) {
     v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;

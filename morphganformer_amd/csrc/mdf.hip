@@ -29,7 +29,7 @@ constexpr int MDF_MAX_C = 128;                    // discriminator width N
 constexpr int MDF_MAX_SLOTS = 27;                 // 9 discriminators x 3 taps
 typedef const float __attribute__((address_space(4)))* mdf_cfp;   // weights through the scalar cache: every lane reads the same value
 
-// fixed-order sum of one float64 per lane over the workgroup (256 lanes)
+// fixed-order sum of one float64 per lane over the workgroup (256 lanes); not mgf_block_sum_256 of mgf_common.h: a halving tree in LDS, another order
 __device__ __forceinline__ double mdf_block_sum(double v, double* red) {
     const int t = threadIdx.y * MDF_BX + threadIdx.x;
     red[t] = v;

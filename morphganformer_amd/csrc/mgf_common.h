@@ -70,6 +70,16 @@ __device__ __forceinline__ T wave_sum(T v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// Sum over the 256 threads of a workgroup in a fixed order (wave butterflies, then the four waves in index order) through four slots of
+// LDS; every thread gets the result.  The first barrier lets `sh` still be read from a previous call.
+template <typename T>
+__device__ __forceinline__ T mgf_block_sum_256(T v, T* sh) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
 template <typename T>
 __device__ __forceinline__ T wave_max(T v) {
 #pragma unroll

@@ -14,15 +14,6 @@ namespace {
 
 constexpr double PAIR_COS_EPS = 1e-8;
 
-// Sum over the 256 threads of a block in a fixed order; every thread gets the result.
-__device__ __forceinline__ double pair_block_sum(double v, double* sh) {
-    v = wave_sum(v);
-    __syncthreads();                    // (sh may still be read from the previous call)
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
 __global__ __launch_bounds__(256) void embed_pair_loss_kernel(float* __restrict__ loss, float* __restrict__ demb, double* __restrict__ trace,
                                                               const float* __restrict__ emb, const float* __restrict__ ta,
                                                               const float* __restrict__ tb, const float* __restrict__ alpha, int width,
@@ -49,8 +40,8 @@ __global__ __launch_bounds__(256) void embed_pair_loss_kernel(float* __restrict_
             v4 += q * q;
         }
     }
-    v0 = pair_block_sum(v0, sh);
-    v1 = pair_block_sum(v1, sh);
+    v0 = mgf_block_sum_256(v0, sh);
+    v1 = mgf_block_sum_256(v1, sh);
     double d_a, d_b;
     // d(d_t)/d e[i] = ce_t * e[i] + ct_t * t[i] + c0_t * (e[i] - t[i])
     double ce_a = 0.0, ct_a = 0.0, ce_b = 0.0, ct_b = 0.0, c0 = 0.0;
@@ -59,9 +50,9 @@ __global__ __launch_bounds__(256) void embed_pair_loss_kernel(float* __restrict_
         d_b = v1 / (double)width;
         c0 = 2.0 / (double)width;
     } else {
-        v2 = pair_block_sum(v2, sh);
-        v3 = pair_block_sum(v3, sh);
-        v4 = pair_block_sum(v4, sh);
+        v2 = mgf_block_sum_256(v2, sh);
+        v3 = mgf_block_sum_256(v3, sh);
+        v4 = mgf_block_sum_256(v4, sh);
         const double re = sqrt(v2);
         const double ne = fmax(re, PAIR_COS_EPS), na = fmax(sqrt(v3), PAIR_COS_EPS), nb = fmax(sqrt(v4), PAIR_COS_EPS);
         d_a = 1.0 - v0 / (ne * na);

@@ -2,9 +2,9 @@
 //   mgf_noise_grad_f32             dnoise[p] (+)= strength * sum_c dpre[c, p]                (the layer's pre-activation gradient, channel sum)
 //   mgf_noise_regularize(_grad)_f32  noise_regularize of the drivers (1024_example_wing_loss_perceptual_sqz_MSE.py:32-52) and its gradient
 //   mgf_noise_normalize_f32        noise_normalize_ (:55-60): x <- (x - mean) / std, std unbiased
-//   mgf_adam_elementwise_f32       mgf_adam_step_f32's arithmetic on any number of workgroups
-//   mgf_noise_sets_* / mgf_adam_sets_f32   the same four over SETS (one target's maps each; a map table that holds for every set) in a
+//   mgf_noise_sets_*               the same three over SETS (one target's maps each; a map table that holds for every set) in a
 //                                  launch count that depends on neither the number of sets nor of maps; the per-element bodies are shared
+// (The maps' Adam step, mgf_adam_elementwise_f32 / mgf_adam_sets_f32, lives with the latent's in adam.hip.)
 // float32 in and out, float64 accumulation, fixed summation order (block partials in caller scratch, folded by a fixed tree), no atomics.
 #include "mgf_common.h"
 
@@ -13,15 +13,6 @@
 namespace {
 
 constexpr int NO_PARTS = 256;          // at most this many block partials per reduction (one per thread of the block that folds them)
-
-// Sum over the 256 threads of a block in a fixed order (wave butterflies, then the four waves in index order); every thread gets the result.
-__device__ __forceinline__ double block_sum_256(double v, double* sh) {
-    v = wave_sum(v);
-    __syncthreads();                    // (sh may still be read from the previous call)
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
 
 // ---------------------------------------------------------------------------------------------- d noise
 // block = PQ pixel groups x S channel slices (PQ * S = 256); a thread sums its slice's channels in index order for V consecutive pixels,
@@ -131,8 +122,8 @@ __device__ __forceinline__ void reg_level_fwd_body(double* __restrict__ partials
         b += v00 * u0 + v01 * u1 + v10 * v00 + v11 * v01;
         if (next) next[i] = (v00 + v01 + v10 + v11) * 0.25;
     }
-    a = block_sum_256(a, sh);
-    b = block_sum_256(b, sh);
+    a = mgf_block_sum_256(a, sh);
+    b = mgf_block_sum_256(b, sh);
     if (threadIdx.x == 0) { partials[2 * blockIdx.x] = a; partials[2 * blockIdx.x + 1] = b; }
 }
 
@@ -155,8 +146,8 @@ __device__ __forceinline__ double reg_finish_level(double* __restrict__ stats, c
                                                    double* sh) {
     const double* p = partials + (int64_t)l * NO_PARTS * 2;
     const bool in = (int)threadIdx.x < nparts;
-    const double a = block_sum_256(in ? p[2 * threadIdx.x] : 0.0, sh);
-    const double b = block_sum_256(in ? p[2 * threadIdx.x + 1] : 0.0, sh);
+    const double a = mgf_block_sum_256(in ? p[2 * threadIdx.x] : 0.0, sh);
+    const double b = mgf_block_sum_256(in ? p[2 * threadIdx.x + 1] : 0.0, sh);
     const double n = (double)side * (double)side;
     const double A = a / n, B = b / n;
     if (threadIdx.x == 0) { stats[2 * l] = A; stats[2 * l + 1] = B; }
@@ -260,8 +251,8 @@ __device__ __forceinline__ void norm_partial_body(double* __restrict__ partials,
         s += v;
         q += v * v;
     }
-    s = block_sum_256(s, sh);
-    q = block_sum_256(q, sh);
+    s = mgf_block_sum_256(s, sh);
+    q = mgf_block_sum_256(q, sh);
     if (threadIdx.x == 0) { partials[2 * bx] = s; partials[2 * bx + 1] = q; }
 }
 
@@ -269,8 +260,8 @@ __device__ __forceinline__ void norm_partial_body(double* __restrict__ partials,
 __device__ __forceinline__ void norm_apply_body(float* __restrict__ x, const double* __restrict__ partials, int nparts, int64_t numel, int bx, int gx,
                                                 double* sh) {
     const bool in = (int)threadIdx.x < nparts;
-    const double s = block_sum_256(in ? partials[2 * threadIdx.x] : 0.0, sh);
-    const double q = block_sum_256(in ? partials[2 * threadIdx.x + 1] : 0.0, sh);
+    const double s = mgf_block_sum_256(in ? partials[2 * threadIdx.x] : 0.0, sh);
+    const double q = mgf_block_sum_256(in ? partials[2 * threadIdx.x + 1] : 0.0, sh);
     const double n = (double)numel;
     const double mean = s / n;
     const double var = (q - s * mean) / (n - 1.0);                            // unbiased, torch's default
@@ -289,57 +280,6 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(float* __restrict__ x, 
     __shared__ double sh[4];
     if (!step_is_live(step, valid, steps_total)) return;                     // (uniform over the grid)
     norm_apply_body(x, partials, nparts, numel, blockIdx.x, gridDim.x, sh);
-}
-
-// ---------------------------------------------------------------------------------------------- Adam
-// adam_step_kernel of backward.hip, expression for expression, over a grid; the step count is advanced by a launch of its own behind it
-// (no block may see the new count).
-__device__ __forceinline__ void adam_elementwise_body(float* param, float* m, float* v, const int32_t* t_ctr, const float* grad,
-                                                      const float* lr_table, const int32_t* step, const int32_t* valid, int64_t numel,
-                                                      int steps_total, float beta1, float beta2, float eps, float weight_decay) {
-    const int s = *step;
-    if (s >= steps_total || (valid && valid[s] == 0)) return;
-    const int t = *t_ctr + 1;
-    const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
-    const float step_size = (float)((double)lr_table[s] / bc1);
-    const float bc2_sqrt = (float)sqrt(bc2);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < numel; i += (int64_t)gridDim.x * 256) {
-        float g = grad[i];
-        if (weight_decay != 0.f) g += weight_decay * param[i];
-        const float mi = m[i] + (g - m[i]) * (1.f - beta1);                 // exp_avg.lerp_(grad, 1 - beta1)
-        const float vi = v[i] * beta2 + (1.f - beta2) * g * g;
-        m[i] = mi;
-        v[i] = vi;
-        param[i] -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    }
-}
-
-// Slice blockIdx.y of n_sets: its own optimizer count, step counter and `valid` row (one slice: n_sets = 1, strides 0).
-__global__ __launch_bounds__(256) void adam_sets_kernel(float* param, float* m, float* v, const int32_t* t_ctr, const float* grad, const float* lr_table,
-                                                        const int32_t* step, int64_t step_stride, const int32_t* valid, int64_t valid_stride,
-                                                        int64_t numel, int64_t set_stride, int steps_total, float beta1, float beta2, float eps,
-                                                        float weight_decay) {
-    const int64_t t = blockIdx.y, o = t * set_stride;
-    adam_elementwise_body(param + o, m + o, v + o, t_ctr + t, grad + o, lr_table, step + t * step_stride, valid ? valid + t * valid_stride : nullptr,
-                          numel, steps_total, beta1, beta2, eps, weight_decay);
-}
-
-__global__ void adam_sets_advance_kernel(int32_t* t_ctr, const int32_t* step, int64_t step_stride, const int32_t* valid, int64_t valid_stride,
-                                         int n_sets, int steps_total) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_sets) return;
-    const int s = step[t * step_stride];
-    if (s >= steps_total || (valid && valid[t * valid_stride + s] == 0)) return;
-    t_ctr[t] = t_ctr[t] + 1;
-}
-
-void launch_adam_sets(float* param, float* m, float* v, int32_t* t_ctr, const float* grad, const float* lr_table, const int32_t* step,
-                      int64_t step_stride, const int32_t* valid, int64_t valid_stride, int64_t numel, int n_sets, int64_t set_stride, int steps_total,
-                      float beta1, float beta2, float eps, float weight_decay, hipStream_t st) {
-    hipLaunchKernelGGL(adam_sets_kernel, dim3(mgf_stream_grid(numel, 256, 4), n_sets), dim3(256), 0, st, param, m, v, (const int32_t*)t_ctr, grad,
-                       lr_table, step, step_stride, valid, valid_stride, numel, set_stride, steps_total, beta1, beta2, eps, weight_decay);
-    hipLaunchKernelGGL(adam_sets_advance_kernel, dim3((n_sets + 255) / 256), dim3(256), 0, st, t_ctr, step, step_stride, valid, valid_stride, n_sets,
-                       steps_total);
 }
 
 // ---------------------------------------------------------------------------------------------- sets
@@ -623,17 +563,6 @@ extern "C" int mgf_noise_normalize_f32(float* x, int64_t numel, const int32_t* s
     return MGF_OK;
 }
 
-extern "C" int mgf_adam_elementwise_f32(float* param, float* exp_avg, float* exp_avg_sq, int32_t* adam_t, const float* grad, const float* lr_table,
-                                        const int32_t* step, const int32_t* valid, int64_t numel, int32_t steps_total, float beta1, float beta2,
-                                        float eps, float weight_decay, mgf_stream_t stream) {
-    MGF_REQUIRE(param && exp_avg && exp_avg_sq && adam_t && grad && lr_table && step, MGF_EINVAL, "adam_elementwise: null pointer");
-    MGF_REQUIRE(numel >= 1 && steps_total >= 1, MGF_EINVAL, "adam_elementwise: bad sizes");
-    launch_adam_sets(param, exp_avg, exp_avg_sq, adam_t, grad, lr_table, step, 0, valid, 0, numel, 1, numel, steps_total, beta1, beta2, eps,
-                     weight_decay, (hipStream_t)stream);
-    MGF_CHECK_LAUNCH("adam_elementwise");
-    return MGF_OK;
-}
-
 // ---------------------------------------------------------------------------------------------- sets: entries
 extern "C" int64_t mgf_noise_sets_scratch_bytes(const int32_t* sides, int32_t n_maps, int32_t n_sets) {
     if (!sides || n_maps < 1 || n_maps > SETS_MAX_MAPS || n_sets < 1) return 0;
@@ -716,21 +645,6 @@ extern "C" int mgf_noise_sets_grad_f32(float* dnoise, int64_t dnoise_stride, con
     const bool vec = hw % 4 == 0 && dnoise_stride % 4 == 0 && ((uintptr_t)dpre % 16) == 0 && ((uintptr_t)dnoise % 16) == 0;
     choose_noise_grad(vec, dnoise, dpre, strength, c, hw, accumulate, (hipStream_t)stream, n, dnoise_stride);
     MGF_CHECK_LAUNCH("noise_sets_grad");
-    return MGF_OK;
-}
-
-extern "C" int mgf_adam_sets_f32(float* param, float* exp_avg, float* exp_avg_sq, int32_t* adam_t, const float* grad, const float* lr_table,
-                                 const int32_t* step, int64_t step_stride, const int32_t* valid, int64_t valid_stride, int64_t numel, int32_t n_sets,
-                                 int64_t set_stride, int32_t steps_total, float beta1, float beta2, float eps, float weight_decay,
-                                 mgf_stream_t stream) {
-    MGF_REQUIRE(param && exp_avg && exp_avg_sq && adam_t && grad && lr_table && step, MGF_EINVAL, "adam_sets: null pointer");
-    MGF_REQUIRE(numel >= 1 && steps_total >= 1, MGF_EINVAL, "adam_sets: bad sizes");
-    MGF_REQUIRE(n_sets >= 1 && n_sets <= 65535, MGF_EINVAL, "adam_sets: n_sets must lie in 1..65535 (got %d)", n_sets);
-    MGF_REQUIRE(set_stride >= numel, MGF_EINVAL, "adam_sets: set_stride %lld is smaller than a slice (%lld)", (long long)set_stride, (long long)numel);
-    MGF_REQUIRE(step_stride >= 0 && valid_stride >= 0, MGF_EINVAL, "adam_sets: negative stride");
-    launch_adam_sets(param, exp_avg, exp_avg_sq, adam_t, grad, lr_table, step, step_stride, valid, valid_stride, numel, n_sets, set_stride,
-                     steps_total, beta1, beta2, eps, weight_decay, (hipStream_t)stream);
-    MGF_CHECK_LAUNCH("adam_sets");
     return MGF_OK;
 }
 

@@ -243,23 +243,27 @@ class GeneratorGrad:
         else:
             raise _lib.MgfError(f"GeneratorGrad: dnoises[{lp.name!r}] must hold one {h}x{w} map, or one per sample (got {tuple(out.shape)})")
 
+    def _act_side(self, lp):
+        """The activation side of layer `lp` as the kernels that invert it take it: ((bias, noise, noise_strength, noise_n), (alpha, gain)),
+        the pointer group in the C argument order, and the layer's <dz, c> partial buffer -- None unless the layer is demodulated and has
+        no attention (with attention the partials come from dc, behind the attention's backward)."""
+        noise, noise_n = self.G._noise_for(lp, *self.G.last_noise)
+        # conv_last carries neither noise nor bias/activation (engine.synthesis): alpha = gain = 1 makes the kernels a plain copy + dot
+        slope = (0.2, lp.act_gain) if lp.bias is not None else (1.0, 1.0)
+        dot = self.dc_part[lp.name].data_ptr() if lp.demod and lp.attn is None else None
+        return (_lib.ptr(lp.bias), _lib.ptr(noise), _lib.ptr(lp.noise_strength) if noise is not None else None, noise_n), slope, dot
+
     def _act_bwd(self, lp, dy, y_out, residual, residual_low=None):
         """d(pre-activation) of one SynthesisLayer from the gradient dy of its output y_out = lrelu(c [attention] + noise + bias) * gain
         + residual (and, for a demodulated layer without attention, the <dz, c> partials of the demodulation gradient)."""
-        G, L, st = self.G, _lib.lib(), _lib.stream_ptr()
         n, c, h, w = y_out.shape
-        mode, noises = G.last_noise
-        noise, noise_n = G._noise_for(lp, mode, noises)
+        act, slope, dot = self._act_side(lp)
         dz = self.buf("dz", y_out.shape)
-        want_dot = lp.demod and lp.attn is None
-        # conv_last carries neither noise nor bias/activation (engine.synthesis): alpha = gain = 1 makes the kernel a plain copy + dot
-        alpha, gain = (0.2, lp.act_gain) if lp.bias is not None else (1.0, 1.0)
         # residual_low: the skip branch at HALF resolution, as the forward's Winograd epilogue consumed it (engine fuse_skip_up): it is
         # up-sampled inside the kernel and the full-resolution skip tensor exists in neither pass
-        _lib.check(L.mgf_layer_act_bwd_low_f32(dz.data_ptr(), self.dc_part[lp.name].data_ptr() if want_dot else None, dy.data_ptr(),
-                                               y_out.data_ptr(), _lib.ptr(residual), _lib.ptr(residual_low), w, _lib.ptr(lp.bias),
-                                               _lib.ptr(noise), _lib.ptr(lp.noise_strength) if noise is not None else None, noise_n, n, c,
-                                               h * w, alpha, gain, st), "layer_act_bwd")
+        _lib.check(_lib.lib().mgf_layer_act_bwd_low_f32(dz.data_ptr(), dot, dy.data_ptr(), y_out.data_ptr(), _lib.ptr(residual),
+                                                        _lib.ptr(residual_low), w, *act, n, c, h * w, *slope, _lib.stream_ptr()),
+                   "layer_act_bwd")
         self._noise_grad(lp, dz)
         return dz
 
@@ -273,30 +277,29 @@ class GeneratorGrad:
         if dT is not None:
             return cv.conv_forward(dT, self.T[lp.name], stride=2, pad=(0, 0), in_scale=G._d(lp) if lp.demod else None, out=self.buf("g", x_in.shape))
         dc = dz
-        if lp.attn is not None and self.attn_defer is not None and self.debug is None:
+        if lp.attn is not None:
+            a = lp.attn
+            T = G.cfg.k - 1
             # deferred form: this layer's dc / dg / probabilities stay in buffers of their own; the value gradient and the demodulation
             # dot products of ALL attention layers are two launches at the end of the pass (_deferred_attention_launch)
-            a = lp.attn
-            T = G.cfg.k - 1
-            b = self.attn_defer["bufs"][lp.name]
-            dc = b["dc"]
-            _lib.check(L.mgf_duplex_attention_bwd(dc.data_ptr(), b["dg"].data_ptr(), b["probs"].data_ptr(), dz.data_ptr(), c_pre.data_ptr(),
-                                                  a.wqc.data_ptr(), a.spos.data_ptr(), G._v(lp).data_ptr(), n, a.c, a.f, T, st),
-                       "duplex_attention_bwd")
-            self.attn_defer["cpre"][b["dg"].data_ptr()] = c_pre.data_ptr()
-        elif lp.attn is not None:
-            a = lp.attn
-            T = G.cfg.k - 1
-            dc, dg, probs = self.buf("dc", y_out.shape), self.buf("dg", y_out.shape), self.buf("probs", (n, a.f, T))
+            defer = self.attn_defer is not None and self.debug is None
+            if defer:
+                b = self.attn_defer["bufs"][lp.name]
+                dc, dg, probs = b["dc"], b["dg"], b["probs"]
+            else:
+                dc, dg, probs = self.buf("dc", y_out.shape), self.buf("dg", y_out.shape), self.buf("probs", (n, a.f, T))
             _lib.check(L.mgf_duplex_attention_bwd(dc.data_ptr(), dg.data_ptr(), probs.data_ptr(), dz.data_ptr(), c_pre.data_ptr(),
                                                   a.wqc.data_ptr(), a.spos.data_ptr(), G._v(lp).data_ptr(), n, a.c, a.f, T, st),
                        "duplex_attention_bwd")
-            ws = self.avg_ws
-            _lib.check(L.mgf_attn_values_grad_ws(self.dvwb[lp.name].data_ptr(), dg.data_ptr(), probs.data_ptr(), n, a.c, a.f, T,
-                                                 ws.data_ptr(), ws.numel(), st), "attn_values_grad")
-            if lp.demod:
-                _lib.check(L.mgf_channel_dot_f32(self.dc_part[lp.name].data_ptr(), dc.data_ptr(), c_pre.data_ptr(), n, c, hw, st),
-                           "channel_dot")
+            if defer:
+                self.attn_defer["cpre"][dg.data_ptr()] = c_pre.data_ptr()
+            else:
+                ws = self.avg_ws
+                _lib.check(L.mgf_attn_values_grad_ws(self.dvwb[lp.name].data_ptr(), dg.data_ptr(), probs.data_ptr(), n, a.c, a.f, T,
+                                                     ws.data_ptr(), ws.numel(), st), "attn_values_grad")
+                if lp.demod:
+                    _lib.check(L.mgf_channel_dot_f32(self.dc_part[lp.name].data_ptr(), dc.data_ptr(), c_pre.data_ptr(), n, c, hw, st),
+                               "channel_dot")
         if self.debug is not None:
             self.debug[lp.name + ":dc"] = dc.clone()
         d = G._d(lp) if lp.demod else None
@@ -321,36 +324,36 @@ class GeneratorGrad:
         (mgf_style_grad_act_bwd_f32).  conv1 -> conv0 of a block: prev has no residual and the intermediate s * g never reaches memory.
         conv_last -> conv1 of the last block: prev's residual is the block's skip tensor and s * g is stored too (dx_role: the skip
         branch's backward reads it).  Returns dz, or (dz, dx) with a residual."""
-        G, L, st = self.G, _lib.lib(), _lib.stream_ptr()
+        G, L = self.G, _lib.lib()
         n, c, h, w = y_prev.shape
-        mode, noises = G.last_noise
-        noise, noise_n = G._noise_for(prev, mode, noises)
+        act, slope, dot = self._act_side(prev)
         dz = self.buf("dz", y_prev.shape)
-        want_dot = prev.demod and prev.attn is None
-        alpha, gain = (0.2, prev.act_gain) if prev.bias is not None else (1.0, 1.0)
         with_res = residual is not None or residual_low is not None
         dx = self.buf(dx_role, y_prev.shape) if with_res else None
-        _lib.check(L.mgf_style_grad_act_bwd_f32(self.ds_part[lp.name].data_ptr(), self.dc_part[prev.name].data_ptr() if want_dot else None,
-                                                dz.data_ptr(), _lib.ptr(dx), y_prev.data_ptr(), g.data_ptr(), G._s(lp).data_ptr(),
-                                                _lib.ptr(residual), _lib.ptr(residual_low), w, _lib.ptr(prev.bias), _lib.ptr(noise),
-                                                _lib.ptr(prev.noise_strength) if noise is not None else None, noise_n,
-                                                n, c, h * w, alpha, gain, st), "style_grad_act_bwd")
+        _lib.check(L.mgf_style_grad_act_bwd_f32(self.ds_part[lp.name].data_ptr(), dot, dz.data_ptr(), _lib.ptr(dx), y_prev.data_ptr(),
+                                                g.data_ptr(), G._s(lp).data_ptr(), _lib.ptr(residual), _lib.ptr(residual_low), w, *act,
+                                                n, c, h * w, *slope, _lib.stream_ptr()), "style_grad_act_bwd")
         self._noise_grad(prev, dz)
         return (dz, dx) if with_res else dz
 
     def _style_act_fir_bwd(self, lp, g, prev, y_prev):
         """_style_act_bwd of (lp, prev) followed by the adjoint of prev's blur, in one pass (mgf_style_act_fir_bwd_f32): returns
         dT [n, c, h + 1, w + 1], the map prev's stride-2 data-gradient convolution reads."""
-        G, L, st = self.G, _lib.lib(), _lib.stream_ptr()
+        G, L = self.G, _lib.lib()
         n, c, h, w = y_prev.shape
-        mode, noises = G.last_noise
-        noise, noise_n = G._noise_for(prev, mode, noises)
+        act, slope, dot = self._act_side(prev)
         dT = self.buf("dT", (n, c, h + 1, w + 1))
-        _lib.check(L.mgf_style_act_fir_bwd_f32(self.ds_part[lp.name].data_ptr(), self.dc_part[prev.name].data_ptr() if prev.demod else None,
-                                               dT.data_ptr(), y_prev.data_ptr(), g.data_ptr(), G._s(lp).data_ptr(), _lib.ptr(prev.bias),
-                                               _lib.ptr(noise), _lib.ptr(prev.noise_strength) if noise is not None else None, noise_n,
-                                               G.plan.fir.data_ptr(), 1, 4.0, n, c, h, w, 0.2, prev.act_gain, st), "style_act_fir_bwd")
+        _lib.check(L.mgf_style_act_fir_bwd_f32(self.ds_part[lp.name].data_ptr(), dot, dT.data_ptr(), y_prev.data_ptr(), g.data_ptr(),
+                                               G._s(lp).data_ptr(), *act, G.plan.fir.data_ptr(), 1, 4.0, n, c, h, w, *slope,
+                                               _lib.stream_ptr()), "style_act_fir_bwd")
         return dT
+
+    def _skip_bwd(self, res, d_out, out, epilogue=None):
+        """The resnet skip branch of block `res`: y = upfirdn(conv1x1(x), up=2, pad (2,1,2,1), gain 4)  ->  out = conv1x1^T(upfirdn(d_out,
+        down=2, pad (1,1,1,1))) [then the epilogue: the in-line path adds the main chain's d(x) that `out` already holds]."""
+        dlow = self.buf("dlow", self.G.bufs[res]["skip_low"].shape)
+        cv.upfirdn_into(dlow, d_out, self.G.plan.fir, up=1, down=2, pad=(1, 1, 1, 1), gain=4.0, flip=True)
+        cv.conv_forward(dlow, self.Tskip[res], epilogue=epilogue, out=out)
 
     def _layer_bwd(self, lp, dy, y_out, c_pre, residual, x_in, dx_role):
         """One SynthesisLayer.  dy: gradient wrt the layer output y_out (= lrelu(c [attention] + noise + bias) * gain + residual);
@@ -431,10 +434,7 @@ class GeneratorGrad:
             else:
                 dx = self._style_bwd(ll, gl, out_of(R), "dxin")
         else:
-            dh = self.buf("dh", h.shape)
-            _lib.check(L.mgf_style_grad_f32(self.ds_part[lt.name].data_ptr(), dh.data_ptr(), h.data_ptr(), g.data_ptr(),
-                                            G._s(lt).data_ptr(), n, h.shape[1], h.shape[2] * h.shape[3], 0, st), "style_grad(torgb)")
-            dx = self._layer_bwd(ll, dh, h, None, None, out_of(R), "dxin")
+            dx = self._layer_bwd(ll, self._style_bwd(lt, g, h, "dh"), h, None, None, out_of(R), "dxin")
         for res in reversed(cfg.block_resolutions):
             B = G.bufs[res]
             att = cfg.has_attention(res)
@@ -456,9 +456,7 @@ class GeneratorGrad:
                 main = torch.cuda.current_stream(G.device)
                 G.side.wait_stream(main)
                 with torch.cuda.stream(G.side):
-                    dlow = self.buf("dlow", B["skip_low"].shape)
-                    cv.upfirdn_into(dlow, d_out, P.fir, up=1, down=2, pad=(1, 1, 1, 1), gain=4.0, flip=True)
-                    cv.conv_forward(dlow, self.Tskip[res], out=self.buf("dxin", x_prev.shape))
+                    self._skip_bwd(res, d_out, self.buf("dxin", x_prev.shape))
             # conv1 then conv0: conv1's input IS conv0's output y0, so conv1's style gradient and conv0's activation backward are one
             # pass over (y0, g) -- d(y0) = s g is never stored (MGF_FUSE_STYLE_ACT=0: the two kernels in sequence, bit-identical)
             if res == R and dz1_top is not None:
@@ -485,10 +483,7 @@ class GeneratorGrad:
                 dxin = self._style_bwd(l0, g0, x_prev, "dxin", accumulate=True)
             else:
                 dxin = self._style_bwd(l0, g0, x_prev, "dxin")
-                # skip branch: y = upfirdn(conv1x1(x), up=2, pad (2,1,2,1), gain 4)  ->  conv1x1^T(upfirdn(dy, down=2, pad (1,1,1,1)))
-                dlow = self.buf("dlow", B["skip_low"].shape)
-                cv.upfirdn_into(dlow, d_out, P.fir, up=1, down=2, pad=(1, 1, 1, 1), gain=4.0, flip=True)
-                cv.conv_forward(dlow, self.Tskip[res], epilogue=_lib.make_epilogue(residual=dxin), out=dxin)
+                self._skip_bwd(res, d_out, dxin, epilogue=_lib.make_epilogue(residual=dxin))
             dx = dxin
         if self.attn_defer is not None and self.debug is None:
             self._deferred_attention_launch()

@@ -210,6 +210,50 @@ def test_activation_backward_with_the_residual_at_half_resolution(h, w):
                                        n, c, hw, 0.2, 1.3, st) != 0
 
 
+@pytest.mark.parametrize("with_dot", [True, False])
+@pytest.mark.parametrize("per_sample_noise", [False, True])
+@pytest.mark.parametrize("h,w", [(8, 8), (64, 64), (70, 136)])
+def test_style_act_fir_bwd_is_the_fused_pair_followed_by_the_blur_gradient(h, w, per_sample_noise, with_dot):
+    """mgf_style_act_fir_bwd_f32 on its own against the two launches it replaces: mgf_style_grad_act_bwd_f32 (no residual) for dz, then the
+    blur's adjoint upfirdn2d(pad 2, gain 4, flipped).  One tile much smaller than 64 x 64; a 65 x 65 output (four tiles, three of them
+    slivers: the "owned element" rule at both tile edges); a 2 x 3 tile grid with ragged edges.  dT to 1e-5 of its largest element (the
+    gate of the whole-generator test of this pair below); the dot-product partials are per 64 x 64 tile here and per 4096-element chunk
+    there, so their sums agree to the dot-product tolerance 1e-5.  Both paths test x > 0 on the same stored x: no element is undecided."""
+    from morphganformer_amd import _lib, conv as cv
+    from morphganformer_amd.synth_weights import fir_kernel_1331
+    L = _lib.lib()
+    torch.manual_seed(h * w)
+    n, c, hw = 2, 3, h * w
+    x = torch.randn(n, c, h, w, device="cuda")                     # conv0's output = conv1's input
+    g = torch.randn(n, c, h, w, device="cuda")
+    s = torch.rand(n, c, device="cuda") + 0.5
+    noise_n = n if per_sample_noise else 1
+    bias, noise, nstr = torch.randn(c, device="cuda"), torch.randn(noise_n, hw, device="cuda"), torch.tensor([0.3], device="cuda")
+    fir = torch.as_tensor(np.ascontiguousarray(np.asarray(fir_kernel_1331(), dtype=np.float64), dtype=np.float32), device="cuda")
+    st = _lib.stream_ptr()
+    chunks, tiles = int(L.mgf_bwd_chunks(hw)), int(L.mgf_style_act_fir_tiles(h, w))
+    assert tiles == -(-(h + 1) // 64) * -(-(w + 1) // 64)
+    ps_a, pd_a = torch.empty(n, c, chunks, device="cuda"), torch.empty(n, c, chunks, device="cuda")
+    dz, dT_a = torch.empty_like(x), torch.empty(n, c, h + 1, w + 1, device="cuda")
+    _lib.check(L.mgf_style_grad_act_bwd_f32(ps_a.data_ptr(), pd_a.data_ptr() if with_dot else None, dz.data_ptr(), None, x.data_ptr(),
+                                            g.data_ptr(), s.data_ptr(), None, None, 0, bias.data_ptr(), noise.data_ptr(), nstr.data_ptr(),
+                                            noise_n, n, c, hw, 0.2, 1.3, st))
+    cv.upfirdn_into(dT_a, dz, fir, up=1, pad=(2, 2, 2, 2), gain=4.0, flip=True, separable=True)
+    ps_b, pd_b = torch.empty(n, c, tiles, device="cuda"), torch.empty(n, c, tiles, device="cuda")
+    dT_b = torch.full_like(dT_a, float("nan"))
+    args = (ps_b.data_ptr(), pd_b.data_ptr() if with_dot else None, dT_b.data_ptr(), x.data_ptr(), g.data_ptr(), s.data_ptr(), bias.data_ptr(),
+            noise.data_ptr(), nstr.data_ptr(), noise_n, fir.data_ptr(), 1, 4.0, n, c)
+    _lib.check(L.mgf_style_act_fir_bwd_f32(*args, h, w, 0.2, 1.3, st))
+    err, top = float((dT_a - dT_b).abs().max()), float(dT_a.abs().max())
+    print(f"dT: max|A - B| {err:.3e}, max|A| {top:.3e}; style sums {rel(ps_b.sum(-1), ps_a.sum(-1)):.3e}"
+          + (f"; <dz, c> sums {rel(pd_b.sum(-1), pd_a.sum(-1)):.3e}" if with_dot else ""))
+    assert err <= 1e-5 * top
+    assert rel(ps_b.sum(-1), ps_a.sum(-1)) < 1e-5
+    if with_dot:
+        assert rel(pd_b.sum(-1), pd_a.sum(-1)) < 1e-5
+    assert L.mgf_style_act_fir_bwd_f32(*args, 8, 6, 0.2, 1.3, st) != 0          # rows that are no whole float4s
+
+
 @pytest.mark.parametrize("c,res", [(32, 8), (512, 4), (20, 6), (256, 32), (64, 16), (512, 8), (256, 8)])
 def test_duplex_attention_bwd_matches_autograd(c, res):
     from morphganformer_amd import _lib

@@ -1,4 +1,4 @@
-"""Per-target noise maps for lockstep targets: the set entries of csrc/noise_opt.hip (mgf_noise_sets_*, mgf_adam_sets_f32) on their own,
+"""Per-target noise maps for lockstep targets: the set entries of csrc/noise_opt.hip and csrc/adam.hip (mgf_noise_sets_*, mgf_adam_sets_f32) on their own,
 then GradientProjectionEngine(optimize_noise=True) with one target (a set of one, against the per-map loops of
 tests/noise_per_map_engine.py, bit for bit) and with two different targets and noise_per_target=True (each against its own autograd + Adam
 run on the CPU), then the drivers.
