@@ -349,6 +349,29 @@ int mgf_attn_values_multi(const mgf_attn_job* jobs_dev, int32_t njobs, const flo
  *   rgb_weights: out[n, c, co] = w[c, co] * s[n, co] */
 int mgf_randn_f32(float* out, int64_t n, uint64_t seed, void* state, mgf_stream_t stream);
 int mgf_rgb_weights_f32(float* out, const float* w, const float* s, int32_t n, int32_t c, int32_t cout, mgf_stream_t stream);
+/* Per-layer noise maps of noise_mode="keyed": N(0,1) values addressed by what they are for, not by how many were drawn before them.  This
+ * comment is the definition of the stream.
+ *   layout:   out is layer-major, flat: [layer l][sample j][sides[l] * sides[l]], n samples; layer l starts at n * sum_{l' < l} sides[l']^2.
+ *             `sides` is a HOST array of n_layers even sides >= 2 (read at call time; at most 32 layers, sides up to 65536).
+ *   counter:  quad q (floats 4q .. 4q + 3 of one sample's map of one layer) takes the four output words of Philox4x32-10 on the counter
+ *             {q, l, (uint32) s_j, (uint32) aux_j} under the key {(uint32) *key, (uint32) (*key >> 32)}, where
+ *               s_j   = min(step[j * step_stride] + j * step_add, step_max)       (64-bit sum; step_stride 0: one counter for all samples)
+ *               aux_j = aux0 + j * aux_add
+ *             `key` (uint64, 8-byte aligned) and `step` (int32) are read from DEVICE memory by the launch: a captured launch follows the
+ *             loop counter and a re-keyed engine without re-capture.  Philox4x32-10: ten rounds of
+ *               {c0, c1, c2, c3} <- {hi(0xCD9E8D57 c2) ^ c1 ^ k0, lo(0xCD9E8D57 c2), hi(0xD2511F53 c0) ^ c3 ^ k1, lo(0xD2511F53 c0)},
+ *             the key going {k0 + 0x9E3779B9, k1 + 0xBB67AE85} after each round -- mgf_randn_f32's rounds.
+ *   normals:  for h in {0, 1}, in float32:  u1 = ((float) c[2h] + 0.5f) * 2^-32,  u2 = ((float) c[2h+1] + 0.5f) * 2^-32,
+ *               r = sqrtf(-2 logf(min(u1, 0.99999994f))),  z[2h] = r cospif(2 u2),  z[2h+1] = r sinpif(2 u2)     -- mgf_randn_f32's expressions.
+ *   separation: aux0 >= 1 and aux_add >= 0 (every aux_j >= 1); mgf_randn_f32 uses the counters {lo, hi, 0, 0}, so under one key the two streams
+ *             never share a counter value.
+ * No device state: no ticket, no atomics, one writer per element; two launches with equal arguments and equal *key / step[] give equal bits,
+ * and sample j of a launch at step s equals sample 0 of a launch at step s + j (step_add 1, aux_add 0).  16-byte stores when out is
+ * 16-byte aligned, scalar stores otherwise (same values).  MGF_EINVAL (the message names randn_keyed), before any launch: a NULL pointer,
+ * n < 1, n_layers < 1, step_max < 0, step_stride < 0, aux0 < 1, aux_add < 0, an odd side or one below 2, a key that is not 8-byte aligned;
+ * MGF_ETOOBIG: more than 32 layers, a side above 65536. */
+int mgf_randn_keyed_f32(float* out, const int32_t* sides, int32_t n_layers, int32_t n, const uint64_t* key, const int32_t* step,
+                        int32_t step_stride, int32_t step_add, int32_t step_max, int32_t aux0, int32_t aux_add, mgf_stream_t stream);
 /* conv_last and ToRGB of the last block composed into one per-sample 3x3 kernel.  conv_last is built without bias, noise and attention
  * (networks.py:1124-1130), so it applies no bias and no activation (:973, :1010-1043); its only consumer is ToRGB, a modulated 1x1 without
  * demodulation plus a bias (:1054-1065, :1169-1173).  The two linear maps are one [rgb_channels, cin, 3, 3] convolution per sample:

@@ -753,25 +753,34 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint
     c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
 }
 
+// The ten rounds, the key bumped by the Weyl constants between them.
+__device__ __forceinline__ void philox10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { philox_round(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+}
+
+// Four N(0, 1) values from the four output words of one counter value: two Box-Muller pairs, (c0, c1) -> z0, z1 and (c2, c3) -> z2, z3.
+__device__ __forceinline__ void box_muller4(const uint32_t (&c)[4], float (&z)[4]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float u1 = ((float)c[2 * h] + 0.5f) * 2.3283064365386963e-10f;          // (0, 1]: + 0.5 keeps the logarithm finite
+        const float u2 = ((float)c[2 * h + 1] + 0.5f) * 2.3283064365386963e-10f;
+        const float r = sqrtf(-2.f * logf(u1 < 1.f ? u1 : 0.99999994f));
+        float sn, cs;
+        sincospif(2.f * u2, &sn, &cs);
+        z[2 * h] = r * cs; z[2 * h + 1] = r * sn;
+    }
+}
+
 __global__ __launch_bounds__(256) void randn_kernel(float* out, int64_t n, uint64_t seed, unsigned long long* counter, unsigned* ticket) {
     const unsigned long long base = *counter;                       // (every workgroup reads it before the last one to finish advances it)
     const int64_t quads = (n + 3) / 4;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (int64_t)gridDim.x * 256) {
         const unsigned long long ctr = base + (unsigned long long)q;
         uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-        uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-        for (int r = 0; r < 10; ++r) { philox_round(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        philox10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
         float z[4];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float u1 = ((float)c[2 * h] + 0.5f) * 2.3283064365386963e-10f;          // (0, 1]: + 0.5 keeps the logarithm finite
-            const float u2 = ((float)c[2 * h + 1] + 0.5f) * 2.3283064365386963e-10f;
-            const float r = sqrtf(-2.f * logf(u1 < 1.f ? u1 : 0.99999994f));
-            float sn, cs;
-            sincospif(2.f * u2, &sn, &cs);
-            z[2 * h] = r * cs; z[2 * h + 1] = r * sn;
-        }
+        box_muller4(c, z);
         if (4 * q + 4 <= n && (((uintptr_t)out) & 15) == 0) *reinterpret_cast<float4*>(out + 4 * q) = make_float4(z[0], z[1], z[2], z[3]);
         else for (int e = 0; e < 4 && 4 * q + e < n; ++e) out[4 * q + e] = z[e];
     }
@@ -782,6 +791,42 @@ __global__ __launch_bounds__(256) void randn_kernel(float* out, int64_t n, uint6
             __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(counter, base + (unsigned long long)quads, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+    }
+}
+
+// noise_mode="keyed": the same generator addressed by WHAT a value is for instead of by how many were drawn before it.  The counter of the
+// quad q (four consecutive floats) of sample j's map of layer l is {q, l, s_j, aux_j}, s_j = min(step[j * step_stride] + j * step_add,
+// step_max), aux_j = aux0 + j * aux_add, under the key *key -- no stream position, no ticket: every element has one writer, and a
+// launch's result depends on its arguments and on the two device words it reads alone.  aux_j >= 1 keeps it clear of randn_kernel's
+// counters {lo, hi, 0, 0} under one key.  Layout [layer][n][side * side], flat: layer l starts at n * first[l] quads, first[l] = the
+// quads of one sample's maps of the layers in front of it.  side * side % 4 == 0 (even sides), so every map starts on a quad.
+constexpr int KEYED_MAX_LAYERS = 32;
+struct KeyedLayers {
+    int64_t first[KEYED_MAX_LAYERS + 1];        // first[n_layers] = the quads of one sample's maps of all layers
+    int32_t n_layers;
+};
+
+// VEC: out is 16-byte aligned (the host looks), every quad goes out as one 16-byte store; otherwise four scalar stores of the same values.
+template <bool VEC>
+__global__ __launch_bounds__(256) void randn_keyed_kernel(float* out, KeyedLayers L, int n, const unsigned long long* key, const int32_t* step,
+                                                          int step_stride, int step_add, int step_max, uint32_t aux0, int aux_add) {
+    const unsigned long long kv = *key;
+    const uint32_t k0 = (uint32_t)kv, k1 = (uint32_t)(kv >> 32);
+    const int64_t quads = (int64_t)n * L.first[L.n_layers];
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < quads; g += (int64_t)gridDim.x * 256) {
+        int l = 0;
+        while (l + 1 < L.n_layers && g >= (int64_t)n * L.first[l + 1]) ++l;
+        const int64_t per = L.first[l + 1] - L.first[l];            // quads of one map of this layer
+        const int64_t local = g - (int64_t)n * L.first[l];
+        const int j = (int)(local / per);
+        const uint32_t q = (uint32_t)(local - (int64_t)j * per);
+        const int64_t s = (int64_t)step[(int64_t)j * step_stride] + (int64_t)j * step_add;
+        uint32_t c[4] = {q, (uint32_t)l, (uint32_t)(int32_t)(s < step_max ? s : step_max), aux0 + (uint32_t)j * (uint32_t)aux_add};
+        philox10(c, k0, k1);
+        float z[4];
+        box_muller4(c, z);
+        if (VEC) *reinterpret_cast<float4*>(out + 4 * g) = make_float4(z[0], z[1], z[2], z[3]);
+        else { out[4 * g] = z[0]; out[4 * g + 1] = z[1]; out[4 * g + 2] = z[2]; out[4 * g + 3] = z[3]; }
     }
 }
 
@@ -818,6 +863,35 @@ extern "C" int mgf_randn_f32(float* out, int64_t n, uint64_t seed, void* state, 
     hipLaunchKernelGGL(randn_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, n, seed, reinterpret_cast<unsigned long long*>(state),
                        reinterpret_cast<unsigned*>(reinterpret_cast<char*>(state) + 8));
     MGF_CHECK_LAUNCH("randn");
+    return MGF_OK;
+}
+
+extern "C" int mgf_randn_keyed_f32(float* out, const int32_t* sides, int32_t n_layers, int32_t n, const uint64_t* key, const int32_t* step,
+                                   int32_t step_stride, int32_t step_add, int32_t step_max, int32_t aux0, int32_t aux_add, mgf_stream_t stream) {
+    MGF_REQUIRE(out && sides && key && step, MGF_EINVAL, "randn_keyed: null pointer");
+    MGF_REQUIRE(n >= 1 && n_layers >= 1, MGF_EINVAL, "randn_keyed: n and n_layers must be >= 1 (got %d, %d)", n, n_layers);
+    MGF_REQUIRE(step_max >= 0 && step_stride >= 0, MGF_EINVAL, "randn_keyed: step_max and step_stride must be >= 0 (got %d, %d)", step_max, step_stride);
+    MGF_REQUIRE(aux0 >= 1, MGF_EINVAL, "randn_keyed: aux0 must be >= 1 (got %d; counters {., ., 0, 0} belong to the randn stream)", aux0);
+    MGF_REQUIRE(aux_add >= 0 && (int64_t)aux0 + (int64_t)(n - 1) * aux_add <= (int64_t)UINT32_MAX, MGF_EINVAL,
+                "randn_keyed: aux_add must be >= 0 and aux0 + (n - 1) aux_add fit 32 bits (got %d, %d): no sample's aux word may wrap to 0", aux0, aux_add);
+    MGF_REQUIRE(((uintptr_t)key % 8) == 0, MGF_EINVAL, "randn_keyed: the uint64 key must be 8-byte aligned");
+    MGF_REQUIRE(((uintptr_t)out % 4) == 0, MGF_EINVAL, "randn_keyed: out must be 4-byte aligned");
+    MGF_REQUIRE(n_layers <= KEYED_MAX_LAYERS, MGF_ETOOBIG, "randn_keyed: at most %d layers (got %d)", KEYED_MAX_LAYERS, n_layers);
+    KeyedLayers L;
+    L.n_layers = n_layers;
+    L.first[0] = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        const int32_t side = sides[l];
+        MGF_REQUIRE(side >= 2 && side % 2 == 0, MGF_EINVAL, "randn_keyed: sides must be even and >= 2 (layer %d: %d)", l, side);
+        MGF_REQUIRE(side <= 65536, MGF_ETOOBIG, "randn_keyed: sides up to 65536 (layer %d: %d)", l, side);       // the quad index is a 32-bit counter word
+        L.first[l + 1] = L.first[l] + (int64_t)side * side / 4;
+    }
+    for (int l = n_layers + 1; l <= KEYED_MAX_LAYERS; ++l) L.first[l] = L.first[n_layers];
+    const int grid = mgf_stream_grid((int64_t)n * L.first[n_layers], 256, 4);
+    const auto kernel = ((uintptr_t)out % 16) == 0 ? randn_keyed_kernel<true> : randn_keyed_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, L, n, reinterpret_cast<const unsigned long long*>(key), step,
+                       step_stride, step_add, step_max, (uint32_t)aux0, aux_add);
+    MGF_CHECK_LAUNCH("randn_keyed");
     return MGF_OK;
 }
 

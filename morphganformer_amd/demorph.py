@@ -58,6 +58,9 @@ class DemorphEngine(GradientProjectionEngine):
         if optimize_noise:
             raise _lib.MgfError("DemorphEngine: optimize_noise=True is not built here (the noise maps are one set per engine, shared by both rows: "
                                 "maps fitted to the morph and the reference at once would not belong to the restored face)")
+        if noise_mode == "keyed" and not optimize_noise:
+            raise _lib.MgfError("DemorphEngine: noise_mode='keyed' is not built here (its two generator rows share ONE step counter, and the keyed "
+                                "launch of lockstep rows reads a counter per row); use 'random' or 'const'")
         if mdf is not None:
             raise _lib.MgfError("DemorphEngine: mdf= is not built here (the MDF objective runs with one target per engine; the two rows would need "
                                 "per-row discriminator activations)")

@@ -124,14 +124,17 @@ def generate_images(G, images_num=32, truncation_psi=0.7, output_dir=None, ratio
     return zs
 
 
-def render_latent(G, w, truncation_psi=0.7, noise_mode="random"):
+def render_latent(G, w, truncation_psi=0.7, noise_mode="random", noise_key=None, noise_step=None):
     """The image of a projected latent as the morph drivers render it: `G(w, truncation_psi)` for a z latent [n,k,D] (the 0.7 lands in `c`,
     SURVEY 0.2) and `G(ws=w)` for a W+ latent [n,k,num_ws,D] (gradient mode, latent_space="w+": every layer reads its own slot;
-    truncation acts in the mapping network only, networks.py:935-941, so there is none to apply).  -> [n,3,R,R], the caller's own tensor."""
+    truncation acts in the mapping network only, networks.py:935-941, so there is none to apply).  -> [n,3,R,R], the caller's own tensor.
+    noise_mode="keyed" with noise_key / noise_step (a projection result's `noise_key` and `step`): the per-layer maps that step of a
+    noise_mode="keyed" projection was scored with, for every latent of `w` -- the image the loop ranked, rendered again."""
     w = (w if isinstance(w, torch.Tensor) else torch.from_numpy(np.asarray(w, dtype=np.float32))).to(G.device)
+    keyed = dict(noise_key=noise_key, noise_step=noise_step, noise_step_add=0) if noise_mode == "keyed" else {}
     if w.ndim == 4:
-        return G(ws=w, noise_mode=noise_mode)[0]
-    return G(w, truncation_psi, noise_mode=noise_mode)[0]
+        return G(ws=w, noise_mode=noise_mode, **keyed)[0]
+    return G(w, truncation_psi, noise_mode=noise_mode, **keyed)[0]
 
 
 def merge_morph(G, w1, w2, alphas=(0.5,), truncation_psi=0.7, noise_mode="random", out_prefix=None, ratio=1.0, batched=False):
@@ -542,7 +545,12 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
 
     engine: a ProjectionEngine from an earlier call with the same generator, objective, step count and batch (return_engine=True
     hands it out) -- it is re-targeted in place (`ProjectionEngine.retarget`), which keeps its captured hipGraph and workspaces; this is
-    how `project_many` walks a list of targets."""
+    how `project_many` walks a list of targets.
+
+    noise_mode="keyed": the per-layer noise of step i is a function of (seed, i) alone (ProjectionEngine), so the run replays bit for bit and
+    does not depend on how its steps were launched.  The result gains `noise_key` (the seed's 64 bits), the final PNG is rendered with the best
+    step's maps instead of constant noise -- the scored image -- and render_latent(G, res["w"], noise_mode="keyed", noise_key=res["noise_key"],
+    noise_step=res["step"]) renders it again."""
     args = args or ProjectionArgs()
     if mode not in ("literal", "gradient", "evolution"):
         raise ValueError(f"mode must be 'literal', 'gradient' or 'evolution' (got {mode!r})")
@@ -594,7 +602,7 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
                                       ("face_crop", engine.face_crop_filter == (face_crop_filter if crop is not None else None))) if not ok]
         if diff:
             raise ValueError("engine= was built for another objective: " + ", ".join(diff) + " differ(s); build a fresh engine")
-        eng = engine.retarget(target, lm_target=lm_target, lm_steps=lm_steps, eps=eps, seed=seed if eps is None else None,
+        eng = engine.retarget(target, lm_target=lm_target, lm_steps=lm_steps, eps=eps, seed=seed if (eps is None or noise_mode == "keyed") else None,
                               latent_mean=latent_mean, latent_std=float(latent_std), lbp_target=lbp_target, region_weight=region_weight,
                               face_crop=crop)
     elif mode == "gradient":
@@ -615,6 +623,11 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     out = {"w": w, "step": step, "loss": loss, "losses": losses}
     if mode == "evolution":
         out["mean"], out["elite_used"] = eng.mean.cpu(), eng.elite_used()
+    # noise_mode="keyed": the key the run drew under; with the best step it names the maps of the scored image, which every rendering below uses
+    png_kw = {}
+    if noise_mode == "keyed" and not optimize_noise:
+        out["noise_key"] = int(eng.noise_key.item()) & 0xFFFFFFFFFFFFFFFF
+        png_kw = dict(noise_mode="keyed", noise_key=out["noise_key"], noise_step=int(step))
     best_noises = None
     if optimize_noise:
         best_noises = {name: t.clone() for name, t in eng.best_noises.items()}
@@ -622,12 +635,12 @@ def project_image(G, target, lm_target, lm_steps, args: ProjectionArgs = None, p
     if out_prefix is not None:
         save_latent_mat(f"{out_prefix}.mat", w, noises=best_noises)
         if path_to_gen is None:                      # no improvement trail asked for: still leave an image of the result beside the latent
-            out["image"] = save_best_png(G, w, f"{out_prefix}.png", args.ratio, noises=best_noises)
+            out["image"] = save_best_png(G, w, f"{out_prefix}.png", args.ratio, noises=best_noises, **png_kw)
     if path_to_gen is not None:
         if sampling:
             out["images"] = eng.save_improvements(path_to_gen, args.ratio)
         else:
-            out["images"] = [save_best_png(G, w, os.path.join(path_to_gen, "{:06d}_{:04f}.png".format(step, loss)), args.ratio, noises=best_noises)]
+            out["images"] = [save_best_png(G, w, os.path.join(path_to_gen, "{:06d}_{:04f}.png".format(step, loss)), args.ratio, noises=best_noises, **png_kw)]
     if lpips_map:
         out["lpips_map"] = _best_lpips_map(G, percept, w, target, best_noises)
         if path_to_gen is not None:
@@ -814,6 +827,8 @@ def _project_group(G, targets, landmarks, args: ProjectionArgs = None, percept=N
     out = {"w": w, "step": step, "loss": loss, "losses": losses}
     if len(targets) == 1:
         out = {"w": w, "step": np.array([step]), "loss": np.array([loss]), "losses": losses[None]}
+    if noise_mode == "keyed" and not optimize_noise:
+        out["noise_key"] = int(eng.noise_key.item()) & 0xFFFFFFFFFFFFFFFF
     if optimize_noise:
         out["noises"] = [{name: t[j].clone() for name, t in eng.best_noises.items()} for j in range(len(targets))]
     return out

@@ -288,6 +288,7 @@ class Generator:
         self._workspaces, self._pins = {}, {}
         self.noise_seed, self._noise_epoch = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF, None
         self.noise_state = torch.zeros(2, dtype=torch.int64, device=self.device)          # {stream position, ticket}: advanced on the device
+        self._keyed_words = {}                # noise_mode="keyed": the device words made from host ints (key / step), kept by value
         self._alloc(max_batch)
 
     # ------------------------------------------------------------------ workspace
@@ -549,10 +550,16 @@ class Generator:
         _lib.check(rc, "mapping_forward")
         return self.w_buf
 
-    def synthesis(self, w, noise_mode="random", noises=None, return_att=False):
+    def synthesis(self, w, noise_mode="random", noises=None, return_att=False, noise_key=None, noise_step=None, noise_step_stride=0,
+                  noise_step_add=1, noise_step_max=None, noise_aux=(1, 0)):
         """w: [n, k, D] -- one latent set shared by all layers, as every driver uses it -- or ws [n, k, num_ws, D] with per-layer
         latents (W+; layer `slot` reads ws[:, :, slot] for its style AND its attention values, networks.py:1022-1031,1252-1253).
-        Returns img [n,3,R,R] (the workspace buffer: valid until the next call with this batch size)."""
+        Returns img [n,3,R,R] (the workspace buffer: valid until the next call with this batch size).
+
+        noise_mode="keyed": the per-layer maps are drawn by what they are for (_draw_noise_keyed) -- sample j of the call takes the maps of
+        (noise_key, step min(noise_step[j * noise_step_stride] + j * noise_step_add, noise_step_max), aux noise_aux[0] + j * noise_aux[1]).
+        noise_key: a device int64[1] tensor or a host int; noise_step: a device int32 tensor or a host int; both are required.  Defaults: one
+        counter for all samples, + 1 per sample, no clamp, aux (1, 0).  The other modes ignore these keywords."""
         cfg, P, L = self.cfg, self.plan, _lib.lib()
         n = w.shape[0]
         if n != self.n:
@@ -583,6 +590,8 @@ class Generator:
                        "attn_values_multi")
         if noise_mode == "random":
             noises = self._draw_noise(n)
+        elif noise_mode == "keyed":
+            noises = self._draw_noise_keyed(n, noise_key, noise_step, noise_step_stride, noise_step_add, noise_step_max, noise_aux)
         self.last_noise = (noise_mode, noises)
         layers = {lp.name: lp for lp in P.layers}
         self.att_maps = {} if return_att else None
@@ -695,11 +704,9 @@ class Generator:
         `torch.manual_seed(s)` -- or any foreign draw -- in front of a call re-keys the stream, so `manual_seed(s); G(z)` is reproducible
         call for call.  Replays of a captured graph cannot see the host generator: they continue the device-side stream of the key the
         capture saw (an eager loop and a replayed loop of one engine therefore draw different, equally distributed noise).  `seed_noise`
-        gives the stream a key of its own."""
-        sizes = [(lp.name, lp.res) for lp in self.plan.layers if lp.noise_strength is not None]
-        total = sum(r * r for _, r in sizes)
-        if self.noise_rand is None or self.noise_rand.numel() != n * total:
-            self.noise_rand = torch.empty(n * total, dtype=torch.float32, device=self.device)
+        gives the stream a key of its own.  noise_mode="keyed" (_draw_noise_keyed) is the mode that does not depend on the launch order;
+        this one is unchanged by it, bit for bit."""
+        sizes = self._noise_buffer(n)
         # The library's own Philox / Box-Muller kernel: its stream position lives on the device and every launch -- every replay of a
         # captured graph -- advances it.  torch.manual_seed still governs it, like the reference's torch.randn: outside graph capture the
         # call looks at torch's CUDA generator -- (seed, offset) other than what the previous draw left behind means the user re-seeded (or
@@ -714,11 +721,64 @@ class Generator:
             self._noise_epoch = (seed, off + 4)
         _lib.check(_lib.lib().mgf_randn_f32(self.noise_rand.data_ptr(), self.noise_rand.numel(), self.noise_seed, self.noise_state.data_ptr(),
                                             _lib.stream_ptr()), "randn")
+        return self._noise_views(n, sizes)
+
+    def _noise_buffer(self, n):
+        """[(layer name, side)] of the layers that add noise, with `noise_rand` sized for n samples of their maps (layer-major, flat)."""
+        sizes = [(lp.name, lp.res) for lp in self.plan.layers if lp.noise_strength is not None]
+        total = sum(r * r for _, r in sizes)
+        if self.noise_rand is None or self.noise_rand.numel() != n * total:
+            self.noise_rand = torch.empty(n * total, dtype=torch.float32, device=self.device)
+        return sizes
+
+    def _noise_views(self, n, sizes):
         out, off = {}, 0
         for name, r in sizes:
             out[name] = self.noise_rand[off * n:(off + r * r) * n].view(n, r * r)
             off += r * r
         return out
+
+    def _keyed_word(self, value, dtype, what):
+        """A device tensor for the key (int64[1]) / the step counter (int32) of noise_mode="keyed": the caller's own tensor, or one made from
+        a host int and kept by value (the launch reads it asynchronously; a captured launch must be given tensors)."""
+        if isinstance(value, torch.Tensor):
+            _lib.require_gpu(value)
+            if value.dtype != dtype or value.numel() < 1 or not value.is_contiguous():
+                raise _lib.MgfError(f"noise_mode='keyed': {what} must be a contiguous device {dtype} tensor (got {value.dtype}, {tuple(value.shape)})")
+            return value
+        if value is None:
+            raise _lib.MgfError(f"noise_mode='keyed' needs {what} (a device {dtype} tensor or an int): the maps are a function of noise_key and "
+                                "noise_step, there is no stream to continue")
+        v = int(value)
+        if dtype == torch.int64:                    # the 64 key bits, as the signed value that holds them
+            v &= 0xFFFFFFFFFFFFFFFF
+            v -= (v >> 63) << 64
+        t = self._keyed_words.get((dtype, v))
+        if t is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.MgfError(f"noise_mode='keyed': {what} is a host int inside a graph capture; pass a device tensor")
+            if len(self._keyed_words) >= 256:
+                self._keyed_words.clear()
+            t = self._keyed_words[(dtype, v)] = torch.tensor([v], dtype=dtype, device=self.device)
+        return t
+
+    def _draw_noise_keyed(self, n, key, step, step_stride=0, step_add=1, step_max=None, aux=(1, 0)):
+        """The per-layer maps of noise_mode="keyed": ONE mgf_randn_keyed_f32 launch into the buffer and views of random mode.  A value is
+        addressed by (key, layer, step, aux, position in the map) -- include/mgf.h has the definition -- so the maps do not depend on the
+        launch order: not on the batch size a step was scored in, eager or replayed, pipelined or not, the warm-up passes of a capture, or
+        what ran before.  No host state is read or advanced (torch's CUDA generator is not looked at); the key and the counter are read from
+        the device by the launch, so a captured launch follows a loop counter and a re-keyed engine."""
+        sizes = self._noise_buffer(n)
+        key_t = self._keyed_word(key, torch.int64, "noise_key")
+        step_t = self._keyed_word(step, torch.int32, "noise_step")
+        step_stride, step_add = int(step_stride), int(step_add)
+        if step_stride < 0 or (n - 1) * step_stride >= step_t.numel():
+            raise _lib.MgfError(f"noise_mode='keyed': noise_step holds {step_t.numel()} counter(s), {n} samples at stride {step_stride} read past them")
+        step_max = 2 ** 31 - 1 if step_max is None else int(step_max)
+        sides = (C.c_int32 * len(sizes))(*[r for _, r in sizes])
+        _lib.check(_lib.lib().mgf_randn_keyed_f32(self.noise_rand.data_ptr(), sides, len(sizes), n, key_t.data_ptr(), step_t.data_ptr(), step_stride,
+                                                  step_add, step_max, int(aux[0]), int(aux[1]), _lib.stream_ptr()), "randn_keyed")
+        return self._noise_views(n, sizes)
 
     def _bf_direct(self, lp, n, residual_low):
         """Does this 3x3 layer take the bf16x3 direct kernel?  Only in that mode, only where it wins: maps of 32^2 .. 128^2 (the layers whose
@@ -769,14 +829,19 @@ class Generator:
         return y
 
     def forward_workspace(self, z=None, c=None, ws=None, truncation_psi=1, truncation_cutoff=None, return_img=True, return_att=False,
-                          return_ws=False, subnet=None, noise_mode="random", noises=None, fused_modconv=None, att_format="tensor", lean=False):
+                          return_ws=False, subnet=None, noise_mode="random", noises=None, fused_modconv=None, att_format="tensor", lean=False,
+                          noise_key=None, noise_step=None, noise_step_stride=0, noise_step_add=1, noise_step_max=None, noise_aux=(1, 0)):
         """Generator.forward (networks.py:1304-1331), zero-copy: the returned image IS the workspace buffer of this batch size and is
         overwritten by the next call (what the projection engines want; `__call__` hands out copies).
 
         ws [n, k, num_ws, D]: per-layer latents are honoured (every layer reads its own slot, :1252-1253).  truncation_psi /
         truncation_cutoff act in the mapping network only, i.e. when `z` is given (:1317, :935-941).  return_att=True returns the
         stacked attention tensor [n, k-1, layers, 1, R, R] of list2tensor (:1262,1222-1242); att_format="maps" returns the per-layer
-        dict {layer: (probs [n,F,k-1], argmax [n,F])} instead (the cheap form: the stacked tensor is 738 MB per image at 1024^2)."""
+        dict {layer: (probs [n,F,k-1], argmax [n,F])} instead (the cheap form: the stacked tensor is 738 MB per image at 1024^2).
+
+        noise_mode="keyed" with noise_key / noise_step (and noise_step_stride / noise_step_add / noise_step_max / noise_aux): `synthesis`."""
+        if noise_mode == "keyed" and (noise_key is None or noise_step is None):
+            raise _lib.MgfError("Generator: noise_mode='keyed' needs noise_key and noise_step (the maps are a function of the two)")
         lean = bool(lean) and self.taps is None and not return_att      # (intermediate tensors are handed out: they need their own storage)
         nb = (z if ws is None else ws)
         if nb is not None and (nb.shape[0], lean) != (self.n, self.lean):
@@ -804,7 +869,9 @@ class Generator:
             w_in = ws_out = ws.contiguous().float()
         ret = ()
         if return_img or return_att:
-            img = self.synthesis(w_in if w_in.ndim == 4 else w_in.contiguous(), noise_mode=noise_mode, noises=noises, return_att=return_att)
+            img = self.synthesis(w_in if w_in.ndim == 4 else w_in.contiguous(), noise_mode=noise_mode, noises=noises, return_att=return_att,
+                                 noise_key=noise_key, noise_step=noise_step, noise_step_stride=noise_step_stride, noise_step_add=noise_step_add,
+                                 noise_step_max=noise_step_max, noise_aux=noise_aux)
             if return_img:
                 ret += (img,)
             if return_att:

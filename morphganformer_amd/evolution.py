@@ -144,6 +144,9 @@ def build_parser():
     ap.add_argument("--mean-lr", type=float, default=1.0, help="step of the mean towards the recombined point, in (0, 1]")
     ap.add_argument("--pixel-term", choices=["mse", "psnr", "dssim", "msssim"], default="mse",
                     help="the pixel term, as the literal loop scores it (dssim: of the uint8 images)")
+    ap.add_argument("--noise-mode", choices=["random", "const", "keyed"], default="random",
+                    help="the generator's per-layer noise: fresh draws in launch order (random), the checkpoint's constant maps (const), or draws "
+                         "keyed by --seed and the step number (keyed: a run replays bit for bit and the best image can be re-rendered)")
     ap.add_argument("--noise_ramp", type=float, default=0.75)
     ap.add_argument("--truncation_psi", type=float, default=0.7)
     ap.add_argument("--min-loss-init", type=float, default=100.0)
@@ -186,7 +189,7 @@ def main(argv=None):
             raise SystemExit(f"--landmarks holds {lm_s.shape[0]} steps, --step is {a.step}")
     stem = os.path.splitext(os.path.basename(a.image))[0]
     res = drivers.project_image(G, target, lm_t, lm_s, args=args, percept=percept, biometric=biometric, gamma=a.gamma, use_mse=not a.no_mse,
-                                seed=a.seed, batch=a.batch, mode="evolution", elite=a.elite, es_weights=a.es_weights, mean_lr=a.mean_lr,
+                                seed=a.seed, batch=a.batch, mode="evolution", noise_mode=a.noise_mode, elite=a.elite, es_weights=a.es_weights, mean_lr=a.mean_lr,
                                 keep_images=a.keep_images, out_prefix=os.path.join(a.path_to_gen, stem), path_to_gen=a.path_to_gen)
     moved = int((res["elite_used"] > 0).sum())
     print(f"best step {res['step']}  loss {res['loss']:.6f}  (the mean moved in {moved} of {len(res['elite_used'])} generations)")

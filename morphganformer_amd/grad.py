@@ -174,8 +174,10 @@ class GeneratorGrad:
         _lib.check(_lib.lib().mgf_attn_grad_multi(D["table"].data_ptr(), len(D["jobs"]), self.G.n, g, d, r, _lib.stream_ptr()), "attn_grad_multi")
 
     # ------------------------------------------------------------------ forward
-    def forward(self, z=None, ws=None, truncation_psi=1, noise_mode="const", noises=None):
-        """G(z)[0] (or G(ws=...)) with conv_last kept in memory (the fused conv_last+ToRGB kernel never writes it)."""
+    def forward(self, z=None, ws=None, truncation_psi=1, noise_mode="const", noises=None, **keyed):
+        """G(z)[0] (or G(ws=...)) with conv_last kept in memory (the fused conv_last+ToRGB kernel never writes it).  keyed: the noise_key /
+        noise_step / ... keywords of noise_mode="keyed" (Generator.synthesis); the backward pass reads those maps from G.last_noise exactly
+        as it reads random ones."""
         G = self.G
         if ws is not None:
             # ws [n, k, num_ws, D]: a broadcast VIEW (what mapping() returns: stride 0 over the layer axis) or [n, k, D] takes the shared
@@ -204,9 +206,9 @@ class GeneratorGrad:
             if ws is not None:
                 if (w.shape[0], False) != (G.n, G.lean):        # the backward pass reads every layer output: the FULL workspace flavour
                     G._alloc(w.shape[0], False)
-                img = G.synthesis(w, noise_mode=noise_mode, noises=noises)
+                img = G.synthesis(w, noise_mode=noise_mode, noises=noises, **keyed)
             else:
-                img = G.forward_workspace(z, None, truncation_psi=truncation_psi, noise_mode=noise_mode, noises=noises)[0]
+                img = G.forward_workspace(z, None, truncation_psi=truncation_psi, noise_mode=noise_mode, noises=noises, **keyed)[0]
         finally:
             G.fuse_torgb, G.fuse_skip_up, G.map_save = True, keep_up, None
         self.z = None if z is None else z.contiguous().float()

@@ -51,7 +51,7 @@ class GradientProjectionEngine(ProjectionEngine):
         optimize_noise: the generator's per-layer noise inputs become parameters next to the latent, as in the StyleGAN2-style projectors the
         drivers derive from (they still carry noise_regularize / noise_normalize_ and the --noise_regularize flag, :32-60, :243): the maps are
         engine-owned tensors (`noise_init`: "randn", seeded, or "const", a copy of every layer's noise_const) the generator runs with
-        (`noise_mode` is then irrelevant), the total gains args.noise_regularize * sum over the maps of the regulariser, and every step the maps take
+        (`noise_mode` is then irrelevant, "keyed" included), the total gains args.noise_regularize * sum over the maps of the regulariser, and every step the maps take
         an Adam step with the latent's learning rate and betas followed by noise_normalize_.  `noises` holds the current maps, `best_noises`
         those of the best step's image ({layer name: [B, res, res]}, row j: target j), both filled inside the launch sequence.  Every target
         owns a SET of maps (one target: a set of one): the maps, their gradient, the Adam moments and the best step's maps are [B, total]
@@ -288,6 +288,14 @@ class GradientProjectionEngine(ProjectionEngine):
                                                   self.noise_total, self.noise_ctr.data_ptr(), 1, vptr, vstride, self.steps,
                                                   self.noise_scratch.data_ptr(), st), "noise_sets_normalize")
 
+    def _noise_kw(self, ctr):
+        """noise_mode="keyed": row t of the forward is target t at ITS step -- stride 1 over the per-target counters, nothing added per row --
+        so a target of a lockstep group draws what a one-target engine on it draws."""
+        kw = super()._noise_kw(ctr)
+        if kw["noise_mode"] == "keyed":
+            kw.update(noise_step_stride=1 if self.targets > 1 else 0, noise_step_add=0, noise_aux=(1, 0))
+        return kw
+
     # The three points at which a subclass couples the rows (demorph.DemorphEngine: rows that are linear mixes of parameters).  Here a row IS
     # a parameter: the hooks add no launch and reorder none.
     def _make_rows(self):
@@ -321,7 +329,7 @@ class GradientProjectionEngine(ProjectionEngine):
         opt_noise = self.optimize_noise
         if opt_noise:
             self._noise_pack()
-        nkw = dict(noise_mode="inject", noises=self.gen_noises) if opt_noise else dict(noise_mode=self.noise_mode)
+        nkw = dict(noise_mode="inject", noises=self.gen_noises) if opt_noise else self._noise_kw(self.step_ctr)
         if self.latent_space == "w+":
             img = self.gg.forward(ws=rows, **nkw)                                 # [B, k, num_ws, D]: every layer reads its own slot
         else:

@@ -242,6 +242,12 @@ class ProjectionEngine:
 
         face_crop: the biometric term embeds through the aligned face crop (BiometricLoss.set_crop; an ArcFace embedder) -- the [2,3] matrix of
         the candidates, crop pixel index -> pixel index of the image the losses see (the pooled one under pool_above: drivers.scale_crop);
+        noise_mode: the generator's per-layer noise.  "random" (the drivers'): fresh draws in launch order, so a result depends on the batch
+        size, eager or replayed, pipelined or not.  "keyed": the maps of step i are a function of (seed, i) alone (Generator._draw_noise_keyed;
+        the key is `seed`, held in the device tensor `noise_key`, which retarget(seed=...) rewrites in place) -- every launch form of one batch
+        size gives the same bits, a rewound or re-targeted engine repeats its run, and drivers.render_latent(noise_mode="keyed",
+        noise_key=seed, noise_step=best step) re-renders the image that was scored.
+
         face_crop_target / face_crop_target_b: the matrices of the target image(s), face_crop by default; face_crop_filter "area" or
         "bilinear".  The engine only hands them to `biometric.set_crop` ahead of its set_target calls; without face_crop it never touches the
         crop, and one set on the BiometricLoss by hand stays."""
@@ -264,6 +270,7 @@ class ProjectionEngine:
             raise _lib.MgfError("projection: pixel_term='lbp' is the whole objective of 1024_example_LBP_percept.py -- pass lbp_target "
                                 "(lbp.target_feature of the target file) and no landmark / LPIPS / biometric term")
         self.noise_mode = noise_mode
+        self.noise_key = None                       # noise_mode="keyed": the key on the device (_init_state)
         k, D = G.cfg.k, G.cfg.z_dim
         # (k, D): the drivers' z latent.  GradientProjectionEngine(latent_space="w+") passes (k, num_ws, D)
         self.latent_shape = ls = tuple(latent_shape) if latent_shape is not None else (k, D)
@@ -379,6 +386,9 @@ class ProjectionEngine:
         self.valid = None if lm_valid is None else torch.as_tensor(lm_valid, dtype=torch.int32, device=dev).contiguous()
         if nt > 1 and self.valid is not None:
             self.valid = self.valid.reshape(nt, -1)
+        if self.noise_mode == "keyed":              # what the keyed launches read next to the step counter; not rewound: a rewound run repeats
+            self.noise_key = self._reg(torch.zeros(1, dtype=torch.int64, device=dev))
+            self._set_noise_key(seed)
         # device-resident loop state, one row per target (select_best advances a target's own counter)
         self.step_ctr = self._reg(torch.zeros(nt, dtype=torch.int32, device=dev), 0)
         self.min_loss = self._reg(torch.full([nt], float(a.min_loss_init), dtype=torch.float64, device=dev), float(a.min_loss_init))
@@ -390,6 +400,18 @@ class ProjectionEngine:
         self.p_loss = torch.zeros(n, dtype=torch.float32, device=dev)
         self.mse_loss = torch.zeros(n, dtype=torch.float32, device=dev)
         self.w_loss = torch.zeros(n, dtype=torch.float64, device=dev)
+
+    def _set_noise_key(self, seed):
+        """The 64 key bits of `seed` into the device tensor the captured keyed launches read (in place)."""
+        v = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.noise_key.fill_(v - ((v >> 63) << 64))
+
+    def _noise_kw(self, ctr):
+        """The generator's noise keywords of one forward whose sample j is step ctr + j: in keyed mode the counter and the clamp that
+        mgf_latent_perturb reads, so candidate j of a batch draws the maps of ITS step whatever batch it is scored in."""
+        if self.noise_mode != "keyed":
+            return dict(noise_mode=self.noise_mode)
+        return dict(noise_mode="keyed", noise_key=self.noise_key, noise_step=ctr, noise_step_add=1, noise_step_max=self.steps - 1)
 
     def _reg(self, tensor, reset=None):
         """Register a loop-state tensor where it is allocated, and return it.  Every registered tensor is saved and restored around a graph
@@ -457,7 +479,7 @@ class ProjectionEngine:
             _lib.check(L.mgf_latent_perturb(latent_n.data_ptr(), self.latent_in.data_ptr(), self.eps.data_ptr(),
                                             self.sigma.data_ptr(), ctr.data_ptr(), B, self.steps, self.numel, st), "latent_perturb")
         # psi lands in `c`.  lean: the literal loop has no backward pass -- layer outputs share arenas block after block
-        return self.G.forward_workspace(latent_n, a.truncation_psi, noise_mode=self.noise_mode, lean=True)[0]
+        return self.G.forward_workspace(latent_n, a.truncation_psi, lean=True, **self._noise_kw(ctr))[0]
 
     def _loss_phase(self, img, latent_n):
         L, st, a, B = _lib.lib(), _lib.stream_ptr(), self.args, self.batch
@@ -639,8 +661,8 @@ class ProjectionEngine:
 
     def _capture_graphs(self, warmup, bodies):
         """THE capture protocol of every launch mode.  warmup: bodies run once each, eagerly, in order, on a side stream (allocations, lazy
-        init; they advance the loop for real, and random per-layer noise is drawn in launch order: their number and order are part of a mode's
-        result).  bodies: [(body, index into this list of the graph whose memory pool it shares, or None)], captured in order.  The loop state
+        init; they advance the loop for real, and noise_mode="random" draws its per-layer noise in launch order: their number and order are part
+        of a mode's result there -- unchanged -- while noise_mode="keyed" draws by (key, step) and does not depend on them).  bodies: [(body, index into this list of the graph whose memory pool it shares, or None)], captured in order.  The loop state
         -- every registered tensor -- is saved in front and put back afterwards, and the generator's workspace is pinned.  Returns the graphs."""
         state = [t.clone() for t in self._state()]
         main, s = torch.cuda.current_stream(self.device), torch.cuda.Stream(device=self.device)
@@ -688,7 +710,7 @@ class ProjectionEngine:
         """Point this engine at ANOTHER target image and rewind the loop, keeping everything that was expensive to set up: the captured
         hipGraph(s), the generator workspace, the LPIPS / embedder workspaces, the loss scratch.  Only data changes, in place, in the
         buffers the graph already references: the target image and its cached LPIPS taps / embedding, the landmark tables, the noise
-        stream (`eps` given, or redrawn from `seed`), optionally the start latent and the noise schedule, and the loop state (step
+        stream (`eps` given, or redrawn from `seed`; `seed` also re-keys noise_mode="keyed"), optionally the start latent and the noise schedule, and the loop state (step
         counter, best-so-far, loss history, improvement trail).  A run after retarget() equals the run of a freshly constructed engine
         on the same inputs bit for bit (tests/test_hip_drivers.py).  This is what the reference's serial per-image loop amortises by
         keeping G / percept / latent statistics outside `projection()` (projection_example_v2_percept_morph.py:311-355); BASELINE
@@ -723,6 +745,8 @@ class ProjectionEngine:
             self.eps[:a.step].copy_(eps[:a.step].reshape(a.step, *self.eps.shape[1:]))
         elif seed is not None:
             self.eps.copy_(seeded_randn(self.eps.shape, dev, seed))                      # same draw as the constructor's
+        if seed is not None and self.noise_key is not None:
+            self._set_noise_key(seed)               # noise_mode="keyed": the captured launches read the key from this tensor
         if latent_mean is not None:
             self.latent_in.copy_(latent_mean.detach().reshape(self.latent_in.shape))
         if latent_std is not None:
@@ -755,17 +779,19 @@ class ProjectionEngine:
         return self.best_latent.cpu().clone(), bs, float(self.min_loss.item()), self.losses.cpu().numpy()
 
 
-def save_best_png(G, latent, path, ratio=1.0, noise_mode="const", noises=None):
+def save_best_png(G, latent, path, ratio=1.0, noise_mode="const", noises=None, noise_key=None, noise_step=None):
     """Write the image of `latent` as the drivers do (misc.to_pil + crop_max_rectangle, misc.py:94-130; :194-195).  noises: the per-layer
-    maps to render with (GradientProjectionEngine(optimize_noise=True).best_noises: the saved PNG is then the scored image)."""
+    maps to render with (GradientProjectionEngine(optimize_noise=True).best_noises: the saved PNG is then the scored image).
+    noise_mode="keyed" with noise_key / noise_step (the engine's seed and the best step): the maps the best step was scored with."""
     from . import misc
     latent = latent.to(G.device)
     if noises is not None:
         noise_mode = "inject"
+    keyed = dict(noise_key=noise_key, noise_step=noise_step, noise_step_add=0) if noise_mode == "keyed" else {}
     if latent.ndim == 4:                       # a W+ result [1, k, num_ws, D] (GradientProjectionEngine(latent_space="w+"))
-        img = G.forward_workspace(ws=latent, noise_mode=noise_mode, noises=noises)[0]
+        img = G.forward_workspace(ws=latent, noise_mode=noise_mode, noises=noises, **keyed)[0]
     else:
-        img = G.forward_workspace(latent, None, noise_mode=noise_mode, noises=noises)[0]
+        img = G.forward_workspace(latent, None, noise_mode=noise_mode, noises=noises, **keyed)[0]
     im = misc.crop_max_rectangle(misc.to_pil(img), ratio)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     im.save(path)
