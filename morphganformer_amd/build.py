@@ -27,7 +27,7 @@ LIB = os.path.join(HERE, "libmgf_hip.so")
 SOURCES = ["capi.cpp", "bias_act.hip", "upfirdn2d.hip", "conv_taps.hip", "latent_prep.hip", "attention.hip", "losses.hip", "lpips_stem.hip",
            "embed.hip", "backward.hip", "loss_bwd.hip", "adam.hip", "wino.hip", "wino3.hip", "pointwise.hip", "narrow_conv.hip", "warp.hip", "lbp.hip", "mdf.hip",
            "wino_tconv.hip", "depthwise.hip", "noise_opt.hip", "morph_pair.hip", "tconv_blur.hip", "msssim.hip", "face_crop.hip", "demorph.hip",
-           "evolution.hip", "block_pool.hip"]
+           "evolution.hip", "block_pool.hip", "maxpool.hip", "loop_step.hip", "dssim.hip"]
 HEADERS = [os.path.join(CSRC, "mgf_common.h"), os.path.join(ROOT, "include", "mgf.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=on: fma only inside one source expression (so `acc += a * b` still fuses) and never across statements --

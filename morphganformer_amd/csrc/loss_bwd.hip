@@ -1,10 +1,9 @@
 // Gradient mode, loss side: dLoss/dimage of the terms the synthesis network's pass (backward.hip) starts from -- what torch autograd does
-// for the reference through the LPIPS taps (lpips/networks_basic.py:64-92), the backbones' ReLU and max-pool layers
-// (lpips/pretrained_networks.py) and torch.nn.MSELoss.  The convolutions' data gradients are the forward kernels on transposed taps and live
-// with them; here are the element-wise and window kernels:
+// for the reference through the LPIPS taps (lpips/networks_basic.py:64-92), the backbones' ReLU layers (lpips/pretrained_networks.py) and
+// torch.nn.MSELoss.  The convolutions' data gradients are the forward kernels on transposed taps and live with them, the max-pool gradients
+// with the pools (maxpool.hip); here are the element-wise kernels:
 //   mgf_lpips_layer_bwd*              one tap's gradient, alone or fused with the tap's ReLU backward, plain / from stored stats / weighted
 //   mgf_relu_bwd_split_f32            ReLU backward into the two halves of a Fire concat
-//   mgf_maxpool*_bwd*                 MaxPool2d(3, 2, ceil_mode) from the input or from stored tap indices, MaxPool2d(2 | 3, 2) floor mode
 //   mgf_mse_grad_f32                  gradient of the per-sample mean squared error
 // No reduction across lanes beyond a workgroup's own pixels: every output element is written by one lane, bit-reproducible.
 // Contract: include/mgf.h ("Loss side of gradient mode").
@@ -142,123 +141,6 @@ __global__ __launch_bounds__(256) void relu_bwd_split_kernel(float* dz_a, float*
     }
 }
 
-// MaxPool2d(3, 2, ceil_mode=True) backward: the gradient of a window goes to its FIRST maximum in row-major order (torch's argmax rule).
-// A workgroup owns a 32 x 32 tile of INPUT elements of one plane.  The 17 x 17 windows that touch it (one row / column of them
-// belongs to the neighbouring tile and is recomputed) read a 35 x 35 input patch from LDS; every window's argmax (as a patch offset)
-// and gradient are computed once, then each input element collects from the <= 4 windows that cover it.
-// Input tile owned by a workgroup: 64 columns x 32 rows (both even: windows start on even rows / columns), the (32/2 + 1) x (64/2 + 1)
-// windows that touch it, and their (32 + 3) x (64 + 3) input patch.  The kernel is bound by its instruction count, not by memory
-// (2.1 TB/s in its first form): no coordinates are divided, the patch is padded with -inf so the window scan needs no bounds tests,
-// and a lane scatters the windows' gradients to one 2 x 2 block of inputs (whose four window memberships are fixed by parity).
-constexpr int MPTX = 64, MPTY = 32, MPWX = MPTX / 2 + 1, MPWY = MPTY / 2 + 1, MPIX = MPTX + 3, MPIY = MPTY + 3, MPS = MPIX + 1;
-__global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(float* dx, const float* dy, const float* x, int ih, int iw, int oh, int ow,
-                                                               int tiles_x, int tiles_y) {
-    __shared__ float patch[MPIY * MPS];
-    __shared__ int16_t arg[MPWY][MPWX + 1];
-    __shared__ float gw[MPWY][MPWX + 1];
-    const int tid = threadIdx.x;
-    const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y;
-    const int64_t pl = blockIdx.x / ((int64_t)tiles_x * tiles_y);
-    const int iy0 = ty * MPTY, ix0 = tx * MPTX;          // first owned input row / column
-    const int py0 = iy0 - 2, px0 = ix0 - 2;              // patch origin: patch[2 wy + ky][2 wx + kx] is tap (ky, kx) of local window (wy, wx)
-    const int wy0 = iy0 / 2 - 1, wx0 = ix0 / 2 - 1;      // first window row / column (may be -1)
-    const float* xp = x + pl * ih * iw;
-    const float* dp = dy + pl * oh * ow;
-    const float NEG = -__builtin_inff();
-    {
-        const int cc = tid & 63, r0 = tid >> 6;
-        const int xx = px0 + cc;
-        const bool xin = xx >= 0 && xx < iw;
-#pragma unroll
-        for (int r = r0; r < MPIY; r += 4) {
-            const int yy = py0 + r;
-            patch[r * MPS + cc] = (xin && yy >= 0 && yy < ih) ? xp[(int64_t)yy * iw + xx] : NEG;
-        }
-        if (tid < 3 * MPIY) {                            // the three columns past the 64th
-            const int r = tid / 3, c3 = 64 + tid - 3 * r;
-            const int yy = py0 + r, x3 = px0 + c3;
-            patch[r * MPS + c3] = (x3 < iw && yy >= 0 && yy < ih) ? xp[(int64_t)yy * iw + x3] : NEG;
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < MPWY * MPWX; i += 256) {
-        const int wy = i / MPWX, wx = i - wy * MPWX;
-        const int oy = wy0 + wy, ox = wx0 + wx;
-        int best = -1;
-        float g = 0.f;
-        if (oy >= 0 && ox >= 0 && oy < oh && ox < ow) {  // tap (0, 0) of a window that exists is inside the input
-            const int base = 2 * wy * MPS + 2 * wx;
-            float bv = patch[base];
-            best = base;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    if (ky == 0 && kx == 0) continue;
-                    const float v = patch[base + ky * MPS + kx];
-                    if (v > bv) { bv = v; best = base + ky * MPS + kx; }       // first maximum in row-major order (torch)
-                }
-            g = dp[(int64_t)oy * ow + ox];
-        }
-        arg[wy][wx] = (int16_t)best;
-        gw[wy][wx] = g;
-    }
-    __syncthreads();
-    // input block (2 br, 2 bc) + {0,1}^2 of the tile: windows (br, bc) .. (br + 1, bc + 1) in local indices; element (0,0) is in
-    // all four, (0,1) in the right two, (1,0) in the lower two, (1,1) in the last -- summed in ascending window order like torch
-#pragma unroll
-    for (int i = tid; i < (MPTY / 2) * (MPTX / 2); i += 256) {
-        const int br = i / (MPTX / 2), bc = i - br * (MPTX / 2);
-        const int yy = iy0 + 2 * br, xx = ix0 + 2 * bc;
-        if (yy >= ih || xx >= iw) continue;
-        const int me = (2 * br + 2) * MPS + 2 * bc + 2;
-        const int a00 = arg[br][bc], a01 = arg[br][bc + 1], a10 = arg[br + 1][bc], a11 = arg[br + 1][bc + 1];
-        const float g00 = gw[br][bc], g01 = gw[br][bc + 1], g10 = gw[br + 1][bc], g11 = gw[br + 1][bc + 1];
-        float e00 = 0.f, e01 = 0.f, e10 = 0.f, e11 = 0.f;
-        if (a00 == me) e00 += g00;
-        if (a01 == me) e00 += g01;
-        if (a10 == me) e00 += g10;
-        if (a11 == me) e00 += g11;
-        if (a01 == me + 1) e01 += g01;
-        if (a11 == me + 1) e01 += g11;
-        if (a10 == me + MPS) e10 += g10;
-        if (a11 == me + MPS) e10 += g11;
-        if (a11 == me + MPS + 1) e11 += g11;
-        float* o = dx + pl * ih * iw + (int64_t)yy * iw + xx;
-        const bool x1 = xx + 1 < iw;
-        o[0] = e00;
-        if (x1) o[1] = e01;
-        if (yy + 1 < ih) {
-            o[iw] = e10;
-            if (x1) o[iw + 1] = e11;
-        }
-    }
-}
-
-// MaxPool2d(2, 2) backward (VGG): windows do not overlap, an input element belongs to at most one
-__global__ __launch_bounds__(256) void maxpool2x2s2_bwd_kernel(float* dx, const float* dy, const float* x, int ih, int iw, int oh, int ow,
-                                                               int64_t total) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int ix = (int)(i % iw);
-        const int64_t r = i / iw;
-        const int iy = (int)(r % ih);
-        const int64_t pl = r / ih;
-        const int oy = iy / 2, ox = ix / 2;
-        float g = 0.f;
-        if (oy < oh && ox < ow) {
-            const float* xp = x + pl * ih * iw + (int64_t)(2 * oy) * iw + 2 * ox;
-            const float v00 = xp[0], v01 = xp[1], v10 = xp[iw], v11 = xp[iw + 1];
-            int best = 0;
-            float bv = v00;
-            if (v01 > bv) { bv = v01; best = 1; }
-            if (v10 > bv) { bv = v10; best = 2; }
-            if (v11 > bv) { bv = v11; best = 3; }
-            if (best == (iy & 1) * 2 + (ix & 1)) g = dy[pl * oh * ow + (int64_t)oy * ow + ox];
-        }
-        dx[i] = g;
-    }
-}
-
 // dimg (+)= scale * 2 (a - b) / numel    (gradient of scale * mean((a - b)^2) per sample)
 __global__ __launch_bounds__(256) void mse_grad_kernel(float* d, const float* a, const float* b, int64_t numel, int64_t b_bs, float k,
                                                        int accumulate, int64_t total) {
@@ -370,74 +252,6 @@ extern "C" int mgf_relu_bwd_split_f32(float* dz_a, float* dz_b, const float* dy,
     return MGF_OK;
 }
 
-namespace {
-// dx of the 3x3 / stride-2 ceil-mode pool from the forward's stored tap indices: one lane per 2 x 2 input block (2 bi, 2 bj) + {0,1}^2,
-// whose elements sit at fixed taps of the <= 4 windows around it -- (0,0): tap 8 of window (bi-1, bj-1), 6 of (bi-1, bj), 2 of
-// (bi, bj-1), 0 of (bi, bj); (0,1): 7 of (bi-1, bj), 1 of (bi, bj); (1,0): 5 of (bi, bj-1), 3 of (bi, bj); (1,1): 4 of (bi, bj) --
-// summed in ascending window order like torch.  No LDS, no input map: a stream of stores.
-__global__ __launch_bounds__(256) void maxpool3x3s2_bwd_idx_kernel(float* __restrict__ dx, const float* __restrict__ dy,
-                                                                   const uint8_t* __restrict__ idx, int ih, int iw, int oh, int ow) {
-    const int bj = blockIdx.x * 256 + threadIdx.x, bi = blockIdx.y;
-    const int64_t pl = blockIdx.z;
-    const int yy = 2 * bi, xx = 2 * bj;
-    if (xx >= iw) return;
-    const float* dp = dy + pl * oh * ow;
-    const uint8_t* ip = idx + pl * oh * ow;
-    float g[2][2];
-    int t[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int oy = bi - 1 + a, ox = bj - 1 + b;
-            const bool in = oy >= 0 && ox >= 0 && oy < oh && ox < ow;
-            g[a][b] = in ? dp[(int64_t)oy * ow + ox] : 0.f;
-            t[a][b] = in ? (int)ip[(int64_t)oy * ow + ox] : -1;
-        }
-    float e00 = 0.f, e01 = 0.f, e10 = 0.f, e11 = 0.f;
-    if (t[0][0] == 8) e00 += g[0][0];
-    if (t[0][1] == 6) e00 += g[0][1];
-    if (t[1][0] == 2) e00 += g[1][0];
-    if (t[1][1] == 0) e00 += g[1][1];
-    if (t[0][1] == 7) e01 += g[0][1];
-    if (t[1][1] == 1) e01 += g[1][1];
-    if (t[1][0] == 5) e10 += g[1][0];
-    if (t[1][1] == 3) e10 += g[1][1];
-    if (t[1][1] == 4) e11 += g[1][1];
-    float* o = dx + pl * ih * iw + (int64_t)yy * iw + xx;
-    const bool x1 = xx + 1 < iw;
-    o[0] = e00;
-    if (x1) o[1] = e01;
-    if (yy + 1 < ih) {
-        o[iw] = e10;
-        if (x1) o[iw + 1] = e11;
-    }
-}
-}  // namespace
-
-extern "C" int mgf_maxpool3x3s2_ceil_bwd_idx_f32(float* dx, const float* dy, const uint8_t* idx, int32_t nc, int32_t in_h, int32_t in_w,
-                                                 int32_t out_h, int32_t out_w, mgf_stream_t stream) {
-    MGF_REQUIRE(dx && dy && idx && nc >= 1 && in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1, MGF_EINVAL, "maxpool3x3s2_ceil_bwd_idx: bad arguments");
-    MGF_REQUIRE(2 * (out_h - 1) < in_h && 2 * (out_w - 1) < in_w, MGF_EINVAL, "maxpool3x3s2_ceil_bwd_idx: output extent does not match the input");
-    MGF_REQUIRE(nc <= 65535 && (in_h + 1) / 2 <= 65535, MGF_ETOOBIG, "maxpool3x3s2_ceil_bwd_idx: at most 65535 planes and 131070 rows");
-    const dim3 grid((unsigned)mgf_cdiv((in_w + 1) / 2, 256), (unsigned)((in_h + 1) / 2), nc);
-    hipLaunchKernelGGL(maxpool3x3s2_bwd_idx_kernel, grid, dim3(256), 0, (hipStream_t)stream, dx, dy, idx, in_h, in_w, out_h, out_w);
-    MGF_CHECK_LAUNCH("maxpool3x3s2_ceil_bwd_idx");
-    return MGF_OK;
-}
-
-extern "C" int mgf_maxpool3x3s2_ceil_bwd_f32(float* dx, const float* dy, const float* x, int32_t nc, int32_t in_h, int32_t in_w, int32_t out_h,
-                                             int32_t out_w, mgf_stream_t stream) {
-    MGF_REQUIRE(dx && dy && x && nc >= 1 && in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1, MGF_EINVAL, "maxpool3x3s2_ceil_bwd: bad arguments");
-    MGF_REQUIRE(2 * (out_h - 1) < in_h && 2 * (out_w - 1) < in_w, MGF_EINVAL, "maxpool3x3s2_ceil_bwd: output extent does not match the input");
-    const int tiles_x = (int)mgf_cdiv(in_w, MPTX), tiles_y = (int)mgf_cdiv(in_h, MPTY);
-    MGF_REQUIRE((int64_t)nc * tiles_x * tiles_y <= INT32_MAX, MGF_ETOOBIG, "maxpool3x3s2_ceil_bwd: too many tiles");
-    hipLaunchKernelGGL(maxpool3x3s2_bwd_kernel, dim3((unsigned)((int64_t)nc * tiles_x * tiles_y)), dim3(256), 0, (hipStream_t)stream, dx, dy, x,
-                       in_h, in_w, out_h, out_w, tiles_x, tiles_y);
-    MGF_CHECK_LAUNCH("maxpool3x3s2_ceil_bwd");
-    return MGF_OK;
-}
-
 extern "C" int mgf_mse_grad_f32(float* d, const float* a, const float* b, int32_t n, int64_t numel, int64_t b_batch_stride, float scale,
                                 int32_t accumulate, mgf_stream_t stream) {
     MGF_REQUIRE(d && a && b && n >= 1 && numel >= 1, MGF_EINVAL, "mse_grad: bad arguments");
@@ -445,17 +259,5 @@ extern "C" int mgf_mse_grad_f32(float* d, const float* a, const float* b, int32_
     hipLaunchKernelGGL(mse_grad_kernel, dim3(mgf_stream_grid(total, 256, 4)), dim3(256), 0, (hipStream_t)stream, d, a, b, numel, b_batch_stride,
                        2.f * scale / (float)numel, accumulate, total);
     MGF_CHECK_LAUNCH("mse_grad");
-    return MGF_OK;
-}
-
-extern "C" int mgf_maxpool_s2_floor_bwd_f32(float* dx, const float* dy, const float* x, int32_t nc, int32_t in_h, int32_t in_w, int32_t ksize,
-                                            mgf_stream_t stream) {
-    MGF_REQUIRE(dx && dy && x && nc >= 1 && (ksize == 2 || ksize == 3) && in_h >= ksize && in_w >= ksize, MGF_EINVAL, "maxpool_s2_floor_bwd: bad arguments");
-    const int out_h = (in_h - ksize) / 2 + 1, out_w = (in_w - ksize) / 2 + 1;
-    if (ksize == 3) return mgf_maxpool3x3s2_ceil_bwd_f32(dx, dy, x, nc, in_h, in_w, out_h, out_w, stream);      // same rule, fewer windows
-    const int64_t total = (int64_t)nc * in_h * in_w;
-    hipLaunchKernelGGL(maxpool2x2s2_bwd_kernel, dim3(mgf_stream_grid(total, 256, 2)), dim3(256), 0, (hipStream_t)stream, dx, dy, x, in_h, in_w,
-                       out_h, out_w, total);
-    MGF_CHECK_LAUNCH("maxpool_s2_floor_bwd");
     return MGF_OK;
 }

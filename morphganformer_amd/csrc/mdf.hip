@@ -29,19 +29,9 @@ constexpr int MDF_MAX_C = 128;                    // discriminator width N
 constexpr int MDF_MAX_SLOTS = 27;                 // 9 discriminators x 3 taps
 typedef const float __attribute__((address_space(4)))* mdf_cfp;   // weights through the scalar cache: every lane reads the same value
 
-// fixed-order sum of one float64 per lane over the workgroup (256 lanes); not mgf_block_sum_256 of mgf_common.h: a halving tree in LDS, another order
-__device__ __forceinline__ double mdf_block_sum(double v, double* red) {
-    const int t = threadIdx.y * MDF_BX + threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = MDF_BX * MDF_BY / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
+// the workgroup's 64 x 4 lanes as the thread index 0..255 of mgf_block_tree_sum_256 (mgf_common.h)
+static_assert(MDF_BX * MDF_BY == 256, "mgf_block_tree_sum_256");
+__device__ __forceinline__ int mdf_lane() { return (int)(threadIdx.y * MDF_BX + threadIdx.x); }
 
 // x1[n, co] = lrelu(b[co] + sum_{ci,kh,kw} w[co, ci, kh, kw] img[n, ci, y + kh - 1, x + kw - 1]) on the whole frame (zero padding);
 // part[n][blk] = sum over the ring-1 pixels of the workgroup and the channels of (x1 - x1_target)^2
@@ -77,7 +67,7 @@ __global__ __launch_bounds__(256) void mdf_head_kernel(float* __restrict__ x1, d
         }
     }
     if (part) {
-        const double s = mdf_block_sum(acc, red);
+        const double s = mgf_block_tree_sum_256(acc, red, mdf_lane());
         if (threadIdx.x == 0 && threadIdx.y == 0) part[(int64_t)n * gridDim.x * gridDim.y + blockIdx.y * gridDim.x + blockIdx.x] = s;
     }
 }
@@ -120,11 +110,11 @@ __global__ __launch_bounds__(256) void mdf_tail_kernel(float* __restrict__ x3, d
     }
     const int64_t slot = (int64_t)n * gridDim.x * gridDim.y + blockIdx.y * gridDim.x + blockIdx.x;
     if (part2) {
-        const double s = mdf_block_sum(s2, red);
+        const double s = mgf_block_tree_sum_256(s2, red, mdf_lane());
         if (threadIdx.x == 0 && threadIdx.y == 0) part2[slot] = s;
     }
     if (part3) {
-        const double s = mdf_block_sum(s3, red);
+        const double s = mgf_block_tree_sum_256(s3, red, mdf_lane());
         if (threadIdx.x == 0 && threadIdx.y == 0) part3[slot] = s;
     }
 }
@@ -143,14 +133,7 @@ __global__ __launch_bounds__(256) void mdf_finish_kernel(float* out, const doubl
         const double* p = part + ((int64_t)s * n + b) * nblk;
         double v = 0.0;
         for (int64_t k = t; k < nblk; k += 256) v += p[k];
-        red[t] = v;
-        __syncthreads();
-        for (int h = 128; h > 0; h >>= 1) {
-            if (t < h) red[t] += red[t + h];
-            __syncthreads();
-        }
-        loss += red[0] / args.count[s];               // mean over the tap, taps in the reference's order (mdfloss.py:34-43)
-        __syncthreads();
+        loss += mgf_block_tree_sum_256(v, red) / args.count[s];      // mean over the tap, taps in the reference's order (mdfloss.py:34-43)
     }
     if (t == 0) {
         const float v = (float)((double)scale * loss);

@@ -80,6 +80,20 @@ __device__ __forceinline__ T mgf_block_sum_256(T v, T* sh) {
     __syncthreads();
     return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
+// The same sum as a halving tree over 256 slots of LDS (`t`: the thread's index 0..255): another order than mgf_block_sum_256, the one the
+// float64 partial sums of DSSIM, MS-SSIM and MDF are pinned to.  Every thread gets the result; `red` is free again on return.
+template <typename T>
+__device__ __forceinline__ T mgf_block_tree_sum_256(T v, T* red, int t = threadIdx.x) {
+    red[t] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) red[t] += red[t + s];
+        __syncthreads();
+    }
+    const T r = red[0];
+    __syncthreads();
+    return r;
+}
 template <typename T>
 __device__ __forceinline__ T wave_max(T v) {
 #pragma unroll

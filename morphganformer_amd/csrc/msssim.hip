@@ -1,7 +1,7 @@
 // Multi-scale SSIM (Wang, Simoncelli, Bovik 2003, as the common libraries implement it) of the UNQUANTISED pixels p = 127.5 img + 127.5,
 // q = 127.5 target + 127.5, value and gradient, float64 from the float32 loads on -- the definition is in include/mgf.h (mgf_msssim_f32).
 //
-// Unlike DSSIM (losses.hip: dssim_cont_kernel) one pass cannot fuse value and gradient: ms = prod_j v_j^{w_j}, so the coefficient of every level's
+// Unlike DSSIM (dssim.hip: dssim_cont_kernel) one pass cannot fuse value and gradient: ms = prod_j v_j^{w_j}, so the coefficient of every level's
 // gradient, -scale w_j ms / (v_j c positions_j), needs ALL the level means first.  The launch sequence of one call, all on the caller's stream:
 //   1. msssim_pool_kernel      level j -> level j + 1 of both images, 2 x 2 mean with torch's zero padding of an odd side, float64 in scratch
 //                              (a shared target, t_batch_stride 0, is reduced once, not once per sample)
@@ -135,13 +135,8 @@ __global__ __launch_bounds__(256) void msssim_stats_kernel(double* part, const T
             acc = ms_terms<LAST>(s[0], s[1], s[2], s[3], s[4], c1, c2).s;
         }
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s2 = 128; s2 >= 1; s2 >>= 1) {
-        if ((int)threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[((int64_t)blockIdx.z * c + blockIdx.y) * gridDim.x + tile] = red[0];
+    acc = mgf_block_tree_sum_256(acc, red);
+    if (threadIdx.x == 0) part[((int64_t)blockIdx.z * c + blockIdx.y) * gridDim.x + tile] = acc;
 }
 
 // ---- 3. grid = n: v_j = sum of the level's partials / positions; per channel ms = prod v_j^{w_j} where every v_j > 0, else 0;
@@ -159,14 +154,7 @@ __global__ __launch_bounds__(256) void msssim_finish_kernel(float* out, double* 
             const double* p = part + plan.part_off[j] * gridDim.x * c + ((int64_t)blockIdx.x * c + ch) * plan.tiles[j];
             double s = 0.0;
             for (int i = threadIdx.x; i < plan.tiles[j]; i += 256) s += p[i];
-            red[threadIdx.x] = s;
-            __syncthreads();
-            for (int s2 = 128; s2 >= 1; s2 >>= 1) {
-                if ((int)threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-                __syncthreads();
-            }
-            v[j] = red[0] / plan.positions[j];
-            __syncthreads();
+            v[j] = mgf_block_tree_sum_256(s, red) / plan.positions[j];
             if (!(v[j] > 0.0)) pos = false;
         }
         if (pos) {

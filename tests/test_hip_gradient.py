@@ -582,6 +582,7 @@ def test_lpips_switches_equal_the_default_dispatch(net, size, nw, monkeypatch):
 
 
 def test_mse_grad_and_pool_bwd():
+    """(The pool half lives with the pools: tests/test_hip_maxpool.py::test_pool_bwd_ties_and_forward_shapes.)"""
     from morphganformer_amd import _lib
     L = _lib.lib()
     torch.manual_seed(3)
@@ -590,43 +591,6 @@ def test_mse_grad_and_pool_bwd():
     d = torch.ones_like(ad)
     _lib.check(L.mgf_mse_grad_f32(d.data_ptr(), ad.data_ptr(), bd.data_ptr(), 2, 243, 0, 0.5, 1, _lib.stream_ptr()))
     assert torch.allclose(d.cpu(), 1 + 0.5 * 2 * (a - b) / 243, rtol=1e-6, atol=1e-7)
-    # ceil-mode pooling with ties (ReLU zeros): the gradient must follow torch's first-maximum rule
-    # (one tile; several 64 x 32 tiles with ragged edges, odd and even sides; all-negative inputs: the -inf padding must never win)
-    for shape, neg in (((2, 4, 15, 12), False), ((1, 3, 70, 131), False), ((2, 1, 65, 64), False), ((1, 2, 33, 129), True)):
-        x = torch.relu(torch.randn(*shape))
-        x = (x - 5.0 if neg else x).requires_grad_(True)
-        y = torch.nn.functional.max_pool2d(x, 3, 2, ceil_mode=True)
-        dy = torch.randn_like(y)
-        (ref,) = torch.autograd.grad(y, x, dy)
-        xd, dyd = x.detach().cuda(), dy.cuda()
-        dx = torch.full_like(xd, float("nan"))
-        _lib.check(L.mgf_maxpool3x3s2_ceil_bwd_f32(dx.data_ptr(), dyd.data_ptr(), xd.data_ptr(), shape[0] * shape[1], shape[2], shape[3],
-                                                   y.shape[2], y.shape[3], _lib.stream_ptr()))
-        assert torch.equal(dx.cpu(), ref), shape
-        # the forward that stores each window's winning tap + the backward that reads those: same y as the plain forward, same dx
-        yd, yi = torch.empty_like(dyd), torch.empty_like(dyd)
-        taps = torch.full(dyd.shape, 255, dtype=torch.uint8, device="cuda")
-        pargs = (shape[0] * shape[1], shape[2], shape[3], y.shape[2], y.shape[3], _lib.stream_ptr())
-        _lib.check(L.mgf_maxpool3x3s2_ceil_f32(yd.data_ptr(), xd.data_ptr(), *pargs))
-        _lib.check(L.mgf_maxpool3x3s2_ceil_idx_f32(yi.data_ptr(), taps.data_ptr(), xd.data_ptr(), *pargs))
-        assert torch.equal(yd, yi) and torch.equal(yi.cpu(), y.detach()) and int(taps.max()) <= 8
-        dx2 = torch.full_like(xd, float("nan"))
-        _lib.check(L.mgf_maxpool3x3s2_ceil_bwd_idx_f32(dx2.data_ptr(), dyd.data_ptr(), taps.data_ptr(), *pargs))
-        assert torch.equal(dx2.cpu(), ref), shape
-    # forward pooling, both entries, odd and even sides, wider than one wave's 128 columns: bit-exact
-    for (c, hh, ww) in ((3, 15, 12), (2, 31, 301), (1, 8, 257), (5, 2, 3)):
-        xf = torch.randn(2, c, hh, ww)
-        want = torch.nn.functional.max_pool2d(xf, 3, 2, ceil_mode=True)
-        got = torch.empty_like(want).cuda()
-        _lib.check(L.mgf_maxpool3x3s2_ceil_f32(got.data_ptr(), xf.cuda().data_ptr(), 2 * c, hh, ww, want.shape[2], want.shape[3], _lib.stream_ptr()))
-        assert torch.equal(got.cpu(), want)
-        for k in (2, 3):
-            if hh < k or ww < k:
-                continue
-            want = torch.nn.functional.max_pool2d(xf, k, 2)
-            got = torch.empty_like(want).cuda()
-            _lib.check(L.mgf_maxpool_s2_floor_f32(got.data_ptr(), xf.cuda().data_ptr(), 2 * c, hh, ww, k, _lib.stream_ptr()))
-            assert torch.equal(got.cpu(), want)
 
 
 def test_wplus_gradient_projection_matches_autograd_adam(tiny):
